@@ -1,14 +1,16 @@
 #!/usr/bin/env python
 """bench.py -- headline benchmark of the amortised-posterior flow path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 With ``--gpus N > 1`` and no launcher environment (WORLD_SIZE unset) the script starts the N ranks itself
 (``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...`` as a child process,
 before this process touches the GPU) and forwards rank 0's JSON line; started under ``torch.distributed.run`` it is one
 rank.  Either way it asserts that the process group really has ``--gpus`` ranks and reports that number.
 
-The default run prints ONE JSON line with: the configs[1] sampling leg (`value`, `roofline`, five timed blocks in `repeats`), the other
+A plain run sets up (data, flow, the seeded warm-up fit), warms up, times the K sampling steps of the configs[1] leg below and prints
+ONE JSON line with that leg alone (`value`, `ms_per_step`, `dtype`, `config`, `roofline`); `--dump-outputs DIR` writes the draws of
+the last timed step to DIR/samples.npy (at most 60 MiB).  With `--full` the line also holds five timed blocks in `repeats`, the other
 arithmetic mode of the sampler beside it (`roofline.split_bf16_sampler`), the API level (`api`: SBI_Fitter.sample_posterior -> host
 float64), the per-object call the reference itself times (`per_object_call`), the training leg (`train`, `roofline_train`, `train.dp` =
 the same epoch loop with the RCCL all-reduce inside, a one-rank communicator at N = 1), `log_prob`, the configs[4]-shaped catalogue
@@ -21,7 +23,7 @@ examples/paper/model_testing.ipynb:1543-1554), prior-box rejection included, dri
 (sf_flow_sample: per-galaxy context table + ONE persistent launch that works first attempts and retries to the end; the
 launch is bracketed by HIP events on its stream inside the library and read back through sf_flow_sample_stats).
 value = ACCEPTED posterior samples / s over all ranks (slots that end as NaN rows are not counted); each rank owns its
-own 2 000-galaxy shard: weak scaling, no data-path collective.  The flow-train theta.x pairs/s leg
+own 2 000-galaxy shard: weak scaling, no data-path collective.  With --full the flow-train theta.x pairs/s leg
 (forward+backward+RCCL all-reduce+clip+Adam) is timed right after with the same barrier protocol ("train" object).
 
 roofline.frac is a hardware fraction (<= 1): USEFUL work -- the mask-aware FLOPs of one conditioner evaluation per
@@ -137,11 +139,18 @@ def parse():
     ap.add_argument("--skip-throughput-regime", action="store_true",
                     help="leave out the 8 x batch training launches (profiling runs: they share the bench batch's grid size)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the sampling leg of the CPU baseline")
-    ap.add_argument("--repeats", type=int, default=5, help="timed blocks of --steps sampling steps (the first one is `value`; all of them: `repeats`)")
+    ap.add_argument("--repeats", type=int, default=5, help="--full: timed blocks of --steps sampling steps (the first one is `value`; all of them: `repeats`)")
     ap.add_argument("--skip-nsf-leg", action="store_true", help="leave out the configs[2] (NSF cfg3) leg of the default run")
     ap.add_argument("--skip-lampe-leg", action="store_true", help="leave out the lampe-backend (nsfar_cfg2) leg of the default run")
     ap.add_argument("--skip-per-object", action="store_true", help="leave out the per-object posterior.sample((S,), x=X[i]) loop")
     ap.add_argument("--skip-dp", action="store_true", help="leave out the RCCL leg of the train object (communicator over the ranks; one rank at N = 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline sampling leg, run every other leg (repeats, the other sampler precision, API, per-object "
+                         "call, training, log_prob, large catalogue, CPU baseline, the configs[2] and lampe workloads); the --skip-* "
+                         "options then leave single legs out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the draws of the last timed step as DIR/samples.npy (float32, (galaxies, draws, "
+                         "theta_dim); above 60 MiB a fixed seeded subset of galaxy rows, in row order)")
     return ap.parse_args()
 
 
@@ -385,6 +394,23 @@ def note(msg):
         print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+DUMP_BYTES = 60 << 20   # --dump-outputs: at most this much over all ranks (under 64 MB with the .npy headers)
+
+
+def dump_outputs(dirname, samples, rank, world):
+    """--dump-outputs: the (galaxies, draws, theta_dim) draws of the last timed step as float32 .npy, so that two builds can
+    be compared draw for draw.  When they do not fit into this rank's share of DUMP_BYTES, a fixed seeded subset of galaxy
+    rows (the same rows in every run with the same arguments), in row order."""
+    os.makedirs(dirname, exist_ok=True)
+    rows = samples.shape[0]
+    keep = min(rows, DUMP_BYTES // world // (samples[0].numel() * 4))
+    if keep < rows:
+        idx = np.sort(np.random.default_rng(0).choice(rows, keep, replace=False))
+        samples = samples[torch.as_tensor(idx, device=samples.device)]
+    name = "samples.npy" if world == 1 else f"samples_rank{rank}.npy"
+    np.save(os.path.join(dirname, name), samples.float().cpu().numpy())
+
+
 def main():
     a = parse()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -413,14 +439,14 @@ def main():
             dist.init_process_group(backend)
         assert dist.get_world_size() == a.gpus, (dist.get_world_size(), a.gpus)
     rec = run_workload(a, world, rank, dev, gloo)
-    # ---------------- BASELINE configs[2] beside configs[1] in the default run: the coupling NSF (8 bins) on the 100k-galaxy
+    # ---------------- BASELINE configs[2] beside configs[1] in the --full run: the coupling NSF (8 bins) on the 100k-galaxy
     # 20-filter mock -- sampling, training and both roofline objects, a few steps each (the full-length line is
     # `--workload nsf_cfg3`)
-    if a.workload == "maf_cfg2" and not a.skip_nsf_leg and not a.hidden_bf16 and not a.galaxies:
+    if a.full and a.workload == "maf_cfg2" and not a.skip_nsf_leg and not a.hidden_bf16 and not a.galaxies:
         b = argparse.Namespace(**vars(a))
         b.workload, b.steps, b.warmup, b.train_steps, b.fit_steps, b.repeats = "nsf_cfg3", 4, 2, 20, 4000, 1
         b.skip_api = b.skip_large_catalogue = b.no_cpu_baseline = b.skip_per_object = b.skip_dp = True
-        b.skip_throughput_regime = True
+        b.skip_throughput_regime, b.dump_outputs = True, None
         note("configs[2] leg (NSF cfg3)")
         sub = run_workload(b, world, rank, dev, gloo)
         if rank == 0:
@@ -431,11 +457,11 @@ def main():
             rec["nsf_cfg3"]["log_prob"] = sub["log_prob"]
     # ---------------- the reference's second backend beside it (row f4): the lampe flow (zuko NSF, 8 bins) on the configs[1] mock -- a
     # few steps of sampling and training with both roofline objects (the full-length line is `--workload nsfar_cfg2`)
-    if a.workload == "maf_cfg2" and not a.skip_lampe_leg and not a.hidden_bf16 and not a.galaxies:
+    if a.full and a.workload == "maf_cfg2" and not a.skip_lampe_leg and not a.hidden_bf16 and not a.galaxies:
         b = argparse.Namespace(**vars(a))
         b.workload, b.steps, b.warmup, b.train_steps, b.repeats = "nsfar_cfg2", 5, 2, 20, 1
         b.skip_api = b.skip_large_catalogue = b.no_cpu_baseline = b.skip_per_object = b.skip_dp = True
-        b.skip_throughput_regime = True
+        b.skip_throughput_regime, b.dump_outputs = True, None
         note("lampe leg (autoregressive NSF, cfg2 mock)")
         sub = run_workload(b, world, rank, dev, gloo)
         if rank == 0:
@@ -544,6 +570,51 @@ def run_workload(a, world, rank, dev, gloo):
     busy, _ = pmc_traffic("sample_busy") if default_wl else (None, None)
 
     note(f"sampling done: {1e3 * t_samp / a.steps:.3f} ms/step, kernel {k_ms:.3f} ms, unfilled {unfilled_all}")
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, out, rank, world)
+    default_split = (not a.hidden_bf16) and wl["kind"] == "nsf" and bool(desc.get("nsf_split_sampler"))
+    kname = ("k_ar_samp16<D,NI> (16-candidate register tiles, one hyper-network sweep per transform; find / resolve rounds on the same routine)"
+             if wl["kind"] == "nsf_ar" and desc.get("sampler_tiles16") else
+             "k_ar_sample (one wave per 64 draws, one hyper-network sweep per transform)") if wl["kind"] == "nsf_ar" else \
+            (("k_maf_samp16<NB,SPAN,HM,TPW,DD,PREC=2> (16-row tiles, every product on v_mfma_f32_16x16x4_f32, first block layer folded into the input layer)" if desc.get("m16_ok") and not a.hidden_bf16 else "k_sample_persist<MafOps>")
+             if wl["kind"] == "maf" else
+             ("k_sample_persist<NsfOps<..., BF = 2>> (sampler image, split-bf16 hidden blocks)" if desc.get("nsf_split_sampler") and
+              not a.hidden_bf16 else "k_sample_persist<NsfOps>"))
+    observed_world = dist.get_world_size() if (world > 1 and dist.is_initialized()) else 1
+    observed_backend = dist.get_backend() if (world > 1 and dist.is_initialized()) else "none (single process, no process group)"
+    rec = None if rank != 0 else {
+        "metric": "posterior samples/sec (accepted, prior-box rejection included)",
+        "value": value, "unit": "samples/s", "n_gpus": world, "rccl_ranks": observed_world, "steps": a.steps, "warmup": a.warmup,
+        "ms_per_step": 1e3 * t_samp / a.steps, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": ("bf16 hidden-layer MFMA operands, f32 elsewhere" if a.hidden_bf16 else
+                  ("f32 (sampler hidden HxH blocks: split-bf16 x3, fp32 accumulate; log_prob and training: f32 throughout)"
+                   if default_split else "f32")),
+        "data": "synthetic",
+        "config": {"workload": f"{wl['label']}; sample_posterior over {M} test galaxies x {S} draws per GPU",
+                   "name": a.workload,
+                   "galaxies_per_gpu": M, "draws_per_galaxy": S, "theta_dim": D, "filters": C,
+                   "parallelism": f"one catalogue of {world * M} rows sharded over {world} GPU(s) as contiguous row blocks, no collective",
+                   "backend": observed_backend,
+                   "first_attempt_acceptance": accept, "fit_steps": a.fit_steps, "fit_final_loss": fit_loss,
+                   "launches_per_step": launches[0] / a.steps, "unfilled_slots": unfilled_all,
+                   "flow_evaluations_per_step": evals_per_launch},
+        "roofline": {"bound": "mfma", "kernel": kname + " (persistent: first attempts + retries in one launch)",
+                     "achieved": useful, "peak": PEAK_FP32_TFLOPS, "unit": "TFLOP/s",
+                     "frac": useful / PEAK_FP32_TFLOPS, "traffic": traffic, "traffic_source": traffic_src,
+                     "traffic_measured_in_this_run": False,
+                     "algorithmic_bytes_per_launch": 4.0 * D * M * S + 4.0 * C * M,
+                     "launch_ms": k_ms, "flops_per_launch": f_min * accepted_per_launch,
+                     "accepted_draws_per_launch": accepted_per_launch,
+                     "note": "achieved = USEFUL work / measured kernel time: mask-aware FLOPs of ONE conditioner evaluation per "
+                             "transform (SURVEY 8d; MAF cfg1 40030 FLOP/draw -- the least any algorithm needs; the "
+                             "reference's D-pass inverse spends 175150) x ACCEPTED draws; rejected evaluations, tile "
+                             "padding and the per-galaxy context kernel are overhead.  issue_busy = SQ counters "
+                             "of the committed PMC summary; contract_* = SURVEY "
+                             "8d's figure for the reference algorithm x accepted draws (an algorithmic ratio, can exceed 1).",
+                     "issue_busy": busy, "contract_tflops": contract, "contract_ratio": contract / PEAK_FP32_TFLOPS}}
+    if not a.full:   # a plain run: the headline leg alone
+        return rec
     # the same timed block again (same protocol: barrier + synchronize on both sides, max over ranks): run-to-run scatter of the
     # headline.  `value` stays the FIRST block (the contract's K steps); block 0 below is that block.
     block_ms = [1e3 * t_samp / a.steps]
@@ -562,7 +633,6 @@ def run_workload(a, world, rank, dev, gloo):
     # mode runs the hidden H x H blocks as split-bf16 x3 products; a coupling NSF's default is its split-bf16 sampler image and the
     # other mode is the all-fp32 image.  mode_cost: the same seed drawn in both modes, both sets re-scored by the fp32 density kernel.
     alt_leg = None
-    default_split = (not a.hidden_bf16) and wl["kind"] == "nsf" and bool(desc.get("nsf_split_sampler"))
     has_alt = (not a.hidden_bf16) and (bool(desc.get("m16_ok")) if wl["kind"] == "maf" else bool(desc.get("nsf_split_sampler")))
     if has_alt:
         from synference_amd import _lib as _sflib
@@ -860,14 +930,6 @@ def run_workload(a, world, rank, dev, gloo):
     f_train = 3.0 * wl["f_lp"]   # a training step costs 3x the log_prob figure per row
     train_tf = f_train * B / (train_kernel_ms * 1e-3) / 1e12
     ttraffic, ttraffic_src = pmc_traffic("train") if a.workload == "maf_cfg2" else (None, None)
-    kname = ("k_ar_samp16<D,NI> (16-candidate register tiles, one hyper-network sweep per transform; find / resolve rounds on the same routine)"
-             if wl["kind"] == "nsf_ar" and desc.get("sampler_tiles16") else
-             "k_ar_sample (one wave per 64 draws, one hyper-network sweep per transform)") if wl["kind"] == "nsf_ar" else \
-            (("k_maf_samp16<NB,SPAN,HM,TPW,DD,PREC=2> (16-row tiles, every product on v_mfma_f32_16x16x4_f32, first block layer folded into the input layer)" if desc.get("m16_ok") and not a.hidden_bf16 else "k_sample_persist<MafOps>")
-             if wl["kind"] == "maf" else
-             ("k_sample_persist<NsfOps<..., BF = 2>> (sampler image, split-bf16 hidden blocks)" if desc.get("nsf_split_sampler") and
-              not a.hidden_bf16 else "k_sample_persist<NsfOps>"))
-    split = default_split
     tpath = flow.train_path(B)
     tkname = ({1: "k_maf_trainc<TS,NI,NT,1> (cooperative 16-row tiles, 4 waves per 32 samples)",
                2: "k_maf_trainc<TS,NI,NT,2> (cooperative 16-row tiles, 8 waves per 64 samples)",
@@ -875,41 +937,10 @@ def run_workload(a, world, rank, dev, gloo):
                4: "sf_nsf1: context MLPs (k_mlp_*) + k_nsf1_train",
                5: "k_ar_train<NWV> (64 samples per workgroup, MFMA tiles on masked images)"}.get(tpath)
               or ("k_maf_train<HT>" if wl["kind"] == "maf" else "k_nsf_train<HT,PT>"))
-    observed_world = dist.get_world_size() if (world > 1 and dist.is_initialized()) else 1
-    observed_backend = dist.get_backend() if (world > 1 and dist.is_initialized()) else "none (single process, no process group)"
-    rec = {
-        "metric": "posterior samples/sec (accepted, prior-box rejection included)",
-        "value": value, "unit": "samples/s", "n_gpus": world,
-        "rccl_ranks": (dp.get("rccl_ranks", observed_world) if dp else observed_world), "steps": a.steps, "warmup": a.warmup,
-        "ms_per_step": 1e3 * t_samp / a.steps, "repeats": repeats, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": ("bf16 hidden-layer MFMA operands, f32 elsewhere" if a.hidden_bf16 else
-                  ("f32 (sampler hidden HxH blocks: split-bf16 x3, fp32 accumulate; log_prob and training: f32 throughout)"
-                   if split else "f32")),
-        "data": "synthetic",
-        "config": {"workload": f"{wl['label']}; sample_posterior over {M} test galaxies x {S} draws per GPU",
-                   "name": a.workload,
-                   "galaxies_per_gpu": M, "draws_per_galaxy": S, "theta_dim": D, "filters": C,
-                   "parallelism": f"one catalogue of {world * M} rows sharded over {world} GPU(s) as contiguous row blocks, no collective",
-                   "backend": observed_backend,
-                   "first_attempt_acceptance": accept, "fit_steps": a.fit_steps, "fit_final_loss": fit_loss,
-                   "launches_per_step": launches[0] / a.steps, "unfilled_slots": unfilled_all,
-                   "flow_evaluations_per_step": evals_per_launch},
-        "roofline": {"bound": "mfma", "kernel": kname + " (persistent: first attempts + retries in one launch)",
-                     "achieved": useful, "peak": PEAK_FP32_TFLOPS, "unit": "TFLOP/s",
-                     "frac": useful / PEAK_FP32_TFLOPS, "traffic": traffic, "traffic_source": traffic_src,
-                     "traffic_measured_in_this_run": False,
-                     "algorithmic_bytes_per_launch": 4.0 * D * M * S + 4.0 * C * M,
-                     "launch_ms": k_ms, "flops_per_launch": f_min * accepted_per_launch,
-                     "accepted_draws_per_launch": accepted_per_launch,
-                     "note": "achieved = USEFUL work / measured kernel time: mask-aware FLOPs of ONE conditioner evaluation per "
-                             "transform (SURVEY 8d; MAF cfg1 40030 FLOP/draw -- the least any algorithm needs; the "
-                             "reference's D-pass inverse spends 175150) x ACCEPTED draws; rejected evaluations, tile "
-                             "padding and the per-galaxy context kernel are overhead.  issue_busy = SQ counters "
-                             "of the committed PMC summary; contract_* = SURVEY "
-                             "8d's figure for the reference algorithm x accepted draws (an algorithmic ratio, can exceed 1).",
-                     "issue_busy": busy, ("fp32_sampler" if default_split else "split_bf16_sampler"): alt_leg,
-                     "contract_tflops": contract, "contract_ratio": contract / PEAK_FP32_TFLOPS},
+    rec["rccl_ranks"] = dp.get("rccl_ranks", observed_world) if dp else observed_world
+    rec["repeats"] = repeats
+    rec["roofline"]["fp32_sampler" if default_split else "split_bf16_sampler"] = alt_leg
+    rec.update({
         "roofline_train": {"bound": "mfma", "kernel": tkname,
                            "achieved": train_tf, "peak": PEAK_FP32_TFLOPS, "unit": "TFLOP/s",
                            "frac": train_tf / PEAK_FP32_TFLOPS, "traffic": ttraffic, "traffic_source": ttraffic_src,
@@ -934,7 +965,7 @@ def run_workload(a, world, rank, dev, gloo):
                                      "ms_per_step": 1e3 * t_strong / tsteps}},
         "log_prob": {"value": lp_rows, "unit": "rows/s", "rows_per_call": int(Xl.shape[0]),
                      "achieved_tflops": lp_rows * wl["f_lp"] / 1e12},
-    }
+    })
     # ---------------- BASELINE configs[4] on one GPU: 1e5 galaxies x 1000 draws through the same call (its own catalogue; the
     # few galaxies of acceptance ~1e-4 that a catalogue of this size holds put two thirds of the evaluations into the
     # find / resolve launches of the deep tail -- DESIGN.md section 3)

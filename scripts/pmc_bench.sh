@@ -10,7 +10,7 @@ for pass in "FETCH_SIZE" "WRITE_SIZE" \
             "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_ACTIVE_INST_VALU SQ_VALU_MFMA_COEXEC_CYCLES SQ_WAIT_ANY" \
             "SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_SALU SQ_INSTS_VALU_TRANS_F32 SQ_INSTS_VMEM"; do
   i=$((i+1))
-  rocprofv3 --pmc $pass --kernel-trace --output-format csv -d $RAW/p$i -- python3 bench.py $ARGS --no-cpu-baseline > $RAW/p$i.out 2> $RAW/p$i.err || { tail -5 $RAW/p$i.err; exit 1; }
+  rocprofv3 --pmc $pass --kernel-trace --output-format csv -d $RAW/p$i -- python3 bench.py $ARGS --full --no-cpu-baseline > $RAW/p$i.out 2> $RAW/p$i.err || { tail -5 $RAW/p$i.err; exit 1; }
   echo "pass $i done" >> gpurun_out/pmc_bench_$TAG.progress
 done
 python3 - "$RAW" "$TAG" "$PAT" <<'PY' | tee gpurun_out/pmc_bench_$TAG.txt

@@ -774,6 +774,29 @@ def test_bench_flop_model_of_the_autoregressive_nsf_counts_the_oracle_masks():
     assert w["kind"] == "nsf_ar" and w["K"] == 8 and w["f_lp"] == b.nsfar_flops(5, 10, 50, 5, 8)[0]
 
 
+def test_bench_dump_outputs_writes_every_draw_or_a_fixed_row_subset(tmp_path):
+    """bench.py --dump-outputs: the draws as float32 .npy, whole when they fit into 60 MiB, else the same seeded subset of galaxy
+    rows (in row order) in every run; with several ranks each rank writes its own file within its share."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod3", os.path.join(os.path.dirname(os.path.dirname(__file__)), "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    small = torch.randn(2000, 1000, 5, generator=torch.Generator().manual_seed(0))        # the default catalogue: 40 MB
+    small[7] = float("nan")                                                                  # an unfilled galaxy stays NaN
+    b.dump_outputs(str(tmp_path / "a"), small, 0, 1)
+    got = np.load(tmp_path / "a" / "samples.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small.numpy(), equal_nan=True)
+    big = torch.arange(3000 * 1000 * 8, dtype=torch.float32).reshape(3000, 1000, 8)         # 96 MB
+    for d in ("b", "c"):
+        b.dump_outputs(str(tmp_path / d), big, 0, 1)
+    sub, again = np.load(tmp_path / "b" / "samples.npy"), np.load(tmp_path / "c" / "samples.npy")
+    assert os.path.getsize(tmp_path / "b" / "samples.npy") < 64e6 and sub.shape[1:] == (1000, 8) and np.array_equal(sub, again)
+    rows = sub[:, 0, 0].astype(np.int64) // 8000
+    assert (np.diff(rows) > 0).all() and np.array_equal(sub, big.numpy()[rows])
+    b.dump_outputs(str(tmp_path / "d"), big, 1, 2)
+    assert os.path.getsize(tmp_path / "d" / "samples_rank1.npy") < 32e6
+
+
 def test_result_buffers_are_recycled_only_when_nobody_holds_them():
     """hostio.result_array: a large float64 result is handed out again once the caller has dropped it (and every view of it);
     a result that is still referenced is never touched; small arrays are not pooled."""
