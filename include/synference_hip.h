@@ -152,7 +152,7 @@ int sf_flow_inverse_from_noise(sf_flow* f, const float* z /*[B,D]*/, const float
  * (negative: error):
  *   0  split-bf16 x3 hidden blocks with fp32 accumulation (the opt-in mode of a MAF with H <= 64; the default of the coupling NSF)
  *   1  the generic all-fp32 path (the result is sf_flow_inverse_from_noise's)
- *   2  the 16-row fp32 kernels, both layers of block 0 as they are stored (SF_FUSE=0)
+ *   2  the 16-row fp32 kernels, both layers of block 0 as they are stored (span placements, and shapes without the fused form)
  *   3  the 16-row fp32 kernels with the first block layer folded into the input layer (W' = W1 W0; the default of a MAF)
  * Replaces nothing in the reference: test surface of posterior.sample's numerics (sbi_runner.py:6442). */
 int sf_flow_inverse_from_noise_sampler(sf_flow* f, const float* z /*[B,D]*/, const float* x /*[B,C]*/, int64_t B,

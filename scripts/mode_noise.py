@@ -1,9 +1,8 @@
-"""Developer probe: how far apart are two ALL-fp32 evaluations of the same draws?  The bench flow (MAF cfg1, fitted) samples 256
-galaxies x 1000 draws with the same seed through (a) the 16-row fp32 sampler, (b) the split-bf16 x3 fast mode, and -- in a second
-process started with SF_MAF16=0 -- (c) the 32-row fp32 kernels; |d log_prob| of the draws under the fp32 density kernel, the
-statistic of bench.py's split_bf16_cost.  (c) vs (a) is the floor any alternative arithmetic is measured against.
-    python scripts/mode_noise.py write OUT.npz          (run twice: plain, and with SF_MAF16=0)
-    python scripts/mode_noise.py compare A.npz B.npz"""
+"""Developer probe: how far apart are the fp32 and split-bf16 x3 evaluations of the same draws?  The bench flow (MAF cfg1,
+fitted) samples 256 galaxies x 1000 draws with the same seed through (a) the 16-row fp32 sampler and (b) the split-bf16 x3 fast
+mode; |d log_prob| of the draws under the fp32 density kernel, the statistic of bench.py's split_bf16_cost.
+    python scripts/mode_noise.py write OUT.npz
+    python scripts/mode_noise.py compare OUT.npz"""
 import os
 import sys
 
@@ -57,7 +56,7 @@ def main():
         out["sigma"] = np.asarray(est.spec.theta_std)
         np.savez(sys.argv[2], **out)
         return
-    a, b = np.load(sys.argv[2]), np.load(sys.argv[3])
+    a = np.load(sys.argv[2])
 
     def cmp(t1, l1, t2, l2, what):
         dth = (np.abs(t1 - t2) / a["sigma"]).max(-1)
@@ -65,9 +64,7 @@ def main():
         d = np.abs(l1 - l2)[same]
         print(f"{what}: compared {same.sum()}, differ {np.sum(~same)}, max |dlogp| {d.max():.3e}, p99.9 {np.quantile(d, 0.999):.3e}, "
               f"median {np.median(d):.3e}, max dtheta/sigma {dth[same].max():.3e}")
-    cmp(a["theta1"], a["lp1"], a["theta0"], a["lp0"], "A fp32 vs A split x3")
-    cmp(a["theta1"], a["lp1"], b["theta1"], b["lp1"], "A fp32 vs B fp32 (two all-fp32 kernels)")
-    cmp(b["theta1"], b["lp1"], a["theta0"], a["lp0"], "B fp32 vs A split x3")
+    cmp(a["theta1"], a["lp1"], a["theta0"], a["lp0"], "fp32 vs split x3")
 
 
 if __name__ == "__main__":

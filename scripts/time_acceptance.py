@@ -11,4 +11,4 @@ for _ in range(2): acc = f.acceptance(X, 10000, lo, hi, seed=3)
 torch.cuda.synchronize(); t0 = time.perf_counter()
 for _ in range(5): acc = f.acceptance(X, 10000, lo, hi, seed=3)
 torch.cuda.synchronize(); dt = (time.perf_counter() - t0) / 5
-print(os.environ.get("SF_FIND16S", "1"), "acceptance of 2000 contexts x 10000 draws: %.2f ms = %.2f G evals/s; mean acc %.4f" % (dt * 1e3, 2e7 / dt / 1e9, float(acc.float().mean()) / 10000))
+print("acceptance of 2000 contexts x 10000 draws: %.2f ms = %.2f G evals/s; mean acc %.4f" % (dt * 1e3, 2e7 / dt / 1e9, float(acc.float().mean()) / 10000))

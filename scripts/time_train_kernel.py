@@ -1,5 +1,5 @@
-"""Training-kernel timings: cooperative 16-row kernel (SF_TRAINC=1, default) vs the one-wave-per-tile kernel (SF_TRAINC=0).
-Run once per setting (the switch is read once per process): prints HIP-event kernel ms and wall ms per loss_grad."""
+"""Training-kernel timings: prints HIP-event kernel ms and wall ms per loss_grad of the training path the library picks at
+each batch size."""
 import os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -28,5 +28,5 @@ for B in [int(b) for b in os.environ.get("SF_PROBE_BS", "64,2048,16384,131072").
         ks.append(f.train_kernel_ms())
     torch.cuda.synchronize(); dt = (time.perf_counter() - t0) / n
     k = float(np.median(ks))
-    print(f"{KIND} SF_TRAINC={os.environ.get('SF_TRAINC','1')} path={f.train_path(B)} B={B}: kernel {k*1e3:.1f} us (min {min(ks)*1e3:.1f}), wall {dt*1e3:.3f} ms, "
+    print(f"{KIND} path={f.train_path(B)} B={B}: kernel {k*1e3:.1f} us (min {min(ks)*1e3:.1f}), wall {dt*1e3:.3f} ms, "
           f"{3*F_LP*B/(k*1e-3)/1e12:.2f} TFLOP/s = {3*F_LP*B/(k*1e-3)/157.3e12:.3f} of fp32 peak", flush=True)

@@ -159,12 +159,6 @@ void sf_flow_destroy(sf_flow* f) {
     (void)hipFree(f->d_imgC); (void)hipFree(f->d_sC1); (void)hipFree(f->d_sC2); (void)hipFree(f->d_gdstC); (void)hipFree(f->d_gsrcC); (void)hipFree(f->d_gzeroC); (void)hipFree(f->d_gpartC); (void)hipFree(f->d_gfixC); (void)hipFree(f->d_ustash);
     (void)hipFree(f->d_queue); (void)hipFree(f->d_ring); (void)hipFree(f->d_galacc); (void)hipFree(f->d_sqpart); (void)hipFree(f->d_losspart_mem); (void)hipFree(f->d_best); (void)hipHostFree(f->h_queue);
     (void)hipFree(f->d_act); (void)hipFree(f->d_rej[0]); (void)hipFree(f->d_rej[1]); (void)hipFree(f->d_cnt);
-    if (f->step_exec) (void)hipGraphExecDestroy(f->step_exec);
-    if (f->step_graph) (void)hipGraphDestroy(f->step_graph);
-    if (f->step_stream) (void)hipStreamDestroy(f->step_stream);
-    if (f->step_ev[0]) (void)hipEventDestroy(f->step_ev[0]);
-    if (f->step_ev[1]) (void)hipEventDestroy(f->step_ev[1]);
-    (void)hipFree(f->d_step_ctr); (void)hipFree(f->d_step_bc); (void)hipFree(f->d_step_rows);
   }
   delete f;
 }
@@ -632,12 +626,7 @@ static int sample_persistent(sf_flow* f, const float* x, int64_t M, int64_t S, c
   //  instead of covering a whole window: 78 ms at 256, 81 at 1 024 -- an iteration of that kernel costs 180 us, so a
   //  slot that needs hundreds of attempts is cheaper side by side in a find launch than 32 at a time in the tail; the
   //  16-row MAF kernel, 35 us per sparse iteration and 64 attempts wide, is best left at 1 024)
-  uint32_t first_window = fast16 ? 1024u : 256u;
-  {
-    static int env_w = -1;  // developer knob: SF_FIRST_WINDOW=<attempts> (power of two)
-    if (env_w < 0) { const char* e = std::getenv("SF_FIRST_WINDOW"); env_w = e ? std::atoi(e) : 0; }
-    if (env_w >= 64) first_window = (uint32_t)env_w;
-  }
+  const uint32_t first_window = fast16 ? 1024u : 256u;
   uint32_t attempt = 0, limit = ceiling < first_window ? ceiling : first_window;
   int buf = 0, stage = 0;
   double evals = 0.0;
@@ -682,9 +671,7 @@ static int sample_persistent(sf_flow* f, const float* x, int64_t M, int64_t S, c
       if (env_il < 0) { const char* e = std::getenv("SF_INTERLEAVE"); env_il = e ? std::atoi(e) : 128; }
       a.dense_G = (!cur && env_il > 0 && pending == M * S && M > 1 && (int64_t)env_il * S < (int64_t)1 << 31) ? (uint32_t)env_il : 0u;
       {
-        static int env_run = -1;  // developer knob: SF_DENSE_RUN=<draws> (0 = the kernel's tile: 16 / 32)
-        if (env_run < 0) { const char* e = std::getenv("SF_DENSE_RUN"); env_run = e ? std::atoi(e) : 0; }
-        uint32_t run = env_run > 0 ? (uint32_t)env_run : (fast16 ? 16u : 32u);
+        uint32_t run = fast16 ? 16u : 32u;  // the kernel's tile
         // (S = 1000 does not divide into tiles of 16 / 32: the largest power of two that divides S -- 8 -- still gives every
         //  tile runs of consecutive draws of few galaxies; round 4 fell back to draw-by-draw order there)
         while (run > 1 && S % (int64_t)run != 0) run >>= 1;
@@ -697,12 +684,6 @@ static int sample_persistent(sf_flow* f, const float* x, int64_t M, int64_t S, c
         a.list_log2 = k;
         a.list_mul = (uint32_t)(((1ull << k) / 128u) | 1u);   // odd: a bijection of [0, 2^k)
       }
-      static int env_sp = -1;  // developer knob: SF_SPEC_AFTER=<attempts> (0 = width grows with the attempt number only)
-      if (env_sp < 0) { const char* e = std::getenv("SF_SPEC_AFTER"); env_sp = e ? std::atoi(e) : 0; }
-      a.spec_full_after = (uint32_t)env_sp;
-      static int env_tc = -1;  // developer knob: SF_TAIL_CAP=<items> (0 = the whole iteration)
-      if (env_tc < 0) { const char* e = std::getenv("SF_TAIL_CAP"); env_tc = e ? std::atoi(e) : 0; }
-      a.tail_cap = (uint32_t)env_tc;
     }
     a.attempt = attempt; a.attempt_limit = limit; a.attempts_per_slot = 1;
     a.rejected = f->d_rej[buf];
@@ -793,9 +774,7 @@ static int sample_persistent(sf_flow* f, const float* x, int64_t M, int64_t S, c
       // average: doubling wastes at most half of a launch, a launch over the whole window up to 15/16 of it), within a
       // budget of 4M items per launch
       uint32_t A = 32;
-      static int find_div = -1;  // developer knob: SF_FIND_DIV=<d>: a round tries at most attempt / d new attempts per survivor
-      if (find_div < 0) { const char* e = std::getenv("SF_FIND_DIV"); find_div = e ? std::atoi(e) : 1; if (find_div < 1) find_div = 1; }
-      const uint32_t a_max = attempt / (uint32_t)find_div < 64u ? 64u : attempt / (uint32_t)find_div;
+      const uint32_t a_max = attempt < 64u ? 64u : attempt;
       while ((uint64_t)(2u * A) * (uint64_t)pending <= (1ull << 22) && 2u * A <= 65536u && 2u * A <= a_max) A *= 2;
       while (A > 1 && (uint64_t)attempt + A > (uint64_t)window_end) A /= 2;  // windows (and the caller's ceiling) are exact
       SF_HIP(hipMemsetAsync(f->d_best, 0xff, (size_t)pending * sizeof(uint32_t), st));
@@ -1035,7 +1014,8 @@ int sf_flow_train_epoch_dp(sf_flow* f, float* flat, const float* theta, const fl
       f->d_losspart = nullptr;
     }
   } spread(f, loss_sum, (hipStream_t)stream);
-  auto plain_step = [&](int64_t b) -> int {
+  // (a captured HIP graph of the step, replayed per batch, measured SLOWER than these back-to-back launches: DESIGN.md)
+  for (int64_t b = 0; b < n_batches; ++b) {
     f->n_sqpart = 0;
     f->prep_lite = b + 1 < n_batches;   // (the last step of the call re-tiles every image)
     int rc = sf_flow_loss_grad_rows(f, flat, theta, x, order + b * batch, batch, grad_scale, nullptr, nullptr, loss_sum, grad,
@@ -1053,100 +1033,9 @@ int sf_flow_train_epoch_dp(sf_flow* f, float* flat, const float* theta, const fl
     const int64_t step = step0 + b + 1;
     const double bc1 = 1.0 - std::pow((double)d->beta1, (double)step), bc2 = 1.0 - std::pow((double)d->beta2, (double)step);
     hipError_t e = sf_launch_adam(flat, grad, exp_avg, exp_avg_sq, scratch, (long)f->L.n_params, *d, (float)bc1, (float)bc2, max_norm,
-                                  scratch + 1, (hipStream_t)stream, nullptr, f->n_sqpart > 0 ? f->d_sqpart : nullptr, f->n_sqpart);
+                                  scratch + 1, (hipStream_t)stream, f->n_sqpart > 0 ? f->d_sqpart : nullptr, f->n_sqpart);
     f->prep_lite = false;
     if (e != hipSuccess) return hip_fail(e, "sf_launch_adam");
-    return SF_OK;
-  };
-  // ---- the step as ONE captured HIP graph, replayed per batch.  What changes from step to step -- the batch's rows and Adam's
-  // bias correction -- lives on the device: k_step_begin copies rows [ctr[0] * batch, ...) of `order` into a fixed buffer the
-  // training kernels read and computes 1 - beta^(ctr[1] + 1); k_step_end advances both counters.  The first step of a call
-  // runs the plain way (lazy allocations, function attributes); the graph is kept on the handle and captured again only when
-  // an argument changes.  OPT-IN (SF_TRAIN_GRAPH=1): measured on the bench workloads the replay is SLOWER than the four
-  // back-to-back launches it replaces -- MAF cfg1 at batch 16 384: 0.117 ms per step against 0.091, NSF cfg3: 0.370 against
-  // 0.351 (hipGraphLaunch of a 6-node graph costs more on this runtime than the launches' own overhead, which the GPU hides
-  // behind the previous step anyway).  A flow kind whose step is not capturable (the one-parameter NSF allocates inside its
-  // MLP calls) never uses it.
-  static int use_graph = -1;
-  if (use_graph < 0) { const char* e = std::getenv("SF_TRAIN_GRAPH"); use_graph = e ? std::atoi(e) : 0; }
-  int64_t b0 = 0;
-  if (use_graph && !comm && n_batches >= 4 && !f->nsf1 && !f->nsfar && !f->profiling) {
-    int rc = plain_step(0);
-    if (rc) return rc;
-    b0 = 1;
-    hipStream_t user = (hipStream_t)stream;
-    auto hip_ok = [&](hipError_t e) { return e == hipSuccess; };
-    bool ok = true;
-    if (!f->step_stream) {
-      ok = hip_ok(hipStreamCreateWithFlags(&f->step_stream, hipStreamNonBlocking)) &&
-           hip_ok(hipEventCreateWithFlags(&f->step_ev[0], hipEventDisableTiming)) &&
-           hip_ok(hipEventCreateWithFlags(&f->step_ev[1], hipEventDisableTiming)) &&
-           hip_ok(hipMalloc(&f->d_step_ctr, 2 * sizeof(long long))) && hip_ok(hipMalloc(&f->d_step_bc, 2 * sizeof(float)));
-    }
-    if (ok && f->step_rows_cap < (size_t)batch) {
-      (void)hipFree(f->d_step_rows);
-      f->d_step_rows = nullptr; f->step_rows_cap = 0;
-      ok = hip_ok(hipMalloc(&f->d_step_rows, (size_t)batch * sizeof(long long)));
-      if (ok) f->step_rows_cap = (size_t)batch;
-      if (f->step_exec) { (void)hipGraphExecDestroy(f->step_exec); f->step_exec = nullptr; }   // (the buffer moved)
-    }
-    if (ok) {
-      // (the handle's lazily grown buffers are baked into the captured kernels' arguments: a loss_grad call at a larger batch
-      //  between two epoch calls moves them, and the key must notice)
-      unsigned long long key[20] = {(unsigned long long)flat, (unsigned long long)theta, (unsigned long long)x, (unsigned long long)order,
-                                    (unsigned long long)batch, 0, (unsigned long long)exp_avg, (unsigned long long)exp_avg_sq, 0, 0, 0,
-                                    (unsigned long long)scratch, (unsigned long long)grad, (unsigned long long)loss_sum, 0, 0,
-                                    (unsigned long long)f->d_gpartC, (unsigned long long)f->d_ustash, (unsigned long long)f->d_sqpart,
-                                    (unsigned long long)f->d_gfixC};
-      std::memcpy(&key[5], &grad_scale, sizeof(float));
-      std::memcpy(&key[8], d, sizeof(sf_adam_desc) < 24 ? sizeof(sf_adam_desc) : 24);
-      std::memcpy(&key[14], &max_norm, sizeof(float));
-      // the step runs on the handle's own stream, ordered behind the caller's
-      ok = hip_ok(hipEventRecord(f->step_ev[0], user)) && hip_ok(hipStreamWaitEvent(f->step_stream, f->step_ev[0], 0));
-      const long long ctr0[2] = {1, (long long)(step0 + 1)};   // next batch, Adam steps already taken
-      ok = ok && hip_ok(hipMemcpyAsync(f->d_step_ctr, ctr0, sizeof(ctr0), hipMemcpyHostToDevice, f->step_stream)) &&
-           hip_ok(hipStreamSynchronize(f->step_stream));   // (ctr0 is a stack variable)
-      if (ok && (!f->step_exec || std::memcmp(key, f->step_key, sizeof(key)) != 0)) {
-        if (f->step_exec) { (void)hipGraphExecDestroy(f->step_exec); f->step_exec = nullptr; }
-        if (f->step_graph) { (void)hipGraphDestroy(f->step_graph); f->step_graph = nullptr; }
-        hipStream_t cs = f->step_stream;
-        bool cap = hip_ok(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
-        int rc2 = 0;
-        if (cap) {
-          if (!hip_ok(sf_launch_step_begin(reinterpret_cast<const long long*>(order), f->d_step_ctr, (long)batch, f->d_step_rows, d->beta1,
-                                           d->beta2, f->d_step_bc, cs))) rc2 = SF_ERR_HIP;
-          if (!rc2) rc2 = sf_flow_loss_grad_rows(f, flat, theta, x, reinterpret_cast<const int64_t*>(f->d_step_rows), batch, grad_scale, nullptr,
-                                                 nullptr, loss_sum, grad, nullptr, cs);
-          if (!rc2 && !hip_ok(sf_launch_adam(flat, grad, exp_avg, exp_avg_sq, scratch, (long)f->L.n_params, *d, 1.f, 1.f, max_norm,
-                                             scratch + 1, cs, f->d_step_bc, f->n_sqpart > 0 ? f->d_sqpart : nullptr, f->n_sqpart))) rc2 = SF_ERR_HIP;
-          if (!rc2 && !hip_ok(sf_launch_step_end(f->d_step_ctr, cs))) rc2 = SF_ERR_HIP;
-          hipGraph_t g = nullptr;
-          const bool ended = hip_ok(hipStreamEndCapture(cs, &g));
-          if (!rc2 && ended && g && hip_ok(hipGraphInstantiate(&f->step_exec, g, nullptr, nullptr, 0))) {
-            f->step_graph = g;
-            std::memcpy(f->step_key, key, sizeof(key));
-          } else {
-            if (g) (void)hipGraphDestroy(g);
-            f->step_exec = nullptr;
-            (void)hipGetLastError();
-          }
-        }
-      }
-      if (ok && f->step_exec) {
-        for (int64_t b = b0; b < n_batches && ok; ++b) ok = hip_ok(hipGraphLaunch(f->step_exec, f->step_stream));
-        if (!ok) return hip_fail(hipGetLastError(), "hipGraphLaunch (training step)");
-        SF_HIP(hipEventRecord(f->step_ev[1], f->step_stream));
-        SF_HIP(hipStreamWaitEvent(user, f->step_ev[1], 0));
-        f->params_set = true; f->flat_valid = false; f->ctab_x = nullptr;
-        f->packed_stale = false; f->packed16_stale = false;   // (the captured step re-tiles every image)
-        return SF_OK;
-      }
-    }
-    (void)hipGetLastError();   // capture not possible here: the rest of the epoch the plain way
-  }
-  for (int64_t b = b0; b < n_batches; ++b) {
-    int rc = plain_step(b);
-    if (rc) return rc;
   }
   return SF_OK;
 }

@@ -1,7 +1,6 @@
 // sf_inst.hip -- one translation unit per (SF_KIND, SF_HT): instantiates the inference kernels
 // for that hidden-tile count and exports plain launchers (sf_internal.h, sf_launch_*_k?_h?).
 // NS (32-sample tiles per wave) is a runtime choice among the instantiated values.
-#include <cstdlib>
 
 #include "sf_inst_templates.h"
 
@@ -16,11 +15,7 @@
 static inline bool sf_fits_lds(const SfDev& m) { return m.n_parts > 0; }
 // waves per workgroup of the LDS-staged kernels: 8 (one workgroup per CU) unless two 4-wave workgroups
 // fit the LDS side by side -- then one workgroup's staging barriers overlap the other's compute.
-// SF_WPB=4|8 overrides (diagnostics).
 static inline int sf_lds_wpb(size_t shmem_bytes) {
-  static int forced = -1;
-  if (forced < 0) { const char* e = std::getenv("SF_WPB"); forced = e ? std::atoi(e) : 0; }
-  if (forced == 4 || forced == 8) return forced;
   return 2 * shmem_bytes <= 156 * 1024 ? 4 : 8;
 }
 

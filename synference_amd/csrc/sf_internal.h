@@ -57,12 +57,6 @@ struct SfSampleArgsHost {
   // walk(i), walk = i -> i * list_mul mod 2^list_log2, repeated until the result is < n_total (cycle walking: a
   // permutation of [0, n_total)) -- consecutive items lie ~n_total / 128 entries apart, for the same reason as dense_G
   uint32_t list_mul = 0, list_log2 = 0;
-  // tail mode: entries that have failed at least this many attempts are tried at the full speculation width at once
-  // (0 = the width only grows with the attempt number)
-  uint32_t spec_full_after = 0;
-  // tail mode: speculation fills at most this many items of a workgroup iteration (0 = all of them).  A wave walks its
-  // tiles one after the other, so items beyond one tile per wave double the latency of the iteration.
-  uint32_t tail_cap = 0;
   int32_t* gal_acc = nullptr;          // optional [M]: += 1 per accepted slot of the galaxy (progress test between stages)
 #ifdef SF_Q_STATS
   // developer build: [workgroup][256][4] = {start of the iteration (10 ns since the first workgroup's start is taken on
@@ -176,16 +170,6 @@ struct sf_flow {
   long long* d_gfixC = nullptr; // SF_FIX_REPLICAS int64 gradient images (fixed-point accumulation, sf_fixacc.h)
   size_t gpartC_cap = 0;        // floats
   bool trainc_ready = false;
-  // captured training step of sf_flow_train_epoch (HIP graph: step_begin -> prep -> flow -> gather -> clip + Adam -> step_end)
-  hipGraph_t step_graph = nullptr;
-  hipGraphExec_t step_exec = nullptr;
-  hipStream_t step_stream = nullptr;     // the capture / replay stream (the caller's may be the legacy default stream)
-  hipEvent_t step_ev[2] = {nullptr, nullptr};
-  long long* d_step_ctr = nullptr;       // [2]: batch number within the epoch, Adam steps taken
-  float* d_step_bc = nullptr;            // [2]: Adam's bias corrections of the running step
-  long long* d_step_rows = nullptr;      // the running batch's rows
-  size_t step_rows_cap = 0;
-  unsigned long long step_key[20] = {0}; // what the graph was captured for
   float* d_ustash = nullptr;    // cooperative NSF training (sf_nsfc.hip): u / u' of every transform, [rows][T][16]
   size_t ustash_cap = 0;        // floats
   float* d_act = nullptr;       // activation stash (training)

@@ -2,8 +2,6 @@
 // of sf_inst.hip.
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 #include "sf_device.h"
 #include "sf_internal.h"
 
@@ -132,15 +130,9 @@ hipError_t sf_launch_ctab_k1_h2(const SfDev&, const float*, long, float*, hipStr
 hipError_t sf_launch_ctab_k1_h3(const SfDev&, const float*, long, float*, hipStream_t);
 hipError_t sf_launch_ctab_k1_h4(const SfDev&, const float*, long, float*, hipStream_t);
 
-// sample tiles per wave: SF_NS=1|2 overrides (diagnostics); default 2 while HT <= 2
+// sample tiles per wave: 2 while HT <= 2
 int sf_pick_ns(const SfDev& m, bool inverse) {
-  static int forced = -1;
-  if (forced < 0) {
-    const char* e = std::getenv("SF_NS");
-    forced = e ? std::atoi(e) : 0;
-  }
   if (m.HT > 2) return 1;
-  if (forced == 1 || forced == 2) return forced;
   // measured on MI355X: with the operand image in LDS (512-thread workgroups) one 32-sample tile per wave
   // is faster for every kernel (fewer registers, no spills); two tiles per wave only pay off when the
   // weights stream from L2 (oversized images)

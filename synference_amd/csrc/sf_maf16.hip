@@ -977,10 +977,11 @@ struct SfSamp16Args {
   SfSampleArgsHost a;
 };
 
-// TPW = draw tiles per wave and iteration (1 or 2): with 2 a workgroup takes 128 items per iteration and every wave walks
-// TWO tiles of 16 draws through each staged transform, one after the other -- the queue fetch, the image copy and their
-// barriers are paid once per 128 draws instead of once per 64 (together ~20 % of a workgroup's time at TPW = 1); between
-// transforms a tile is just its 4 registers of u and its galaxy index.
+// Draw tiles per wave and iteration: a workgroup takes 128 items per iteration and every wave walks TWO tiles of 16 draws
+// through each staged transform, one after the other -- the queue fetch, the image copy and their barriers are paid once
+// per 128 draws instead of once per 64 (together ~20 % of a workgroup's time with one tile per wave); between transforms a
+// tile is just its 4 registers of u and its galaxy index.
+#define SF_SAMP16_TPW 2
 // Offsets of the 16-row sampler image for the shapes of the unrolled kernels (D = DD, DD - 1 hidden tiles of one degree
 // group each, NB blocks), as sf_layout.cpp emits them: compile-time constants in those kernels (LDS reads with immediate
 // offsets, no descriptor loads inside a pass); the host checks them against the packer's before it picks such a kernel.
@@ -1014,10 +1015,11 @@ struct SfFix16 {
 #ifndef SF_SAMP16_WG_FUSED
 #define SF_SAMP16_WG_FUSED 4
 #endif
-template <int NB, bool SPAN, bool HM, int TPW, int DD = 0, int PREC = 0>
+template <int NB, bool SPAN, bool HM, int DD = 0, int PREC = 0>
 __global__ __launch_bounds__(256, (SPAN ? 3 : (PREC == 2 ? SF_SAMP16_WG_FUSED : 4))) void k_maf_samp16(SfSamp16Args args_in) {
   static_assert(DD == 0 || (HM && !SPAN && DD >= 2 && DD <= 5), "unrolled passes: head tile, aligned placement, D <= 5");
   using HID = SfHid16<PREC>;
+  constexpr int TPW = SF_SAMP16_TPW;
   constexpr int IPW = 64 * TPW;
   const int wave = threadIdx.x >> 6;
   // with the per-galaxy context table the context block Wc is never read: only the prefix of part A before it is staged
@@ -1589,13 +1591,8 @@ static hipError_t sf_launch16b_hook(const SfDev& m, const float* z, const float*
   return sf_sampler_fp32_for(SF_MAF) ? sf_launch16b_hook_p<NB, SPAN, HM, 1>(m, z, x, n, out, st)
                                      : sf_launch16b_hook_p<NB, SPAN, HM, 0>(m, z, x, n, out, st);
 }
-// head rows on the matrix pipe (aligned placement with the head tile in the image: D <= 8); SF_HEAD_MFMA=0 keeps the
-// per-lane dot products (A-B runs)
-static bool sf_maf16_head_mfma(const SfDev& m) {
-  static int env = -1;
-  if (env < 0) { const char* e = std::getenv("SF_HEAD_MFMA"); env = e ? std::atoi(e) : 1; }
-  return env != 0 && !m.m16_span && m.o16_wh >= 0;
-}
+// head rows on the matrix pipe (aligned placement with the head tile in the image: D <= 8); otherwise per-lane dot products
+static bool sf_maf16_head_mfma(const SfDev& m) { return !m.m16_span && m.o16_wh >= 0; }
 // false when the flow has no 16-row persistent sampler (then the sampler IS the 32-row fp32 path and sf_flow_inverse_from_noise
 // covers it)
 bool sf_maf16b_available(const SfDev& m) {
@@ -1692,7 +1689,7 @@ hipError_t sf_launch_maf_ctab16(const SfDev& m, const float* x, long M, float* t
   return hipGetLastError();
 }
 
-// SF_MAF16=0 disables the path (diagnostics / A-B runs).  A = 32 retry rounds stay on the 32-row kernel.
+// A = 32 retry rounds stay on the 32-row kernel.
 // Arithmetic of the samplers' hidden blocks (process-wide; sf_set_sampler_fp32 / environment SF_SAMPLER_FP32):
 //   1  fp32 everywhere: MAF k_maf_samp16<.., PREC = 1> (v_mfma_f32_16x16x4_f32), NSF the fp32 image
 //   0  split bf16 x3 where the flow has such an image (the opt-in fast mode of round 2-4)
@@ -1710,12 +1707,7 @@ int sf_sampler_fp32_for(int kind) {
   return g < 0 ? (kind == SF_MAF ? 1 : 0) : g;
 }
 bool sf_maf16_enabled(const SfDev& m, const SfSampleArgsHost& a) {
-  static int env = -1;
-  if (env < 0) {
-    const char* e = std::getenv("SF_MAF16");
-    env = e ? std::atoi(e) : 1;
-  }
-  return env != 0 && m.kind == SF_MAF && m.m16_ok && !m.hidden_bf16 && m.packed16 != nullptr &&
+  return m.kind == SF_MAF && m.m16_ok && !m.hidden_bf16 && m.packed16 != nullptr &&
          (a.attempts_per_slot <= 16 || a.best != nullptr);  // (find mode has no in-tile attempt groups)
 }
 
@@ -1733,38 +1725,38 @@ static int sf_resident_blocks16(const void* fn, size_t sh, int cap) {
 }
 
 // persistent sampler: no more workgroups than the chip holds (more would only queue behind the spinning ones)
-template <int NB, bool SPAN, bool HM, int TPW, int DD, int PREC>
+template <int NB, bool SPAN, bool HM, int DD, int PREC>
 static hipError_t sf_launch16q_p(const SfDev& m, const SfSampleArgsHost& a, hipStream_t st) {
   static SfAttrCache attr;
   static SfResidentCache rcache;
   const size_t sh = ((size_t)(m.ctab ? m.t16_a_tab : m.t16_a) + (size_t)SfHid16<PREC>::lds_floats(m, !SPAN)) * sizeof(float) +
-                    (SF_Q_WORDS(64 * TPW) + 96) * sizeof(unsigned int);
+                    (SF_Q_WORDS(64 * SF_SAMP16_TPW) + 96) * sizeof(unsigned int);
   if (sh > 160 * 1024) return hipErrorInvalidValue;
   int attr_dev;
   if (attr.need(attr_dev)) {
-    hipError_t e = hipFuncSetAttribute((const void*)k_maf_samp16<NB, SPAN, HM, TPW, DD, PREC>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipError_t e = hipFuncSetAttribute((const void*)k_maf_samp16<NB, SPAN, HM, DD, PREC>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return e;
     attr.set(attr_dev);
   }
   int resident = 0, cur_dev = 0;
   (void)hipGetDevice(&cur_dev);
   if (!rcache.get(cur_dev, sh, resident)) {
-    resident = sf_resident_blocks16((const void*)k_maf_samp16<NB, SPAN, HM, TPW, DD, PREC>, sh, SPAN ? 3 : (PREC == 2 ? SF_SAMP16_WG_FUSED : 4));
+    resident = sf_resident_blocks16((const void*)k_maf_samp16<NB, SPAN, HM, DD, PREC>, sh, SPAN ? 3 : (PREC == 2 ? SF_SAMP16_WG_FUSED : 4));
     rcache.put(cur_dev, sh, resident);
   }
-  long grid = (a.n_items + 64 * TPW - 1) / (64 * TPW);
+  long grid = (a.n_items + 64 * SF_SAMP16_TPW - 1) / (64 * SF_SAMP16_TPW);
   if (grid > resident) grid = resident;
   SfSamp16Args args;
   args.m = m;
   args.a = a;
-  hipLaunchKernelGGL((k_maf_samp16<NB, SPAN, HM, TPW, DD, PREC>), dim3((unsigned)grid), dim3(256), sh, st, args);
+  hipLaunchKernelGGL((k_maf_samp16<NB, SPAN, HM, DD, PREC>), dim3((unsigned)grid), dim3(256), sh, st, args);
   return hipGetLastError();
 }
-template <int NB, bool SPAN, bool HM, int TPW, int DD = 0>
+template <int NB, bool SPAN, bool HM, int DD = 0>
 static hipError_t sf_launch16q(const SfDev& m, const SfSampleArgsHost& a, hipStream_t st) {
-  if (sf_sampler_fp32_for(SF_MAF)) return sf_launch16q_p<NB, SPAN, HM, TPW, DD, 1>(m, a, st);
+  if (sf_sampler_fp32_for(SF_MAF)) return sf_launch16q_p<NB, SPAN, HM, DD, 1>(m, a, st);
   if (!m.packed16B) return hipErrorInvalidValue;
-  return sf_launch16q_p<NB, SPAN, HM, TPW, DD, 0>(m, a, st);
+  return sf_launch16q_p<NB, SPAN, HM, DD, 0>(m, a, st);
 }
 template <int NB, bool SPAN>
 static hipError_t sf_launch16(const SfDev& m, const SfSampleArgsHost& a, hipStream_t st) {
@@ -1780,17 +1772,9 @@ static hipError_t sf_launch16(const SfDev& m, const SfSampleArgsHost& a, hipStre
   hipLaunchKernelGGL((k_maf_inv16<NB, SPAN>), dim3((unsigned)((a.n_items + per_block - 1) / per_block)), dim3(256), sh, st, m, a);
   return hipGetLastError();
 }
-// SF_TPW=1: one draw tile per wave and iteration (64 items per workgroup iteration) instead of two (A-B runs)
-static int sf_maf16_tpw() {
-  static int env = -1;
-  if (env < 0) { const char* e = std::getenv("SF_TPW"); env = (e && std::atoi(e) == 1) ? 1 : 2; }
-  return env;
-}
-// the unrolled-pass kernels apply when degree p - 1 sits alone in tile p - 2 (SF_SEQ=0: the dispatching kernel, A-B runs)
+// the unrolled-pass kernels apply when degree p - 1 sits alone in tile p - 2 (otherwise: the dispatching kernel)
 static int sf_maf16_seq_d(const SfDev& m) {
-  static int env = -1;
-  if (env < 0) { const char* e = std::getenv("SF_SEQ"); env = e ? std::atoi(e) : 1; }
-  if (!env || !m.ctab || m.m16_span || m.D < 3 || m.D > 5 || m.nT16 != m.D - 1) return 0;
+  if (!m.ctab || m.m16_span || m.D < 3 || m.D > 5 || m.nT16 != m.D - 1) return 0;
   for (int p = 2; p <= m.D; ++p)
     if (m.g16_tile[p - 1] != p - 2) return 0;
   bool fits = false;  // the image offsets the unrolled kernels hard-wire
@@ -1799,33 +1783,30 @@ static int sf_maf16_seq_d(const SfDev& m) {
   return fits ? m.D : 0;
 }
 // The fused first layer (PREC = 2, sf_pass16g) applies where the fp32 unrolled kernels do and the context table carries the c0'
-// rows (SF_FUSE=0: the two-layer fp32 form, A-B runs).  Returns D (3..5) or 0.
+// rows (otherwise the two-layer fp32 form).  Returns D (3..5) or 0.
 int sf_maf16_fused_d(const SfDev& m) {
-  static int env = -1;
-  if (env < 0) { const char* e = std::getenv("SF_FUSE"); env = e ? std::atoi(e) : 1; }
-  if (!env || !sf_sampler_fp32_for(SF_MAF) || !m.ctab || m.o16_wp < 0 || m.ctab_R != 2 * m.nT16 * 16 || !sf_maf16_head_mfma(m)) return 0;
+  if (!sf_sampler_fp32_for(SF_MAF) || !m.ctab || m.o16_wp < 0 || m.ctab_R != 2 * m.nT16 * 16 || !sf_maf16_head_mfma(m)) return 0;
   return sf_maf16_seq_d(m);
 }
 template <int NB, bool SPAN, bool HM>
 static hipError_t sf_launch16q_t(const SfDev& m, const SfSampleArgsHost& a, hipStream_t st) {
-  if (sf_maf16_tpw() == 1) return sf_launch16q<NB, SPAN, HM, 1>(m, a, st);
   if constexpr (HM && !SPAN) {
     switch (sf_maf16_fused_d(m)) {
-      case 3: return sf_launch16q_p<NB, SPAN, HM, 2, 3, 2>(m, a, st);
-      case 4: return sf_launch16q_p<NB, SPAN, HM, 2, 4, 2>(m, a, st);
-      case 5: return sf_launch16q_p<NB, SPAN, HM, 2, 5, 2>(m, a, st);
+      case 3: return sf_launch16q_p<NB, SPAN, HM, 3, 2>(m, a, st);
+      case 4: return sf_launch16q_p<NB, SPAN, HM, 4, 2>(m, a, st);
+      case 5: return sf_launch16q_p<NB, SPAN, HM, 5, 2>(m, a, st);
       default: break;
     }
     // (round 5, fp32 kernels: FOUR tiles per wave and staged transform -- fetch, staging and prologue once per 256 draws -- measured
     //  2.74 ms per catalogue against 2.62 with two: the coarser iterations cost the tail more than the dense phase saves)
     switch (sf_maf16_seq_d(m)) {
-      case 3: return sf_launch16q<NB, SPAN, HM, 2, 3>(m, a, st);
-      case 4: return sf_launch16q<NB, SPAN, HM, 2, 4>(m, a, st);
-      case 5: return sf_launch16q<NB, SPAN, HM, 2, 5>(m, a, st);
+      case 3: return sf_launch16q<NB, SPAN, HM, 3>(m, a, st);
+      case 4: return sf_launch16q<NB, SPAN, HM, 4>(m, a, st);
+      case 5: return sf_launch16q<NB, SPAN, HM, 5>(m, a, st);
       default: break;
     }
   }
-  return sf_launch16q<NB, SPAN, HM, 2>(m, a, st);
+  return sf_launch16q<NB, SPAN, HM>(m, a, st);
 }
 // parity hook of the fused pass functions: theta = inverse(z | x) through k_maf_find16s<.., PREC = 2> in its given-noise mode (the
 // context table must have been built for the rows of x: item i reads table row i)
@@ -1843,13 +1824,10 @@ hipError_t sf_launch_maf_inv16(const SfDev& m, const SfSampleArgsHost& a, hipStr
     return m.NB == 1 ? sf_launch16q_t<1, false, false>(m, a, st) : sf_launch16q_t<2, false, false>(m, a, st);
   }
   // find / resolve launches of the deep tail: the unrolled split-bf16 kernel where the sampler itself runs one
-  // (SF_FIND16S=0: the fp32 kernel, A-B runs)
   const bool f32 = sf_sampler_fp32_for(SF_MAF) != 0;
   if ((a.best || a.att_list || a.count) && !a.z_in && m.ctab && (f32 || m.packed16B) && sf_maf16_head_mfma(m)) {
-    static int env = -1;
-    if (env < 0) { const char* e = std::getenv("SF_FIND16S"); env = e ? std::atoi(e) : 1; }
-    const int dd = env ? sf_maf16_seq_d(m) : 0;
-    const bool fused = env && sf_maf16_fused_d(m) > 0;
+    const int dd = sf_maf16_seq_d(m);
+    const bool fused = sf_maf16_fused_d(m) > 0;
 #define SF_FIND_CASE(NBV, DDV) \
     if (m.NB == NBV && dd == DDV) return fused ? sf_launch_find16s<NBV, DDV, 2>(m, a, st) : (f32 ? sf_launch_find16s<NBV, DDV, 1>(m, a, st) : sf_launch_find16s<NBV, DDV, 0>(m, a, st));
     SF_FIND_CASE(1, 3) SF_FIND_CASE(1, 4) SF_FIND_CASE(1, 5)

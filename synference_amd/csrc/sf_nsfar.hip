@@ -26,7 +26,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <ctime>
 #include <cstdio>
 #include <string>
 #include <vector>
@@ -1205,9 +1204,6 @@ size_t sf_nsfar_lds_bytes(const SfNsfAr& n, int hidden_buffers, int waves) {
 }
 // waves per 64 samples of the density / training kernels: four (tile pairs and dimensions dealt round robin) when the LDS takes it
 static int ar_waves(const SfNsfAr& n, int hidden_buffers) {
-  static int forced = -1;
-  if (forced < 0) { const char* e = std::getenv("SF_NSFAR_WAVES"); forced = e ? std::atoi(e) : 0; }
-  if (forced == 1 || forced == 4) return sf_nsfar_lds_bytes(n, hidden_buffers, forced) <= (size_t)160 * 1024 - 1024 ? forced : 1;
   return sf_nsfar_lds_bytes(n, hidden_buffers, 4) <= (size_t)160 * 1024 - 1024 ? 4 : 1;
 }
 
@@ -1300,11 +1296,6 @@ int sf_nsfar_sample(SfNsfAr* n, const float* x, long M, long S, const uint32_t* 
     // (16-sample waves: an open entry costs a whole 16-candidate round of ONE wave per 16 attempts once the list has run dry, so the
     //  hand-over comes early -- measured on the bench flow: window 256 / 64 / 32 / 16 -> 8.35 / 7.84 / 6.93 / 7.29 ms per catalogue)
     window = sf_nsfar16_eligible(*n) ? 32u : 256u;
-    {   // (developer knob: attempts of a slot inside the persistent launch before the chip-wide rounds take it)
-      static int w_env = -1;
-      if (w_env < 0) { const char* e = std::getenv("SF_AR_WINDOW"); w_env = e ? std::atoi(e) : 0; }
-      if (w_env >= 16 && (uint32_t)w_env < cap) window = (uint32_t)w_env / 16u * 16u;
-    }
     if ((size_t)n_slots > n->surv_cap) {
       (void)hipFree(n->d_surv[0]); (void)hipFree(n->d_surv[1]); (void)hipFree(n->d_best);
       n->d_surv[0] = n->d_surv[1] = n->d_best = nullptr; n->surv_cap = 0;
@@ -1336,22 +1327,9 @@ int sf_nsfar_sample(SfNsfAr* n, const float* x, long M, long S, const uint32_t* 
       AR_HIP(hipMemcpyAsync(h, n->d_ctr, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
       AR_HIP(hipStreamSynchronize(st));
       const unsigned int ns = reinterpret_cast<const unsigned int*>(h + 4)[cur];
-      {
-        static int dbg = -1;
-        if (dbg < 0) dbg = std::getenv("SF_AR_DEBUG") ? 1 : 0;
-        if (dbg) {
-          static double t_prev = 0.0;
-          timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts);
-          const double tn = ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
-          fprintf(stderr, "[nsfar rounds] base %u survivors %u evaluations %llu  (+%.3f ms since the previous read-back)\n", base, ns, h[2], tn - t_prev);
-          t_prev = tn;
-        }
-      }
       if (ns == 0 || base >= cap) break;
       uint32_t A = 64;
-      static int grow = -1;
-      if (grow < 0) { const char* e = std::getenv("SF_AR_GROW"); grow = e ? std::atoi(e) : 1; if (grow < 1) grow = 1; }
-      while (2u * A <= (uint32_t)grow * base && (uint64_t)(2u * A) * ns <= (1ull << 22) && 2u * A <= 65536u) A *= 2;
+      while (2u * A <= base && (uint64_t)(2u * A) * ns <= (1ull << 22) && 2u * A <= 65536u) A *= 2;
       if ((uint64_t)base + A > cap) A = (uint32_t)(((uint64_t)cap - base + 63u) / 64u * 64u);
       const uint32_t att_end = (uint64_t)base + A > cap ? cap : base + A;
       const uint32_t chunks = A / 64u;
@@ -1446,22 +1424,7 @@ int sf_nsfar_loss_grad(SfNsfAr* n, const float* flat, const float* theta, const 
   if (ev0) AR_HIP(hipEventRecord(ev0, st));
   const int nwv = ar_waves(*n, 3);
   const dim3 grid((unsigned)nwg), block(64 * nwv);
-  size_t lds = sf_nsfar_lds_bytes(*n, 3, nwv);
-  {
-    static long pad = -1;
-    if (pad < 0) { const char* e = std::getenv("SF_AR_LDS_PAD"); pad = e ? std::atol(e) : 0; }
-    lds += (size_t)pad;
-  }
-  {
-    static int dbg = -1;
-    if (dbg < 0) dbg = std::getenv("SF_AR_DEBUG") ? 1 : 0;
-    if (dbg == 1) {
-      dbg = 2;
-      int occ = -1;
-      (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_ar_train<4, true>, 256, lds);
-      fprintf(stderr, "[nsfar train] %d waves, %zu bytes of LDS per workgroup, %d workgroups per CU by the occupancy query, partial mode %d\n", nwv, lds, occ, (int)part);
-    }
-  }
+  const size_t lds = sf_nsfar_lds_bytes(*n, 3, nwv);
   if (nwv == 4) {
     if (part) hipLaunchKernelGGL((k_ar_train<4, true>), grid, block, lds, st, aa, theta, x, idx, B, grad_scale, weights, loss, loss_sum, gdst, gstride, n->d_ustash);
     else hipLaunchKernelGGL((k_ar_train<4, false>), grid, block, lds, st, aa, theta, x, idx, B, grad_scale, weights, loss, loss_sum, gdst, gstride, n->d_ustash);

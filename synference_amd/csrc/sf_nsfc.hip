@@ -904,9 +904,7 @@ size_t sf_nsfc_lds_bytes(const SfNscDev& c) {
 
 bool sf_nsfc_eligible(const SfLayout& L, bool want_dctx) {
   const SfNscDev& c = L.nsc;
-  static int env = -1;
-  if (env < 0) { const char* e = std::getenv("SF_NSFC"); env = e ? std::atoi(e) : 1; }
-  if (!env || !c.ok || want_dctx) return false;
+  if (!c.ok || want_dctx) return false;
   if (c.NT < 2 || c.NT > 5 || (c.OTQ != 6 && c.OTQ != 8) || c.NI < 1 || c.NI > 3) return false;
   return sf_nsfc_lds_bytes(c) <= (size_t)160 * 1024;
 }

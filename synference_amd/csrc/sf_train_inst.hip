@@ -1,7 +1,6 @@
 // sf_train_inst.hip -- one translation unit per SF_HT: instantiates the training kernels.
 #include "sf_train_kernels.h"
 #include <cstdio>
-#include <cstdlib>
 
 #ifndef SF_HT
 #error "compile with -DSF_HT=1..4"
@@ -58,15 +57,13 @@ static hipError_t launch_maf(const SfDev& m, const SfTrainArgs& a, size_t shmem,
 hipError_t SF_CAT(sf_launch_maf_train_h, SF_HT)(const SfDev& m, const SfTrainArgs& a, hipStream_t st) {
   const size_t buf = (size_t)(SF_JOB_HDR + (2 * SF_HT) * SF_TL) * sizeof(float), ctl = SF_PIPE_CTL * sizeof(int);
   const long tiles = (a.B + 31) / 32;
-  static int two = -1;  // SF_TRAIN_CONSUMERS=1 keeps one consumer / two buffers at every batch size
-  if (two < 0) { const char* e = std::getenv("SF_TRAIN_CONSUMERS"); two = e ? (std::atoi(e) >= 2) : 1; }
   // While the whole batch is resident with two workgroups per CU (512 tiles = batch 16 384) LDS is plentiful: four job
   // buffers and TWO consumer waves, so that the producer never waits at a hand-over (with one consumer and two buffers
   // it stalled at every job: the consumer is busy 75 % of the backward sweep).  Measured: 182 -> 172 us at batch
   // 16 384; the sweep is then bound by the producer's own chain.  Larger batches keep two buffers and one consumer:
   // four workgroups per CU matter more there (65 536 rows: 562 vs 577 us).
   const bool d8 = m.D <= 8;  // (every BASELINE shape; D up to 16 runs the same code with longer theta loops)
-  if (two && tiles <= 512 && ctl + 4 * buf <= (size_t)80 * 1024)
+  if (tiles <= 512 && ctl + 4 * buf <= (size_t)80 * 1024)
     return d8 ? launch_maf<4, 2, 8>(m, a, ctl + 4 * buf, st) : launch_maf<4, 2, SF_DMAX>(m, a, ctl + 4 * buf, st);
   return d8 ? launch_maf<2, 1, 8>(m, a, ctl + 2 * buf, st) : launch_maf<2, 1, SF_DMAX>(m, a, ctl + 2 * buf, st);
 }

@@ -904,9 +904,7 @@ bool sf_trainc_fix(int grid, long n_gradC) {
 
 bool sf_trainc_eligible(const SfLayout& L, bool want_dctx) {
   const SfTrcDev& c = L.trc;
-  static int env = -1;
-  if (env < 0) { const char* e = std::getenv("SF_TRAINC"); env = e ? std::atoi(e) : 1; }
-  if (!env || !c.ok) return false;
+  if (!c.ok) return false;
   if (L.dev.T > SF_TRC_TS_MAX || c.NI > 2 || c.NT < 1 || c.NT > 4) return false;
   if (want_dctx && c.NI > 1) return false;
   {

@@ -619,9 +619,8 @@ class SBI_Fitter:
         # by its objects, so the three statistics keep their meaning without a per-galaxy host loop
         # without log_times ONE catalogue call, then the native hand-over.  (Measured: cutting the catalogue in 2 .. 6 chunks so
         # that chunk k crosses the bus while chunk k + 1 is drawn costs more than it hides -- every chunk pays the sampler's
-        # tail: 3.6 / 3.9 / 4.3 / 4.8 ms for 1 / 2 / 3 / 4 chunks of the cfg2 catalogue.  SF_API_CHUNKS=n forces n.)
-        auto_chunks = int(os.environ.get("SF_API_CHUNKS", "0")) or 1
-        n_chunks = min(len(X), 16) if log_times else max(1, min(len(X), auto_chunks))
+        # tail: 3.6 / 3.9 / 4.3 / 4.8 ms for 1 / 2 / 3 / 4 chunks of the cfg2 catalogue.)
+        n_chunks = min(len(X), 16) if log_times else 1
         if seed is None and n_chunks > 1:
             seed = posteriors._next_seed(None)
         bounds = np.linspace(0, len(X), n_chunks + 1).astype(int)

@@ -1,5 +1,5 @@
 """Child of tests/test_gpu_train_bench_shapes.py: one loss_grad call in a fresh process, so that the environment
-variables the library reads once (SF_TRC_NG: 4- or 8-wave cooperative workgroups; SF_NSFC) select the instantiation.
+variables the library reads once (SF_TRC_NG: 4- or 8-wave cooperative workgroups; SF_GRAD_ACC) select the instantiation.
 
 argv: case name, B, output .npz.  Writes loss, grad and the training path the library reports for that batch."""
 import os
