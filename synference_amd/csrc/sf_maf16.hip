@@ -850,25 +850,66 @@ template <> struct SfHid16<1> {
 // so the two are one affine map of the finished dimensions:
 //     W1 (W0 u + c0) + b1  =  W' u + c0',     W' = (W1 o M)(W0 o M0)  [H x D],     c0' = b1 + (W1 o M) c0  [per galaxy and transform]
 // W' is computed once per parameter update (k_maf_fuse16, in fp64, rounded to fp32: image block o16_wp), c0' once per galaxy
-// behind c0 in the context table (k_maf_ctab16).  A pass then costs 4 + 4 (OT + 1) + 4 fp32 MFMAs instead of 4 + 8 (OT + 1) + 4
-// (72 instead of 112 per tile and transform for cfg1), the first block's fragments and the state of its inputs disappear
-// (LDS 22 KB instead of 32 KB per transform, 16 registers), and the dependent chain of a pass is one layer shorter.  Same
-// function of the same parameters as the two-layer form to fp32 rounding (parity rows: given noise, draw for draw).
+// behind c0 in the context table (k_maf_ctab16).
+// The first layer is not a matrix product here: a hidden unit of degree k sees u_1 .. u_k only, so a 16-input MFMA pass over it
+// would be ~90 % structural zeros.  A transform instead starts with the pre-activations of ALL its tiles in registers (c0' from
+// the table), and whenever the dimension of degree k is finished every lane adds W'[rows of tile ot, slot of degree k] . w_k
+// into each tile ot >= k - 1 (one LDS fragment and two v_pk_fma_f32 per tile; only the update of tile k - 1, the next pass's,
+// is on the dependent chain).  k_maf_fuse16 stores exactly those columns, in degree order, as one float4 per row group:
+// entry sf_wp16_entry(NT, k, ot).  A pass then costs 4 (OT + 1) + 4 fp32 MFMAs (56 per tile and transform for cfg1, against
+// 72 with the first layer on the matrix pipe and 112 unfused), and its chain is tanh -> W1[OT, OT] -> tanh -> head -> w.
+// The draw state is handed to the passes in the transform's DEGREE order (sf_transform16g): written once per transform to the
+// sample's row in LDS in physical slot order and read back by degree, every finished dimension written to its slot there --
+// the passes themselves carry no runtime slot select and no write-back into a tile-layout quad.  Same function of the same
+// parameters as the two-layer form to fp32 rounding (parity rows: given noise, draw for draw).
 // ---------------------------------------------------------------------------------------------------------------
 struct SfPass16G {
   f32x4 act[4];        // output of block 0 = input of block 1; [tile]
-  f32x4 hdone, ut;
+  f32x4 pre[4];        // block 0's pre-activation of tile ot: c0' + the rank-1 updates of the dimensions finished so far
+  f32x4 hdone;
   const float* c0p;    // this draw's c0' rows of the transform
-  const float* xr;
-  f32x4 c0n;
   bool tab;
 };
-template <int OT, int NB>
-__device__ __forceinline__ void sf_pass16g(const SfDev& m, const float* tp, const float* tpF, SfPass16G& S, int NT, int sl, float u_sl,
-                                           int lane, int g4, int next_ot) {
-  const f32x4 c0 = S.c0n;
-  if (next_ot >= 0) sf_c0_prefetch(S, next_ot, g4);
-  const float4 wp = sf_w16(tp + m.o16_wp, 1, OT, 0, lane);
+// W' fragment entry of (input degree k, hidden tile ot >= k - 1): degrees in order, each with its tiles k - 1 .. NT - 1
+__host__ __device__ constexpr int sf_wp16_entry(int NT, int k, int ot) { return (k - 1) * NT - (k - 1) * (k - 2) / 2 + ot - (k - 1); }
+// the sample's row of the draw-state scratch (floats; 20, not 16: the per-degree reads of 16 samples hit 16 different banks)
+#define SF_G16_ROW 20
+#define SF_G16_SCR (16 * SF_G16_ROW)   // per wave
+// c0' of every tile of the transform into the pre-activations (table path: requested before the staging barriers)
+template <int NT>
+__device__ __forceinline__ void sf_pre16g_load(SfPass16G& S, int g4) {
+#pragma unroll
+  for (int ot = 0; ot < NT; ++ot) S.pre[ot] = *reinterpret_cast<const f32x4*>(S.c0p + ot * 16 + 4 * g4);
+}
+// acc += w . v, as two packed FMAs
+__device__ __forceinline__ f32x4 sf_rank1(const f32x4& acc, const float4& w, float v) {
+  const f32x2 vv = {v, v};
+  const f32x2 lo = __builtin_elementwise_fma(f32x2{w.x, w.y}, vv, f32x2{acc[0], acc[1]});
+  const f32x2 hi = __builtin_elementwise_fma(f32x2{w.z, w.w}, vv, f32x2{acc[2], acc[3]});
+  return f32x4{lo[0], lo[1], hi[0], hi[1]};
+}
+// this lane's fragments of W'[., slot of degree K] for the tiles K - 1 .. NT - 1 (requested before the value they multiply exists)
+template <int NT, int K>
+struct SfWpCols {
+  float4 w[NT - K + 1];
+  __device__ __forceinline__ void load(const float* tp, int o_wp, int g4) {
+#pragma unroll
+    for (int q = 0; q <= NT - K; ++q) w[q] = *reinterpret_cast<const float4*>(tp + o_wp + sf_wp16_entry(NT, K, K - 1 + q) * 16 + 4 * g4);
+  }
+  // the finished dimension w_K into every tile that sees it: tile K - 1 first (the next pass starts from it)
+  __device__ __forceinline__ void apply(SfPass16G& S, float wv) const {
+#pragma unroll
+    for (int q = 0; q <= NT - K; ++q) S.pre[K - 1 + q] = sf_rank1(S.pre[K - 1 + q], w[q], wv);
+  }
+};
+__device__ __forceinline__ float sf_scale16(const SfDev& m, float av) {
+  return (m.scale_fn == 0 ? sf_softplus(av) : sf_sigmoid(av + 2.0f)) + m.eps;
+}
+// One pass of the fused kernels: degree group in tile OT (degree OT + 1), new dimension = degree OT + 2 in physical slot sl.
+// Returns the finished value (every row group of the sample holds it) after adding it into the later tiles.
+template <int OT, int NB, int NT>
+__device__ __forceinline__ float sf_pass16g(const SfDev& m, const float* tp, const float* tpF, SfPass16G& S, int sl, float u_in,
+                                            int lane, int g4) {
   const float4 wh = sf_w16(tp + m.o16_wh, NT, 0, OT, lane);
   float4 fw[OT + 1];
   f32x4 b1;
@@ -877,41 +918,69 @@ __device__ __forceinline__ void sf_pass16g(const SfDev& m, const float* tp, cons
 #pragma unroll
     for (int it = 0; it <= OT; ++it) fw[it] = sf_w16f<true>(tpF, NT, OT, it, lane);
   }
+  SfWpCols<NT, (OT + 2 <= NT ? OT + 2 : NT)> wu;   // (the last pass's dimension feeds nothing)
+  if constexpr (OT + 2 <= NT) wu.load(tp, m.o16_wp, g4);
   __builtin_amdgcn_sched_barrier(0);
-  const f32x4 b = sf_mma16(wp, S.ut, c0);   // the first block's pre-activation (tanh pre-scale folded in like every hidden block)
   if (NB == 2) {
 #pragma unroll
     for (int it = 0; it < OT; ++it) b1 = sf_mma16(fw[it], S.act[it], b1);   // tiles finished in earlier passes: not on the chain
   }
-  f32x4 last = sf_tanh4(b);
+  f32x4 last = sf_tanh4(S.pre[OT]);
   if (NB == 2) {
     S.act[OT] = last;
     b1 = sf_mma16(fw[OT], last, b1);
     last = sf_tanh4(b1);
   }
-  const f32x4 fresh = sf_mma16(wh, last, S.hdone);
-  if (next_ot != OT) S.hdone = fresh;
+  S.hdone = sf_mma16(wh, last, S.hdone);
   const bool odd = (sl & 1) != 0;
   const int src = (lane & 15) + 16 * (sl >> 1);
-  const float av = __shfl(odd ? fresh[2] : fresh[0], src, 64);
-  const float mv = __shfl(odd ? fresh[3] : fresh[1], src, 64);
-  const float sc = (m.scale_fn == 0 ? sf_softplus(av) : sf_sigmoid(av + 2.0f)) + m.eps;
-  const float wv = sf_div(u_sl - mv, sc);
+  const float av = __shfl(odd ? S.hdone[2] : S.hdone[0], src, 64);
+  const float mv = __shfl(odd ? S.hdone[3] : S.hdone[1], src, 64);
+  const float wv = sf_div(u_in - mv, sf_scale16(m, av));
+  if constexpr (OT + 2 <= NT) wu.apply(S, wv);
+  return wv;
+}
+// One transform of one tile of 16 draws (k_maf_samp16 / k_maf_find16s, PREC 2).  u: the draw in tile layout (lane (s, g4) holds
+// physical slots 4 g4 .. 4 g4 + 3), in and out; scr: the sample's row of the wave's scratch; S.pre: c0' of the transform,
+// S.hdone: the head biases.
+template <int NB, int DD>
+__device__ __forceinline__ void sf_transform16g(const SfDev& m, const float* tp, const float* tpF, SfPass16G& S, int dsl, f32x4& u,
+                                                float* scr, int lane, int g4) {
+  constexpr int NT = DD - 1;
+  // the 4 row groups write the same row: afterwards every lane reads any slot of its sample (one per degree, slots in SGPRs)
+  *reinterpret_cast<f32x4*>(scr + 4 * g4) = u;
+  int sl[DD];
+  float ud[DD];
 #pragma unroll
-  for (int r = 0; r < 4; ++r) S.ut[r] = (g4 == (sl >> 2) && r == (sl & 3)) ? wv : S.ut[r];
+  for (int q = 0; q < DD; ++q) {
+    sl[q] = __builtin_amdgcn_readlane(dsl, q);
+    ud[q] = scr[sl[q]];
+  }
+  {
+    // degree 1 depends on the context only (head bias)
+    SfWpCols<NT, 1> wu;
+    wu.load(tp, m.o16_wp, g4);
+    const float av = tp[m.o16_hvb + 2 * sl[0]], mv = tp[m.o16_hvb + 2 * sl[0] + 1];
+    const float wv = sf_div(ud[0] - mv, sf_scale16(m, av));
+    wu.apply(S, wv);
+    scr[sl[0]] = wv;
+  }
+  auto pass = [&](auto otc) {
+    constexpr int OT = decltype(otc)::value;
+    scr[sl[OT + 1]] = sf_pass16g<OT, NB, NT>(m, tp, tpF, S, sl[OT + 1], ud[OT + 1], lane, g4);
+  };
+  pass(std::integral_constant<int, 0>{});
+  if constexpr (DD >= 3) pass(std::integral_constant<int, 1>{});
+  if constexpr (DD >= 4) pass(std::integral_constant<int, 2>{});
+  if constexpr (DD >= 5) pass(std::integral_constant<int, 3>{});
+  u = *reinterpret_cast<const f32x4*>(scr + 4 * g4);
 }
 template <> struct SfHid16<2> {
   using State = SfPass16G;
-  template <int OT, int NB, bool CP, bool HM>
-  static __device__ __forceinline__ void pass(const SfDev& m, const float* tp, const void* tpH, State& S, int NT, int sl, float u_sl,
-                                              int lane, int g4, int next_ot) {
-    static_assert(CP && HM, "fused first layer: unrolled kernels only (aligned placement, head tile)");
-    sf_pass16g<OT, NB>(m, tp, static_cast<const float*>(tpH), S, NT, sl, u_sl, lane, g4, next_ot);
-  }
-  template <bool SEQ, bool HM>
-  static __device__ __forceinline__ void clear(State&) {}   // (a pass reads tiles 0 .. OT of its own tile and transform only)
-  // LDS floats behind part A: the SECOND block's fragments on and below the diagonal (the first block lives in W')
-  static __host__ __device__ int lds_floats(const SfDev& m, bool /*cp*/) { return m.NB >= 2 ? m.nT16 * (m.nT16 + 1) / 2 * 256 : 0; }
+  // LDS floats behind part A: the SECOND block's fragments on and below the diagonal (the first block lives in W'), then the
+  // draw-state scratch of the four waves
+  static __host__ __device__ int blk_floats(const SfDev& m) { return m.NB >= 2 ? m.nT16 * (m.nT16 + 1) / 2 * 256 : 0; }
+  static __host__ __device__ int lds_floats(const SfDev& m, bool /*cp*/) { return blk_floats(m) + 4 * SF_G16_SCR; }
 };
 
 // Staging of one transform's operands (all four waves; the caller brackets it with barriers): part A of the fp32 image
@@ -1010,8 +1079,10 @@ struct SfFix16 {
 // with the tile of each known at compile time (pass p works on tile p - 2) -- no dispatch, and the per-tile state is
 // updated in place instead of being copied into the registers every arm of the switch has to agree on.
 // PREC: operand form of the hidden H x H blocks (SfHid16): 0 = split bf16 x3, 1 = fp32.
-// Workgroups per CU of the fused-first-layer kernel (PREC 2: 25 KB of LDS, 106 VGPRs).  Five fit once the compiler is held
-// to 96 VGPRs (94 used, no scratch), and measured SLOWER on the headline workload: 2.11-2.15 ms against 2.06 ms with four.
+// Workgroups per CU of the fused-first-layer kernel (PREC 2, D = 5: 30 KB of LDS with the draw-state scratch, 124 VGPRs with the
+// pre-activations of every tile in registers).  Round 5, first layer still on the matrix pipe (106 VGPRs): five fit once the
+// compiler is held to 96 VGPRs (94 used, no scratch), and measured SLOWER on the headline workload: 2.11-2.15 ms against 2.06 ms
+// with four.
 #ifndef SF_SAMP16_WG_FUSED
 #define SF_SAMP16_WG_FUSED 4
 #endif
@@ -1127,7 +1198,8 @@ __global__ __launch_bounds__(256, (SPAN ? 3 : (PREC == 2 ? SF_SAMP16_WG_FUSED : 
       // slot table of the transform and (table path) c0 of the first tile's first MFMA pass
       const int dsl = (int)m.cst[m.c_dslot + t * SF_DMAX + s];
       S.c0p = S.tab ? m.ctab + ((size_t)gal_cur * m.T + t) * m.ctab_R + (PREC == 2 ? m.nT16 * 16 : 0) : nullptr;
-      if (HM && S.tab) sf_c0_prefetch(S, (int)((tile_bits >> 2) & 3u), g4);
+      if constexpr (PREC == 2) sf_pre16g_load<DD - 1>(S, g4);   // (fused: c0' of every tile, the pre-activations' start)
+      else if (HM && S.tab) sf_c0_prefetch(S, (int)((tile_bits >> 2) & 3u), g4);
 #ifdef SF_Q_STATS
       { const unsigned long long n = __builtin_amdgcn_s_memrealtime(); qs_ph[qs_o + (t == m.T - 1 ? 1 : 3)] += n - qs_t_mark; qs_t_mark = n; }
 #endif
@@ -1148,52 +1220,58 @@ __global__ __launch_bounds__(256, (SPAN ? 3 : (PREC == 2 ? SF_SAMP16_WG_FUSED : 
         if (tile_has_work) {
           if (j > 0) {  // (tile 0's requests went out before the staging barriers)
             S.c0p = S.tab ? m.ctab + ((size_t)gal_cur * m.T + t) * m.ctab_R + (PREC == 2 ? m.nT16 * 16 : 0) : nullptr;
-            if (HM && S.tab) sf_c0_prefetch(S, (int)((tile_bits >> 2) & 3u), g4);
+            if constexpr (PREC == 2) sf_pre16g_load<DD - 1>(S, g4);
+            else if (HM && S.tab) sf_c0_prefetch(S, (int)((tile_bits >> 2) & 3u), g4);
           }
-          S.xr = a.x + gal_cur * m.C;
-          HID::template clear<(DD > 0), HM>(S);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) S.ut[r] = 0.f;
           if (HM) S.hdone = sf_ld4(tp + m.o16_bh + g4 * 4);
-          {
-            const int sl = __builtin_amdgcn_readlane(dsl, 0);
-            const float av = tp[m.o16_hvb + 2 * sl], mv = tp[m.o16_hvb + 2 * sl + 1];
-            const float sc = (m.scale_fn == 0 ? sf_softplus(av) : sf_sigmoid(av + 2.0f)) + m.eps;
-            const float wv = sf_div(sf_slot16_own(u_cur, sl) - mv, sc);
+          if constexpr (PREC == 2) {
+            float* scr = (float*)tpB + HID::blk_floats(m) + wave * SF_G16_SCR + s * SF_G16_ROW;
+            sf_transform16g<NB, DD>(m, tp, static_cast<const float*>(tpB), S, dsl, u_cur, scr, lane, g4);
+          } else {
+            S.xr = a.x + gal_cur * m.C;
+            HID::template clear<(DD > 0), HM>(S);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) S.ut[r] = (g4 == (sl >> 2) && r == (sl & 3)) ? wv : S.ut[r];
-          }
-          if constexpr (DD > 0) {
-            auto seq_pass = [&](auto otc) {
-              constexpr int OT = decltype(otc)::value;
-              const int sl = __builtin_amdgcn_readlane(dsl, OT + 1);
-              HID::template pass<OT, NB, true, true>(m, tp, tpB, S, NT, sl, sf_slot16_own(u_cur, sl), lane, g4, OT + 2 < DD ? OT + 1 : -1);
-            };
-            seq_pass(std::integral_constant<int, 0>{});
-            if constexpr (DD >= 3) seq_pass(std::integral_constant<int, 1>{});
-            if constexpr (DD >= 4) seq_pass(std::integral_constant<int, 2>{});
-            if constexpr (DD >= 5) seq_pass(std::integral_constant<int, 3>{});
-          } else
-          for (int p = 2; p <= m.D; ++p) {
-            const int sl = __builtin_amdgcn_readlane(dsl, p - 1);
-            const float u_sl = sf_slot16_own(u_cur, sl);  // (only the owning row group keeps what is computed from it)
-            const uint32_t hi_t = (tile_bits >> (2 * (p - 1))) & 3u;
-            const uint32_t lo_t = SPAN ? (lo_bits >> (2 * (p - 1))) & 3u : hi_t;
-            const int nx = p < m.D ? (int)((tile_bits >> (2 * p)) & 3u) : -1;  // tile of the next pass (aligned placement)
-            switch (lo_t * 4 + hi_t) {
-              case 0: HID::template pass<0, NB, !SPAN, HM>(m, tp, tpB, S, NT, sl, u_sl, lane, g4, nx); break;
-              case 5: HID::template pass<1, NB, !SPAN, HM>(m, tp, tpB, S, NT, sl, u_sl, lane, g4, nx); break;
-              case 10: HID::template pass<2, NB, !SPAN, HM>(m, tp, tpB, S, NT, sl, u_sl, lane, g4, nx); break;
-              case 15: HID::template pass<3, NB, !SPAN, HM>(m, tp, tpB, S, NT, sl, u_sl, lane, g4, nx); break;
-              case 1: if constexpr (SPAN) HID::template span<0, 1, NB>(m, tp, tpB, S, NT, sl, u_sl, lane, g4); break;
-              case 2: if constexpr (SPAN) HID::template span<0, 2, NB>(m, tp, tpB, S, NT, sl, u_sl, lane, g4); break;
-              case 3: if constexpr (SPAN) HID::template span<0, 3, NB>(m, tp, tpB, S, NT, sl, u_sl, lane, g4); break;
-              case 6: if constexpr (SPAN) HID::template span<1, 2, NB>(m, tp, tpB, S, NT, sl, u_sl, lane, g4); break;
-              case 7: if constexpr (SPAN) HID::template span<1, 3, NB>(m, tp, tpB, S, NT, sl, u_sl, lane, g4); break;
-              default: if constexpr (SPAN) HID::template span<2, 3, NB>(m, tp, tpB, S, NT, sl, u_sl, lane, g4); break;
+            for (int r = 0; r < 4; ++r) S.ut[r] = 0.f;
+            {
+              const int sl = __builtin_amdgcn_readlane(dsl, 0);
+              const float av = tp[m.o16_hvb + 2 * sl], mv = tp[m.o16_hvb + 2 * sl + 1];
+              const float sc = (m.scale_fn == 0 ? sf_softplus(av) : sf_sigmoid(av + 2.0f)) + m.eps;
+              const float wv = sf_div(sf_slot16_own(u_cur, sl) - mv, sc);
+#pragma unroll
+              for (int r = 0; r < 4; ++r) S.ut[r] = (g4 == (sl >> 2) && r == (sl & 3)) ? wv : S.ut[r];
             }
+            if constexpr (DD > 0) {
+              auto seq_pass = [&](auto otc) {
+                constexpr int OT = decltype(otc)::value;
+                const int sl = __builtin_amdgcn_readlane(dsl, OT + 1);
+                HID::template pass<OT, NB, true, true>(m, tp, tpB, S, NT, sl, sf_slot16_own(u_cur, sl), lane, g4, OT + 2 < DD ? OT + 1 : -1);
+              };
+              seq_pass(std::integral_constant<int, 0>{});
+              if constexpr (DD >= 3) seq_pass(std::integral_constant<int, 1>{});
+              if constexpr (DD >= 4) seq_pass(std::integral_constant<int, 2>{});
+              if constexpr (DD >= 5) seq_pass(std::integral_constant<int, 3>{});
+            } else
+            for (int p = 2; p <= m.D; ++p) {
+              const int sl = __builtin_amdgcn_readlane(dsl, p - 1);
+              const float u_sl = sf_slot16_own(u_cur, sl);  // (only the owning row group keeps what is computed from it)
+              const uint32_t hi_t = (tile_bits >> (2 * (p - 1))) & 3u;
+              const uint32_t lo_t = SPAN ? (lo_bits >> (2 * (p - 1))) & 3u : hi_t;
+              const int nx = p < m.D ? (int)((tile_bits >> (2 * p)) & 3u) : -1;  // tile of the next pass (aligned placement)
+              switch (lo_t * 4 + hi_t) {
+                case 0: HID::template pass<0, NB, !SPAN, HM>(m, tp, tpB, S, NT, sl, u_sl, lane, g4, nx); break;
+                case 5: HID::template pass<1, NB, !SPAN, HM>(m, tp, tpB, S, NT, sl, u_sl, lane, g4, nx); break;
+                case 10: HID::template pass<2, NB, !SPAN, HM>(m, tp, tpB, S, NT, sl, u_sl, lane, g4, nx); break;
+                case 15: HID::template pass<3, NB, !SPAN, HM>(m, tp, tpB, S, NT, sl, u_sl, lane, g4, nx); break;
+                case 1: if constexpr (SPAN) HID::template span<0, 1, NB>(m, tp, tpB, S, NT, sl, u_sl, lane, g4); break;
+                case 2: if constexpr (SPAN) HID::template span<0, 2, NB>(m, tp, tpB, S, NT, sl, u_sl, lane, g4); break;
+                case 3: if constexpr (SPAN) HID::template span<0, 3, NB>(m, tp, tpB, S, NT, sl, u_sl, lane, g4); break;
+                case 6: if constexpr (SPAN) HID::template span<1, 2, NB>(m, tp, tpB, S, NT, sl, u_sl, lane, g4); break;
+                case 7: if constexpr (SPAN) HID::template span<1, 3, NB>(m, tp, tpB, S, NT, sl, u_sl, lane, g4); break;
+                default: if constexpr (SPAN) HID::template span<2, 3, NB>(m, tp, tpB, S, NT, sl, u_sl, lane, g4); break;
+              }
+            }
+            u_cur = S.ut;
           }
-          u_cur = S.ut;
         }
         if (TPW > 1) {  // the next tile's turn (after TPW turns every tile is entry 0 under its own index again)
           const f32x4 tu = u_t[0];
@@ -1387,11 +1465,12 @@ __global__ __launch_bounds__(256, 4) void k_maf_find16s(SfDev m, SfSampleArgsHos
   }
   typename HID::State S;
   S.tab = true;
-  S.xr = nullptr;
+  if constexpr (PREC != 2) S.xr = nullptr;
   for (int t = m.T - 1; t >= 0; --t) {
     const int dsl = (int)m.cst[m.c_dslot + t * SF_DMAX + s];
     S.c0p = m.ctab + ((size_t)gal_cur * m.T + t) * m.ctab_R + (PREC == 2 ? m.nT16 * 16 : 0);
-    sf_c0_prefetch(S, 0, g4);
+    if constexpr (PREC == 2) sf_pre16g_load<DD - 1>(S, g4);
+    else sf_c0_prefetch(S, 0, g4);
     __syncthreads();
     sf_stage16<PREC, true>(m, t, m.t16_a_tab, wave);
     __syncthreads();
@@ -1402,30 +1481,36 @@ __global__ __launch_bounds__(256, 4) void k_maf_find16s(SfDev m, SfSampleArgsHos
       if (((long)blockIdx.x * 8 + j * 4 + wave) * 16 < a.n_items) {  // (wave-uniform: the tile holds an item)
         if (j > 0) {
           S.c0p = m.ctab + ((size_t)gal_cur * m.T + t) * m.ctab_R + (PREC == 2 ? m.nT16 * 16 : 0);
-          sf_c0_prefetch(S, 0, g4);
+          if constexpr (PREC == 2) sf_pre16g_load<DD - 1>(S, g4);
+          else sf_c0_prefetch(S, 0, g4);
         }
-        HID::template clear<true, true>(S);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) S.ut[r] = 0.f;
         S.hdone = sf_ld4(tp + m.o16_bh + g4 * 4);
-        {
-          const int sl = __builtin_amdgcn_readlane(dsl, 0);
-          const float av = tp[m.o16_hvb + 2 * sl], mv = tp[m.o16_hvb + 2 * sl + 1];
-          const float sc = (m.scale_fn == 0 ? sf_softplus(av) : sf_sigmoid(av + 2.0f)) + m.eps;
-          const float wv = sf_div(sf_slot16_own(u_cur, sl) - mv, sc);
+        if constexpr (PREC == 2) {
+          float* scr = (float*)tpB + HID::blk_floats(m) + wave * SF_G16_SCR + s * SF_G16_ROW;
+          sf_transform16g<NB, DD>(m, tp, static_cast<const float*>(tpB), S, dsl, u_cur, scr, lane, g4);
+        } else {
+          HID::template clear<true, true>(S);
 #pragma unroll
-          for (int r = 0; r < 4; ++r) S.ut[r] = (g4 == (sl >> 2) && r == (sl & 3)) ? wv : S.ut[r];
+          for (int r = 0; r < 4; ++r) S.ut[r] = 0.f;
+          {
+            const int sl = __builtin_amdgcn_readlane(dsl, 0);
+            const float av = tp[m.o16_hvb + 2 * sl], mv = tp[m.o16_hvb + 2 * sl + 1];
+            const float sc = (m.scale_fn == 0 ? sf_softplus(av) : sf_sigmoid(av + 2.0f)) + m.eps;
+            const float wv = sf_div(sf_slot16_own(u_cur, sl) - mv, sc);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) S.ut[r] = (g4 == (sl >> 2) && r == (sl & 3)) ? wv : S.ut[r];
+          }
+          auto seq_pass = [&](auto otc) {
+            constexpr int OT = decltype(otc)::value;
+            const int sl = __builtin_amdgcn_readlane(dsl, OT + 1);
+            HID::template pass<OT, NB, true, true>(m, tp, tpB, S, NT, sl, sf_slot16_own(u_cur, sl), lane, g4, OT + 2 < DD ? OT + 1 : -1);
+          };
+          seq_pass(std::integral_constant<int, 0>{});
+          if constexpr (DD >= 3) seq_pass(std::integral_constant<int, 1>{});
+          if constexpr (DD >= 4) seq_pass(std::integral_constant<int, 2>{});
+          if constexpr (DD >= 5) seq_pass(std::integral_constant<int, 3>{});
+          u_cur = S.ut;
         }
-        auto seq_pass = [&](auto otc) {
-          constexpr int OT = decltype(otc)::value;
-          const int sl = __builtin_amdgcn_readlane(dsl, OT + 1);
-          HID::template pass<OT, NB, true, true>(m, tp, tpB, S, NT, sl, sf_slot16_own(u_cur, sl), lane, g4, OT + 2 < DD ? OT + 1 : -1);
-        };
-        seq_pass(std::integral_constant<int, 0>{});
-        if constexpr (DD >= 3) seq_pass(std::integral_constant<int, 1>{});
-        if constexpr (DD >= 4) seq_pass(std::integral_constant<int, 2>{});
-        if constexpr (DD >= 5) seq_pass(std::integral_constant<int, 3>{});
-        u_cur = S.ut;
       }
       { const f32x4 tu = u_cur; u_cur = u_oth; u_oth = tu; }
       { const long tg = gal_cur; gal_cur = gal_oth; gal_oth = tg; }
@@ -1660,25 +1745,33 @@ __global__ __launch_bounds__(256) void k_maf_ctab16(SfDev m, const float* __rest
     }
   }
 }
-// W' = (W1 o M)(W0 o M0) of every transform, from the packed fp32 image into its o16_wp block (fp64 sums, one rounding): lane l of
-// tile ot holds W'[ot*16 + (l & 15)][4 (l >> 4) + r], the fragment layout of o16_w0.  Masked weights are structural zeros of the
-// image, and the packed first block carries the tanh pre-scale (SF_PACK_TANH_SCALE): W' and c0' inherit both.
+// W' = (W1 o M)(W0 o M0) of every transform, from the packed fp32 image into its o16_wp block (fp64 sums, one rounding), as the
+// fused kernels' rank-1 updates read it (sf_pass16g): for input degree k = 1 .. min(NT, D - 1) and hidden tile ot = k - 1 .. NT - 1,
+// entry sf_wp16_entry(NT, k, ot) = 16 floats, float4 g4 = W'[ot*16 + 4 g4 + r][slot of degree k], r = 0..3.  The other columns of
+// a tile are structural zeros (a unit of degree d sees u_1 .. u_d).  Masked weights are structural zeros of the image, and the
+// packed first block carries the tanh pre-scale (SF_PACK_TANH_SCALE): W' and c0' inherit both.
 __global__ __launch_bounds__(256) void k_maf_fuse16(SfDev m) {
-  const int t = blockIdx.x, ot = threadIdx.x >> 6, l = threadIdx.x & 63;
+  const int t = blockIdx.x;
   const int NT = m.nT16;
-  if (ot >= NT) return;
+  const int KN = NT < m.D - 1 ? NT : m.D - 1;   // (the dimension of degree D feeds nothing)
+  const int n_ent = KN * NT - KN * (KN - 1) / 2;
   float* tp = const_cast<float*>(m.packed16) + (size_t)t * m.t16_stride;
-  const int row = l & 15, sg = l >> 4;
-  double acc[4] = {0.0, 0.0, 0.0, 0.0};
-  for (int it = 0; it < NT; ++it)
-    for (int kk = 0; kk < 16; ++kk) {
-      const float wk = tp[m.o16_wk[0] + ((ot * NT + it) * 64 + row + 16 * (kk >> 2)) * 4 + (kk & 3)];   // W1[ot*16 + row][it*16 + kk]
-      const float* w0 = tp + m.o16_w0 + (it * 64 + kk + 16 * sg) * 4;                                    // W0[it*16 + kk][4 sg + r]
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[r] += (double)wk * (double)w0[r];
-    }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) tp[m.o16_wp + (ot * 64 + l) * 4 + r] = (float)acc[r];
+  for (int i = threadIdx.x; i < n_ent * 16; i += blockDim.x) {
+    const int e = i >> 4, g4 = (i >> 2) & 3, r = i & 3;
+    int k = 1;
+    while (k < KN && e >= sf_wp16_entry(NT, k + 1, k)) ++k;
+    const int ot = k - 1 + (e - sf_wp16_entry(NT, k, k - 1));
+    const int row = 4 * g4 + r;
+    const int col = (int)m.cst[m.c_dslot + t * SF_DMAX + k - 1];
+    double acc = 0.0;
+    for (int it = 0; it < NT; ++it)
+      for (int kk = 0; kk < 16; ++kk) {
+        const float wk = tp[m.o16_wk[0] + ((ot * NT + it) * 64 + row + 16 * (kk >> 2)) * 4 + (kk & 3)];   // W1[ot*16 + row][it*16 + kk]
+        const float w0 = tp[m.o16_w0 + (it * 64 + kk + 16 * (col >> 2)) * 4 + (col & 3)];                // W0[it*16 + kk][col]
+        acc += (double)wk * (double)w0;
+      }
+    tp[m.o16_wp + e * 16 + g4 * 4 + r] = (float)acc;
+  }
 }
 hipError_t sf_launch_maf_fuse16(const SfDev& m, hipStream_t st) {
   hipLaunchKernelGGL(k_maf_fuse16, dim3((unsigned)m.T), dim3(256), 0, st, m);
