@@ -410,6 +410,28 @@ int sf_scatter_depths(const float* flux /*[N,C]*/, int64_t N, int32_t C, const f
 int sf_pit_ranks(const float* samples /*[N,S,D]*/, const float* truth /*[N,D]*/, int64_t N, int64_t S, int32_t D,
                  float* out /*[N,D]*/, void* stream);
 
+/* TARP expected-coverage curves (Lemos et al. 2023, "Sampling-Based Accuracy Testing of Posterior Estimators"), restated from
+ * the paper -- the reference calls the third-party `tarp` package: get_tarp_coverage(samples, y, norm=True, bootstrap=True,
+ * num_bootstrap=200).  Per pass b over a row list idx[b,:] and reference points r[b,j,:], with i = idx[b,j]:
+ *   counts[b,j] = #{ s : dist(r, samples[i,s,:]) < dist(r, theta[i,:]) }   (a NaN draw compares false and stays in S)
+ *   ecp[b,e]    = #{ j : counts[b,j] / S < edges[e] } / N  (ecp[b,0] = 0, ecp[b,bins] = 1), edges = np.histogram's:
+ *                 linspace(min f, max f, bins + 1), min - 0.5 / max + 0.5 when they are equal.
+ * norm_axis >= 0: draws and truths become (v - low) / (high - low + 1e-10), low / high the min / max of the pass's resampled
+ * truths over the positions (0: per parameter) or over the parameters (1: per position).  num_bootstrap = B > 0: B passes,
+ * idx[b,j] = (uint64(r0) * N) >> 32 from Philox (seed, stream 3; counter (j, 0, b, 0)); 0: one pass over the rows in order.
+ * references NULL: r[b,j,d] uniform in [0,1) from Philox (seed, stream 4; counter (j, 0, b, d / 4)), else row j in every pass.
+ * 1 <= D <= 16, 1 <= S <= 8192, N >= 1, num_alpha_bins >= 1, max(B,1) * N < 2^31.  The draws are read from HBM once per call;
+ * the counts are exact integers, so two calls give the same bits.
+ * Replaces ref: sbi_runner.py:7090-7126 (calculate_TARP) and 6618-6637 (the `tarp` key of evaluate_model). */
+int sf_tarp_coverage(const float* samples /*[N,S,D] device*/, const float* theta /*[N,D] device*/,
+                     int64_t N, int64_t S, int32_t D,
+                     const float* references /*[N,D] device, or NULL: Philox stream 4*/,
+                     int32_t metric /*0 euclidean, 1 manhattan*/, int32_t norm_axis /*-1 no normalisation, 0, 1*/,
+                     int32_t num_bootstrap /*0: one pass over the rows in order*/, int32_t num_alpha_bins, uint64_t seed,
+                     double* ecp /*[max(B,1), bins+1] device*/, double* alpha /*[bins+1] device, last pass; may be NULL*/,
+                     int32_t* counts /*[max(B,1), N] device; may be NULL*/, int32_t* boot_idx /*[B,N] device, out; may be NULL*/,
+                     void* stream);
+
 /* ---- hand-over to the host ----------------------------------------------------------------
  * host_dst[i] = (double) dev_src[i], i < n: the draws of a catalogue call leave HBM as fp32 in pieces through a ring of pinned
  * staging buffers on a private copy stream and are widened into the caller's float64 array (any host memory, not necessarily

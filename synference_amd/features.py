@@ -5,7 +5,8 @@
 ``norm_mag_limit``; 1927-1932: magnitudes fainter than the limit clipped to it; 1699-1702: errors
 ``2.5 sigma / (ln 10 f)``).  ``flux_to_asinh`` is the asinh-magnitude branch (ref: src/synference/utils.py:647-704,
 used at sbi_runner.py:1718-1731) and ``scatter_depths`` the depth-noise augmentation of the library
-(ref: sbi_runner.py:580-691, 0-D / 1-D depths).  ``pit_ranks`` (ref: sbi_runner.py:7153-7158) lives here too.
+(ref: sbi_runner.py:580-691, 0-D / 1-D depths).  ``pit_ranks`` (ref: sbi_runner.py:7153-7158) and ``tarp_coverage`` (the
+coverage test behind ``calculate_TARP``, ref: sbi_runner.py:7090-7126) live here too.
 Normalisation to a reference band, extra feature columns and unit parsing stay host-side and out of scope.
 """
 from __future__ import annotations
@@ -103,3 +104,63 @@ def pit_ranks(samples: torch.Tensor, truth: torch.Tensor) -> torch.Tensor:
     out = torch.empty((N, D), dtype=torch.float32, device=s.device)
     _lib.check(_lib.load().sf_pit_ranks(_p(s), _p(t), N, S, D, _p(out), _stream(s.device)))
     return out
+
+
+def tarp_coverage(samples: torch.Tensor, theta, references="random", metric: str = "euclidean", norm: bool = False,
+                  bootstrap: bool = False, num_alpha_bins: Optional[int] = None, num_bootstrap: int = 100,
+                  seed: Optional[int] = None, norm_axis: int = 0, return_counts: bool = False):
+    """TARP expected coverage (Lemos et al. 2023) of (N,S,D) device draws against (N,D) truths: names and defaults of the
+    ``tarp`` package's ``get_tarp_coverage`` (which the reference calls at sbi_runner.py:7116-7122 with ``norm=True,
+    bootstrap=True``), restated from the paper and run on the device (``sf_tarp_coverage``; the draws are in THIS project's
+    (N,S,D) order, not the package's (S,N,D)).  Returns numpy float64 ``(ecp, alpha)``: ``ecp`` (num_bootstrap, n+1) with
+    ``bootstrap``, else (n+1,); ``alpha`` the n+1 credibility levels (of the last pass), n = ``num_alpha_bins`` or N // 10.
+    ``references``: "random" (uniform in the unit cube, Philox stream 4 of ``seed``) or an (N,D) array used in every pass.
+    ``norm_axis``: which axis ``norm`` takes the min / max of the truths over -- 0 per parameter (the paper's scaling, the
+    default), 1 per row; the package's choice is version-dependent and not pinned here.
+    ``seed=None`` draws one from numpy's global generator, as the package draws from it.  ``return_counts``: also the
+    int32 (B,N) counts #{draws closer to the reference point than the truth} and the int32 (B,N) resampled rows."""
+    import numpy as np
+    if not isinstance(samples, torch.Tensor) or samples.device.type != "cuda":
+        raise RuntimeError("tarp_coverage runs on the GPU (no CPU fallback)")
+    if samples.dim() != 3:
+        raise ValueError("samples must be (N, S, D)")
+    if metric not in ("euclidean", "manhattan"):
+        raise ValueError(f"metric must be 'euclidean' or 'manhattan', not {metric!r}")
+    if norm_axis not in (0, 1):
+        raise ValueError("norm_axis must be 0 (per parameter) or 1 (per row)")
+    s = samples.contiguous().float()
+    N, S, D = s.shape
+    t = torch.as_tensor(np.array(theta, dtype=np.float32) if not isinstance(theta, torch.Tensor) else theta)
+    t = t.to(s.device).float().reshape(N, D).contiguous()
+    if isinstance(references, str):
+        if references != "random":
+            raise ValueError("references must be 'random' or an (N, D) array")
+        refs = None
+    else:
+        refs = torch.as_tensor(np.array(references, dtype=np.float32) if not isinstance(references, torch.Tensor)
+                               else references).to(s.device).float().reshape(N, D).contiguous()
+    if num_alpha_bins is None:
+        if N < 10:
+            raise ValueError("num_alpha_bins=None takes N // 10 bins: it needs at least 10 rows")
+        num_alpha_bins = N // 10
+    n = int(num_alpha_bins)
+    B = int(num_bootstrap) if bootstrap else 0
+    if bootstrap and B < 1:
+        raise ValueError("num_bootstrap must be at least 1")
+    if seed is None:
+        seed = int(np.random.randint(0, 2 ** 31 - 1))
+    rows = max(B, 1)
+    ecp = torch.empty((rows, n + 1), dtype=torch.float64, device=s.device)
+    alpha = torch.empty((n + 1,), dtype=torch.float64, device=s.device)
+    counts = torch.empty((rows, N), dtype=torch.int32, device=s.device) if return_counts else None
+    bidx = torch.empty((B, N), dtype=torch.int32, device=s.device) if return_counts and B else None
+    _lib.check(_lib.load().sf_tarp_coverage(_p(s), _p(t), N, S, D, _p(refs), 0 if metric == "euclidean" else 1,
+                                            int(norm_axis) if norm else -1, B, n, C.c_uint64(int(seed) & (2 ** 64 - 1)),
+                                            _p(ecp), _p(alpha), _p(counts), _p(bidx), _stream(s.device)))
+    e = ecp.cpu().numpy()
+    e = e if bootstrap else e[0]
+    if not return_counts:
+        return e, alpha.cpu().numpy()
+    if bidx is None:
+        bidx = torch.arange(N, dtype=torch.int32).reshape(1, N)
+    return e, alpha.cpu().numpy(), counts.cpu().numpy(), bidx.cpu().numpy()

@@ -1021,13 +1021,15 @@ class SBI_Fitter:
 
     def evaluate_model(self, posteriors=None, X_test=None, y_test=None, num_samples: int = 1000,
                        independent_metrics: bool = True, seed: Optional[int] = None, samples=None,
-                       verbose: bool = False, **unknown) -> dict:
+                       verbose: bool = False, tarp: bool = False, **unknown) -> dict:
         """The reference's evaluate_model for flow posteriors (sbi_runner.py:6484-6735), same keys and arithmetic:
         ``MSE``, ``RMSE``, ``mean_ae``, ``median_ae``, ``R_squared`` (total sum of squares about the GLOBAL mean of
         y_test, as there), ``RMSE_norm`` / ``mean_ae_norm`` (divided by the global std), ``log_dpit_max``
         (-0.5 log max |PIT - uniform|, 6613-6616) and ``mean_log_prob``; per parameter with ``independent_metrics``, else
-        pooled.  ``tarp`` needs the third-party ``tarp`` package and is left out.  The draws stay on the device: means,
-        medians and PIT ranks are reduced there and only (N, D) summaries cross PCIe."""
+        pooled.  ``tarp=True`` adds the reference's ``tarp`` key (6618-6637), a one-element list holding ``calculate_TARP``
+        of the same draws (the reference computes it on every call through the third-party ``tarp`` package; here it is
+        opt-in and runs on the device, ``sf_tarp_coverage``).  The draws stay on the device: means, medians, PIT ranks and
+        the TARP counts are reduced there and only (N, D) summaries cross PCIe."""
         _warn_unknown("evaluate_model", unknown)
         posteriors = posteriors if posteriors is not None else self.posteriors
         X_test = self._X_test if X_test is None else X_test
@@ -1057,6 +1059,8 @@ class SBI_Fitter:
                    "RMSE_norm": np.sqrt(np.mean((y - mean_pred) ** 2, axis=axis)) / np.std(y),
                    "mean_ae_norm": np.mean(np.abs(y - mean_pred), axis=axis) / np.std(y),
                    "log_dpit_max": float(-0.5 * np.log(dpit_max))}
+        if tarp:
+            metrics["tarp"] = np.array([self._tarp_value(sd, y, posteriors=posteriors, seed=seed)])
         try:
             metrics["mean_log_prob"] = float(np.mean(self.log_prob(X_test, y_test, posteriors=posteriors)))
         except Exception:
@@ -1067,6 +1071,42 @@ class SBI_Fitter:
                 logger.info(f"{k}: {v}")
         self.last_metrics = metrics
         return metrics
+
+    def _tarp_value(self, sd: torch.Tensor, y, posteriors=None, num_bootstrap: int = 200, seed: Optional[int] = None,
+                    norm_axis: int = 0) -> float:
+        """| mean over the bootstrap passes of ecp[:, (n + 1) // 2] - 0.5 | of (N,S,D) device draws."""
+        from .features import tarp_coverage
+        if seed is None and hasattr(posteriors, "_next_seed"):
+            seed = posteriors._next_seed(None)
+        y2 = np.asarray(y, dtype=np.float32).reshape(sd.shape[0], -1)
+        ecp, _ = tarp_coverage(sd, y2, norm=True, bootstrap=True, num_bootstrap=num_bootstrap, seed=seed,
+                               norm_axis=norm_axis)
+        return float(abs(np.mean(ecp[:, ecp.shape[1] // 2]) - 0.5))
+
+    def calculate_TARP(self, X: np.ndarray, y: np.ndarray, num_samples: int = 1000, posteriors=None,
+                       num_bootstrap: int = 200, samples=None, seed: Optional[int] = None,
+                       norm_axis: int = 0) -> torch.Tensor:
+        """Tests of Accuracy with Random Points (ref: sbi_runner.py:7090-7126): ``|mean_b ecp[b, mid] - 0.5|`` of
+        ``get_tarp_coverage(samples, y, norm=True, bootstrap=True, num_bootstrap=num_bootstrap)``, as a 0-dim float64
+        tensor on ``self.device``; 0 for a calibrated posterior.  The coverage test is a restatement of the published
+        algorithm that runs on the device (``features.tarp_coverage``), not the ``tarp`` package.  ``samples``, when given,
+        is in the reference's (S, N, D) order.  When it is not, the draws come from ``posteriors.sample_catalogue`` and
+        stay on the device in (N, S, D) order; the reference passes ``sample_posterior``'s (N, S, D) array on that
+        branch without the transpose the package needs (6618-6620 do it for evaluate_model only), so its value there is
+        computed over the wrong axes -- here both branches test the same thing.  ``seed`` (row resampling and reference
+        points; None: the posterior's next seed, as ``sample_catalogue`` takes it) and ``norm_axis`` (see
+        ``features.tarp_coverage``) are additions."""
+        posteriors = posteriors if posteriors is not None else self.posteriors
+        if isinstance(samples, str):
+            samples = np.load(samples)
+        if samples is None:
+            sd = posteriors.sample_catalogue(torch.as_tensor(np.asarray(X, dtype=np.float32)), num_samples, None)
+        elif isinstance(samples, torch.Tensor):
+            sd = samples.to(self.device).float().permute(1, 0, 2).contiguous()
+        else:
+            sd = torch.as_tensor(np.ascontiguousarray(np.asarray(samples, dtype=np.float32).transpose(1, 0, 2))).to(self.device)
+        val = self._tarp_value(sd, y, posteriors=posteriors, num_bootstrap=num_bootstrap, seed=seed, norm_axis=norm_axis)
+        return torch.tensor(val, dtype=torch.float64, device=self.device)
 
     def calculate_PIT(self, X: np.ndarray, y: np.ndarray, num_samples: int = 1000, posteriors=None,
                       samples=None, seed: Optional[int] = None) -> np.ndarray:
