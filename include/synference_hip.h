@@ -381,6 +381,11 @@ int sf_mlp_backward(sf_mlp* m, const float* flat, const float* x, const float* d
  * without moving the (N,S,D) draws to the host.  q: DEVICE [Q]; 1 <= S <= 8192. */
 int sf_quantiles(const float* samples /*[N,S,D]*/, int64_t N, int64_t S, int32_t D,
                  const float* q /*[Q]*/, int32_t Q, float* out /*[N,D,Q]*/, void* stream);
+/* The same contract for long rows, 1 <= S <= 2^24 (the pooled nmc x nposterior draws of the missing-band path, ref:
+ * sbi_runner.py:3292-3297): an exact radix select of the order statistics on the draws' bit patterns instead of a sort in
+ * LDS; the position (n - 1) q and the interpolation are formed in fp64. */
+int sf_quantiles_large(const float* samples /*[N,S,D]*/, int64_t N, int64_t S, int32_t D,
+                       const float* q /*[Q]*/, int32_t Q, float* out /*[N,D,Q]*/, void* stream);
 
 /* ---- feature transform on the device ------------------------------------------------------
  * mag = -2.5 log10(flux_nJy / 1000) + 23.9 ; negative flux -> mag_limit ; mag > mag_limit -> mag_limit ; NaN flux -> NaN
@@ -431,6 +436,39 @@ int sf_tarp_coverage(const float* samples /*[N,S,D] device*/, const float* theta
                      double* ecp /*[max(B,1), bins+1] device*/, double* alpha /*[bins+1] device, last pass; may be NULL*/,
                      int32_t* counts /*[max(B,1), N] device; may be NULL*/, int32_t* boot_idx /*[B,N] device, out; may be NULL*/,
                      void* stream);
+
+/* SBI++ missing-band imputation (ref: sbi_runner.py:7736-7791 _get_neighbor_kdes / _chi2dof, 7831-7841 generate_imputations,
+ * Mode 1; the KDE is scipy.stats.gaussian_kde in one dimension with bw_method = bw and weights).  Per object m, V its observed
+ * bands and X its missing ones:
+ *   chi2[t] = (sum_{b in V} ((train[t,band_col[b]] - obs[m,band_col[b]]) / sigma[m,b])^2) / dof in fp32, every operation
+ *     rounded on its own, NaN terms skipped, dof = the finite observed values among V;
+ *   thresholds ini_chi2, ini_chi2 + chi2_step, ... <= max_chi2 (fp32 sums, at most 32): the first that admits at least
+ *     min_neighbours rows; none: the rows under the last one; no row at all: the fallback_k rows of smallest chi2 (ties to the
+ *     lowest row); a final set below min_neighbours is a failure: n_used = -1 (-2: no finite observed band), NaN outputs;
+ *   w = 1 / dist, dist the fp64 Euclidean distance over V (0 -> 1e-10); var_b = bw^2 sum wn (x - mu)^2 / (1 - sum wn^2), fp64;
+ *   draw (i, b in X): r = Philox(counter ((row_offset + m) lo, hi, i, b), key (seed, stream 5)); neighbour = the first j, in
+ *     ascending training row, whose running fp64 weight sum exceeds (r0 + 0.5) 2^-32 times the total; value = x_j + sqrt(var) z,
+ *     z the first normal of (r2, r3) of the sampler's Box-Muller.
+ * imputed[m,i,:] = obs[m,:] with the column of every missing band replaced by its draw and, with err_col, its error column by
+ * the drawn neighbour's own error value; recon[m,b] = mean over i for missing bands, NaN for observed ones.
+ * 1 <= B <= 32, B <= F <= 64, NT < 2^31.  Exact and reproducible: integer counts, ordered lists, fixed summation order; the
+ * draws of an object do not depend on how the objects are split over calls.  Scratch is owned per device; the neighbour lists
+ * of a group of objects stay within SF_IMPUTE_SCRATCH_BYTES [256 MiB] (one object alone may exceed it).  The call waits on
+ * `stream` once per batch of objects (it reads the list lengths back to form the groups). */
+int sf_impute_missing(const float* train /*[NT,F] device*/, int64_t NT, int32_t F,
+                      const int32_t* band_col /*[B] host*/, const int32_t* err_col /*[B] host, or NULL*/, int32_t B,
+                      const float* obs /*[M,F] device*/, const float* sigma /*[M,B] device*/,
+                      const uint8_t* missing /*[M,B] device, 1 = missing*/, int64_t M, int64_t row_offset,
+                      float ini_chi2, float chi2_step, float max_chi2, int32_t min_neighbours, int32_t fallback_k, float bw,
+                      int32_t nmc, uint64_t seed,
+                      float* imputed /*[M,nmc,F] device*/, float* recon /*[M,B] device*/,
+                      int32_t* n_used /*[M] device: neighbours used, or a negative failure code*/,
+                      float* thr_used /*[M] device, may be NULL: the threshold used (the last one tried on failure / fallback)*/,
+                      double* kde_var /*[M,B] device, may be NULL: NaN for observed bands*/,
+                      int32_t* nbr_idx /*[M,nbr_cap] device, may be NULL: the first nbr_cap neighbours, ascending row*/,
+                      int64_t nbr_cap,
+                      int32_t* draw_idx /*[M,nmc,B] device, may be NULL: training row drawn, -1 for observed bands*/,
+                      void* stream);
 
 /* ---- hand-over to the host ----------------------------------------------------------------
  * host_dst[i] = (double) dev_src[i], i < n: the draws of a catalogue call leave HBM as fp32 in pieces through a ring of pinned

@@ -6,7 +6,8 @@ from .posterior import EnsemblePosterior, FlowPosterior  # noqa: F401
 from .priors import CustomIndependentUniform, Interval, prior_from_parameters  # noqa: F401
 from .runner import HIPRunner, NumpyLoader, train_flow  # noqa: F401
 from .fitter import SBI_Fitter  # noqa: F401
+from .missing import MissingPhotometryHandler  # noqa: F401
 
 __all__ = ["FlowSpec", "FCN", "FlowEstimator", "build_flow", "load_nde_hip", "EnsemblePosterior", "FlowPosterior",
            "CustomIndependentUniform", "Interval", "prior_from_parameters", "HIPRunner", "NumpyLoader",
-           "train_flow", "SBI_Fitter"]
+           "train_flow", "SBI_Fitter", "MissingPhotometryHandler"]

@@ -74,6 +74,124 @@ extern "C" int sf_quantiles(const float* samples, int64_t N, int64_t S, int32_t 
 }
 
 // ---------------------------------------------------------------------------------------------
+// The same quantiles for long rows (1 <= S <= 2^24; the pooled nmc x nposterior = 1e5 draws of the missing-band path,
+// ref: sbi_runner.py:3292-3297): no sort -- an exact radix select of the order statistics every quantile needs, on the
+// order-preserving bit pattern of the draws, 8 bits per pass and up to 8 ranks per batch of passes (ranks that still share
+// a prefix share a histogram, so the two ranks around one quantile cost one).  One 256-thread workgroup per (row, dim);
+// the first pass reads the row from HBM, the later ones from L2.  The position (n - 1) q is formed in fp64 (in fp32 it
+// has no fraction left at n = 1e5) and so is the interpolation.
+// ---------------------------------------------------------------------------------------------
+#define SF_QL_R 8
+__device__ __forceinline__ uint32_t sf_ql_key(float x) {
+  const uint32_t u = __float_as_uint(x);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float sf_ql_val(uint32_t k) {
+  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+__global__ __launch_bounds__(256) void k_quantiles_large(const float* __restrict__ samples, long S, int D,
+                                                         const float* __restrict__ q, int Q, float* __restrict__ out) {
+  __shared__ int s_h0[256];                 // first pass: every finite-or-infinite draw, no prefix
+  __shared__ int s_h[SF_QL_R][256];
+  __shared__ uint32_t s_pre[SF_QL_R];       // prefix of rank r (the bits above the current digit)
+  __shared__ int s_k[SF_QL_R];              // rank r among the draws that share its prefix
+  __shared__ int s_slot[SF_QL_R], s_nd;     // histogram slot of rank r; distinct prefixes
+  __shared__ uint32_t s_spre[SF_QL_R];
+  const long g = blockIdx.x / D;
+  const int d = blockIdx.x % D, tid = threadIdx.x;
+  const float* src = samples + g * S * D + d;
+  float* dst = out + (g * D + d) * Q;
+  s_h0[tid] = 0;
+  __syncthreads();
+  for (long i = tid; i < S; i += 256) {
+    const float x = src[i * D];
+    if (x == x) atomicAdd(&s_h0[sf_ql_key(x) >> 24], 1);
+  }
+  __syncthreads();
+  int n = 0;
+  for (int b = 0; b < 256; ++b) n += s_h0[b];
+  if (n == 0) {
+    for (int t = tid; t < Q; t += 256) dst[t] = __builtin_nanf("");
+    return;
+  }
+  const int nrank = 2 * Q;                  // rank 2t: floor((n - 1) q_t), rank 2t + 1: the next one
+  for (int r0 = 0; r0 < nrank; r0 += SF_QL_R) {
+    const int nr = nrank - r0 < SF_QL_R ? nrank - r0 : SF_QL_R;
+    __syncthreads();
+    if (tid < nr) {
+      const int t = (r0 + tid) >> 1;
+      const double pos = (double)(n - 1) * (double)q[t];
+      long lo = (long)floor(pos);
+      lo = lo < 0 ? 0 : (lo > n - 1 ? n - 1 : lo);
+      const long hi = lo + 1 < n ? lo + 1 : n - 1;
+      int k = (int)(((r0 + tid) & 1) ? hi : lo), b = 0;
+      while (b < 255 && k >= s_h0[b]) { k -= s_h0[b]; ++b; }
+      s_k[tid] = k;
+      s_pre[tid] = (uint32_t)b;
+    }
+    for (int p = 1; p < 4; ++p) {
+      const int shift = 24 - 8 * p;
+      __syncthreads();
+      if (tid == 0) {                       // ranks with the same prefix share a histogram
+        int nd = 0;
+        for (int r = 0; r < nr; ++r) {
+          int s = 0;
+          while (s < nd && s_spre[s] != s_pre[r]) ++s;
+          if (s == nd) s_spre[nd++] = s_pre[r];
+          s_slot[r] = s;
+        }
+        s_nd = nd;
+      }
+      for (int e = tid; e < SF_QL_R * 256; e += 256) (&s_h[0][0])[e] = 0;
+      __syncthreads();
+      const int nd = s_nd;
+      for (long i = tid; i < S; i += 256) {
+        const float x = src[i * D];
+        if (x == x) {
+          const uint32_t key = sf_ql_key(x), top = key >> (shift + 8);
+          for (int s = 0; s < nd; ++s)
+            if (top == s_spre[s]) atomicAdd(&s_h[s][(key >> shift) & 255u], 1);
+        }
+      }
+      __syncthreads();
+      if (tid < nr) {
+        const int* h = s_h[s_slot[tid]];
+        int k = s_k[tid], b = 0;
+        while (b < 255 && k >= h[b]) { k -= h[b]; ++b; }
+        s_k[tid] = k;
+        s_pre[tid] = (s_pre[tid] << 8) | (uint32_t)b;
+      }
+    }
+    __syncthreads();
+    if (tid < nr && !(tid & 1)) {           // (nr is even: the two ranks of a quantile are in one batch)
+      const int t = (r0 + tid) >> 1;
+      const double pos = (double)(n - 1) * (double)q[t];
+      long lo = (long)floor(pos);
+      lo = lo < 0 ? 0 : (lo > n - 1 ? n - 1 : lo);
+      const double vlo = (double)sf_ql_val(s_pre[tid]), vhi = (double)sf_ql_val(s_pre[tid + 1]);
+      const double f = pos - (double)lo;
+      dst[t] = (float)(f > 0.0 ? vlo + f * (vhi - vlo) : vlo);
+    }
+  }
+}
+
+extern "C" int sf_quantiles_large(const float* samples, int64_t N, int64_t S, int32_t D, const float* q_dev, int32_t Q,
+                                  float* out, void* stream) {
+  if (!samples || !q_dev || !out) { sf_set_error("sf_quantiles_large: null argument"); return SF_ERR_INVALID; }
+  if (S < 1 || S > (1ll << 24) || D < 1 || Q < 1 || Q > 256 || N < 0) {
+    sf_set_error("sf_quantiles_large: need 1 <= S <= 2^24, D >= 1, 1 <= Q <= 256, N >= 0");
+    return SF_ERR_INVALID;
+  }
+  if ((uint64_t)N * (uint64_t)D > 0x7fffffffull) { sf_set_error("sf_quantiles_large: N*D too large for one launch"); return SF_ERR_INVALID; }
+  if (N == 0) return SF_OK;
+  hipLaunchKernelGGL(k_quantiles_large, dim3((unsigned)(N * D)), dim3(256), 0, (hipStream_t)stream, samples, (long)S, (int)D,
+                     q_dev, (int)Q, out);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { sf_set_error(std::string("k_quantiles_large: ") + hipGetErrorString(e)); return SF_ERR_HIP; }
+  return SF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Feature transform on the device: fluxes in nJy -> AB magnitudes,
 //   mag = -2.5 log10(f / 1000) + 23.9 ; f < 0 -> mag_limit ; mag > mag_limit (incl. f == 0 -> +inf) -> mag_limit ;
 //   a NaN flux stays NaN (the reference only replaces negative fluxes, sbi_runner.py:1706-1714, so that rows with a

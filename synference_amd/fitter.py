@@ -927,7 +927,9 @@ class SBI_Fitter:
                       return_samples: bool = False, log_times: bool = False, seed: Optional[int] = None,
                       device_quantiles: bool = True, flux_units=None, missing_data_flag=-99,
                       override_transformations: dict = {}, timeout_seconds_per_row: float = 5,
-                      return_feature_array: bool = False, return_full_samples: bool = False, **unknown):
+                      return_feature_array: bool = False, return_full_samples: bool = False,
+                      missing_data_mcmc: bool = False, missing_data_mcmc_params: Optional[dict] = None,
+                      missing_data_sigma=None, **unknown):
         """Sampling + quantile section of the reference's fit_catalogue (sbi_runner.py:3230-3282).
 
         ``observations`` is a pandas DataFrame / dict of columns / (N, C) array.  With ``flux_units`` given and a feature
@@ -936,10 +938,26 @@ class SBI_Fitter:
         otherwise its columns are taken as the model's feature columns.  Masked rows get NaN quantiles.
         ``timeout_seconds_per_row`` (reference default 5 s) x rows is the wall-clock ceiling of the catalogue call
         (sbi_runner.py:3246-3253); ``return_feature_array`` returns (feature_array, mask) like line 3092-3094;
-        ``return_full_samples`` is the reference's name for ``return_samples``."""
+        ``return_full_samples`` is the reference's name for ``return_samples``.
+
+        ``missing_data_mcmc=True`` (sbi_runner.py:3102-3219, 3284-3317): rows whose only defect is the missing-data flag are
+        not dropped but marginalised over their missing bands by ``MissingPhotometryHandler`` (synference_amd/missing.py:
+        ``nmc`` imputations x ``nposterior`` draws, pooled; ``missing_data_mcmc_params`` are its ``run_params`` and ARE applied,
+        unlike in the reference).  Complete rows are sampled exactly as without the switch.  The table gains
+        ``has_missing_data`` and, per band that was imputed somewhere, ``predicted_<band>``; a row the handler fails on
+        keeps NaN quantiles; with ``return_samples`` the flagged rows are NaN in the (N, num_samples, D) array (their pooled
+        draws have another length: ``self.missing_handler.last_posterior_samples``).  The chi2 uncertainty is the row's error
+        feature columns when errors are features, else ``missing_data_sigma`` (scalar, [B] or (N, B)) -- an addition."""
         import pandas as pd
         _warn_unknown("fit_catalogue", unknown)
         return_samples = return_samples or return_full_samples
+        if missing_data_mcmc and not return_feature_array:
+            return self._fit_catalogue_missing(observations, columns_to_feature_names, missing_data_flag, flux_units,
+                                               override_transformations, missing_data_mcmc_params, missing_data_sigma, quantiles,
+                                               append_to_input, return_samples, seed,
+                                               dict(num_samples=num_samples, quantiles=quantiles, sample_method=sample_method,
+                                                    log_times=log_times, seed=seed, device_quantiles=device_quantiles,
+                                                    timeout_seconds_per_row=timeout_seconds_per_row))
         if flux_units is not None and getattr(self, "feature_array_flags", None):
             df0 = pd.DataFrame(observations) if isinstance(observations, dict) else observations
             feats_ok, removed = self.create_features_from_observations(df0, columns_to_feature_names, flux_units,
@@ -1018,6 +1036,101 @@ class SBI_Fitter:
                 col[obs_mask] = np.nan
                 table[f"{param}_{int(quantiles[j] * 100)}"] = col
         return (table, samples) if return_samples else table
+
+    def _fit_catalogue_missing(self, observations, columns_to_feature_names, missing_data_flag, flux_units,
+                               override_transformations, params, sigma_spec, quantiles, append_to_input, return_samples, seed,
+                               inner_kw):
+        """fit_catalogue(missing_data_mcmc=True): the complete rows through the ordinary call (same seed, same positions
+        among the complete rows: the same table entries), the flagged rows through the handler."""
+        import pandas as pd
+        from .missing import MissingPhotometryHandler
+        from .posterior import broadcast_seed
+        flags = dict(getattr(self, "feature_array_flags", None) or {})
+        if flags.get("scatter_fluxes") and flags.get("empirical_noise_models"):
+            raise ValueError("missing_data_mcmc on a feature array built with empirical noise models and scatter_fluxes needs "
+                             "the reference's 'Mode 2' imputation, which is not built on the HIP path (DESIGN.md section 7)")
+        names = list(self.feature_names)
+        if flux_units is not None and flags:
+            df0 = pd.DataFrame(observations) if isinstance(observations, dict) else observations
+            feats, _ = self.create_features_from_observations(df0, columns_to_feature_names, flux_units, missing_data_flag,
+                                                              override_transformations, ignore_missing=True)
+            bands = list(flags["raw_observation_names"])
+            bcols = [names.index(n) for n in bands]
+            ecols = None
+            if flags.get("include_errors_in_feature_array"):
+                ecols = [names.index(f"unc_{b}") if f"unc_{b}" in names else names.index(flags["error_names"][i])
+                         for i, b in enumerate(bands)]
+        else:
+            if isinstance(observations, np.ndarray):
+                df0 = pd.DataFrame(observations, columns=names[: observations.shape[1]])
+            elif isinstance(observations, dict):
+                df0 = pd.DataFrame(observations)
+            else:
+                df0 = observations
+            if columns_to_feature_names:
+                df0 = df0.rename(columns=columns_to_feature_names)
+            lacking = [c for c in names if c not in df0.columns]
+            if lacking:
+                raise ValueError(f"observations lack the feature columns {lacking}")
+            feats = df0[names].to_numpy(dtype=np.float32)
+            bands, bcols, ecols = names, list(range(len(names))), None      # every feature column is a band
+        flag_nan = isinstance(missing_data_flag, float) and np.isnan(missing_data_flag)
+        flagged = np.isnan(feats) if flag_nan else (feats == np.float32(missing_data_flag))
+        N, B = len(feats), len(bcols)
+        miss = flagged[:, bcols]
+        if ecols is not None:
+            miss = miss | flagged[:, ecols]                                     # value or error flagged: the band is missing
+        has_missing = flagged.any(1)
+        full = feats.copy()
+        full[flagged] = np.nan
+        complete = np.where(has_missing[:, None], np.nan, full).astype(np.float32)
+        out = self.fit_catalogue(complete, columns_to_feature_names=None, append_to_input=False,
+                                 return_samples=return_samples, **inner_kw)
+        qt = out[0] if return_samples else out
+        table = df0.copy() if append_to_input else pd.DataFrame({"ID": np.arange(N) + 1})
+        for c in qt.columns:
+            if c != "ID" and c not in names:
+                table[c] = qt[c].to_numpy()
+        self.missing_handler = None
+        if has_missing.any():
+            logger.info(f"{int(has_missing.sum())} rows with missing data found. Marginalizing over missing data.")
+            rows = np.where(has_missing)[0]
+            if ecols is not None:
+                sigma = full[np.ix_(rows, ecols)]
+            elif sigma_spec is not None:
+                sg = np.asarray(sigma_spec, dtype=np.float32)
+                sigma = sg[rows] if sg.ndim == 2 else np.broadcast_to(sg, (len(rows), B))
+            else:
+                raise ValueError("missing_data_mcmc needs an uncertainty for the neighbour search: the model has no error "
+                                 "features (include_errors_in_feature_array), so give missing_data_sigma (scalar, [B] or (N, B))")
+            handler = MissingPhotometryHandler.init_from_synference(self, run_params=params)
+            self.missing_handler = handler
+            seed_h = None if seed is None else (int(seed) + 0x9E3779B97F4A7C15) & (2 ** 63 - 1)
+            if seed_h is None:
+                seed_h = self.posteriors._next_seed(None)
+            seed_h = broadcast_seed(seed_h)                                       # every rank processes all flagged rows
+            res = handler.process_catalogue(full[rows], sigma, miss[rows], seed=seed_h, quantiles=quantiles,
+                                            return_draws=return_samples)
+            # a flag outside the bands (an extra feature, the normalisation column) cannot be imputed: the row fails
+            other = np.ones(feats.shape[1], bool)
+            other[bcols] = False
+            if ecols is not None:
+                other[ecols] = False
+            ok = res["success"] & ~flagged[rows][:, other].any(1)
+            q = np.where(ok[:, None, None], res["quantiles"], np.nan)
+            for i, param in enumerate(self.simple_fitted_parameter_names):
+                for j, qv in enumerate(quantiles):
+                    col = table[f"{param}_{int(qv * 100)}"].to_numpy(dtype=np.float64).copy()
+                    col[rows] = q[:, i, j]
+                    table[f"{param}_{int(qv * 100)}"] = col
+            table["has_missing_data"] = has_missing
+            recon = np.full((N, B), np.nan)
+            recon[rows] = np.where(ok[:, None] & miss[rows], res["reconstructed_photometry"], np.nan)
+            for b, name in enumerate(bands):
+                if not np.all(np.isnan(recon[:, b])):
+                    table[f"predicted_{name}"] = recon[:, b]
+            self.last_missing_result = res
+        return (table, out[1]) if return_samples else table
 
     def evaluate_model(self, posteriors=None, X_test=None, y_test=None, num_samples: int = 1000,
                        independent_metrics: bool = True, seed: Optional[int] = None, samples=None,

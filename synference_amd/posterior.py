@@ -366,6 +366,25 @@ def device_quantiles(samples: torch.Tensor, quantiles) -> torch.Tensor:
     return out
 
 
+def device_quantiles_large(samples: torch.Tensor, quantiles) -> torch.Tensor:
+    """``device_quantiles`` for long rows, 1 <= S <= 2^24 (sf_quantiles_large: an exact radix select instead of a sort in
+    LDS, the position (n - 1) q in float64) -- the pooled nmc x nposterior draws of the missing-band path
+    (ref: sbi_runner.py:3292-3297)."""
+    import ctypes as C
+    from . import _lib
+    if samples.device.type != "cuda":
+        raise RuntimeError("device_quantiles_large needs the draws on the GPU")
+    samples = samples.contiguous().float()
+    N, S, D = samples.shape
+    q = torch.as_tensor(np.asarray(quantiles, dtype=np.float32), device=samples.device)
+    out = torch.empty((N, D, q.numel()), dtype=torch.float32, device=samples.device)
+    st = C.c_void_p(torch.cuda.current_stream(samples.device).cuda_stream)
+    with torch.cuda.device(samples.device):
+        _lib.check(_lib.load().sf_quantiles_large(C.c_void_p(samples.data_ptr()), N, S, D, C.c_void_p(q.data_ptr()), q.numel(),
+                                                  C.c_void_p(out.data_ptr()), st))
+    return out
+
+
 def _sample_slot_list(post: FlowPosterior, X, S: int, slots: torch.Tensor, seed: int, out: torch.Tensor):
     """One member's share of an ensemble draw: the persistent sampler over an explicit slot list
     (sf_flow_sample_slots; ensemble members own disjoint slot sets of every row)."""
