@@ -470,6 +470,28 @@ int sf_impute_missing(const float* train /*[NT,F] device*/, int64_t NT, int32_t 
                       int32_t* draw_idx /*[M,nmc,B] device, may be NULL: training row drawn, -1 for observed bands*/,
                       void* stream);
 
+/* ---- out-of-distribution check: the all-pairs kernels (csrc/sf_ood.hip; synference_amd/ood.py builds LOF, kNN and KDE scores
+ * on them -- ref: utils.py:991-1340 detect_outliers / detect_outliers_pyod, sbi_runner.py:3777-3945 test_in_distribution) -----
+ * Squared distance of two rows, everywhere: acc = 0; for c ascending: t = q[c] - b[c]; acc = acc + t * t, every operation
+ * rounded to nearest in fp32 and none fused.  A NaN distance (a NaN in the base row) counts as +inf.
+ *
+ * sf_knn: the k nearest rows of base[N,C] for every row of query[M,C], exact and brute force.  Candidates order by
+ * (d2 bits, base row): equal distances go to the lowest row, so the result is ONE set: it does not depend on chunking, on
+ * tiling or on how the queries are split over calls.  exclude_self = 1: base row self_offset + m is not a neighbour of query m
+ * (the base against itself, possibly in pieces).  Outputs ascending.  1 <= C <= 64, 1 <= k <= 64, k <= N - exclude_self,
+ * N < 2^31, with exclude_self self_offset + M <= N; anything else is SF_ERR_INVALID and the outputs are untouched.
+ * Asynchronous on `stream`; scratch (M x splits x k keys when few queries meet a long base) is owned per device. */
+int sf_knn(const float* base /*[N,C] device*/, int64_t N, int32_t C, const float* query /*[M,C] device*/, int64_t M,
+           int32_t k, int32_t exclude_self, int64_t self_offset,
+           float* d2 /*[M,k] device, ascending*/, int32_t* idx /*[M,k] device*/, void* stream);
+
+/* out[m] = log sum_i exp(-d2(query_w[m], base_w[i]) / 2) over rows that the caller has whitened (scipy.stats.gaussian_kde's
+ * and pyod KDE's kernel sum without the normalisation).  Terms are v_exp_f32 of the distance above the running minimum, added
+ * in fp64 in ascending row order per split of the base, the splits in ascending order; the split count depends on the shapes
+ * alone: two calls give the same bits.  No finite distance: -inf.  1 <= C <= 64, N < 2^31. */
+int sf_kde_logsumexp(const float* base_w /*[N,C] device*/, int64_t N, int32_t C, const float* query_w /*[M,C] device*/,
+                     int64_t M, double* out /*[M] device*/, void* stream);
+
 /* ---- hand-over to the host ----------------------------------------------------------------
  * host_dst[i] = (double) dev_src[i], i < n: the draws of a catalogue call leave HBM as fp32 in pieces through a ring of pinned
  * staging buffers on a private copy stream and are widened into the caller's float64 array (any host memory, not necessarily

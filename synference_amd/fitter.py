@@ -595,6 +595,8 @@ class SBI_Fitter:
         from .hostio import to_host_f64
         from .posterior import all_gather_rows, broadcast_seed, dist_world, gather_rows, shard_bounds
         rank, world = dist_world()
+        # ``row_offset`` (keyword): X holds rows [row_offset, ...) of a larger catalogue -- same seed, same draws as there
+        off = int(kwargs.get("row_offset", 0))
         if world > 1 and len(X) >= world and kwargs.get("shard", True):
             if seed is None:
                 seed = posteriors._next_seed(None)
@@ -603,7 +605,7 @@ class SBI_Fitter:
             tmo = float(timeout_seconds_per_test) * (b[rank + 1] - b[rank]) if timeout_seconds_per_test else None
             t0 = time.time()
             local = posteriors.sample_catalogue(torch.as_tensor(X[b[rank]:b[rank + 1]]), num_samples, seed,
-                                                timeout_seconds=tmo, row_offset=b[rank])
+                                                timeout_seconds=tmo, row_offset=off + b[rank])
             if log_times:
                 per = (time.time() - t0) / max(1, b[rank + 1] - b[rank])
                 self.last_times_per_object = np.full(b[rank + 1] - b[rank], per)
@@ -653,12 +655,13 @@ class SBI_Fitter:
                 tmo = float(timeout_seconds_per_test) * (b - a) if timeout_seconds_per_test else None
                 # (same seed, rows keyed by their position: the draws do not depend on the chunking)
                 if direct is not None:
-                    posteriors.sample_catalogue(torch.as_tensor(X[a:b]), num_samples, seed, timeout_seconds=tmo, row_offset=a,
-                                                out=pin_t[a:b])
+                    posteriors.sample_catalogue(torch.as_tensor(X[a:b]), num_samples, seed, timeout_seconds=tmo,
+                                                row_offset=off + a, out=pin_t[a:b])
                     torch.cuda.synchronize()     # the host array is complete when the stream is
                     times.extend([(time.time() - t0) / (b - a)] * (b - a))
                     continue
-                s = posteriors.sample_catalogue(torch.as_tensor(X[a:b]), num_samples, seed, timeout_seconds=tmo, row_offset=a)
+                s = posteriors.sample_catalogue(torch.as_tensor(X[a:b]), num_samples, seed, timeout_seconds=tmo,
+                                                row_offset=off + a)
                 # D2H in float32 (half the PCIe bytes of a device-side .double()) through a ring of pinned staging buffers
                 # on a copy stream, widened into the reference's float64 container by a thread pool while the next piece
                 # is on the bus (hostio.py); with log_times the chunk's time includes its hand-over
@@ -929,7 +932,7 @@ class SBI_Fitter:
                       override_transformations: dict = {}, timeout_seconds_per_row: float = 5,
                       return_feature_array: bool = False, return_full_samples: bool = False,
                       missing_data_mcmc: bool = False, missing_data_mcmc_params: Optional[dict] = None,
-                      missing_data_sigma=None, **unknown):
+                      missing_data_sigma=None, check_out_of_distribution: bool = False, outlier_methods=None, **unknown):
         """Sampling + quantile section of the reference's fit_catalogue (sbi_runner.py:3230-3282).
 
         ``observations`` is a pandas DataFrame / dict of columns / (N, C) array.  With ``flux_units`` given and a feature
@@ -947,29 +950,41 @@ class SBI_Fitter:
         ``has_missing_data`` and, per band that was imputed somewhere, ``predicted_<band>``; a row the handler fails on
         keeps NaN quantiles; with ``return_samples`` the flagged rows are NaN in the (N, num_samples, D) array (their pooled
         draws have another length: ``self.missing_handler.last_posterior_samples``).  The chi2 uncertainty is the row's error
-        feature columns when errors are features, else ``missing_data_sigma`` (scalar, [B] or (N, B)) -- an addition."""
+        feature columns when errors are features, else ``missing_data_sigma`` (scalar, [B] or (N, B)) -- an addition.
+
+        ``check_out_of_distribution=True`` (sbi_runner.py:3078-3092, 3299-3305; the reference's default is True, here it is
+        False: DESIGN.md section 0): every complete row is tested against ``self.feature_array`` by
+        ``test_in_distribution_pyod(methods=outlier_methods, contamination=0.01)`` -- ``outlier_methods=None`` means
+        ("knn", "lof", "kde"), majority rule -- on the device (synference_amd/ood.py).  Flagged rows join the row mask: they
+        are not sampled, their quantiles are NaN and ``is_outlier`` is the final row mask.  The other rows keep the draws
+        they would have had (the random streams are keyed by the row's position).  Rows with missing bands
+        (``missing_data_mcmc``) are not checked.  Under a process group every rank runs the whole check."""
         import pandas as pd
         _warn_unknown("fit_catalogue", unknown)
         return_samples = return_samples or return_full_samples
+        ood_kw = dict(check_out_of_distribution=check_out_of_distribution, outlier_methods=outlier_methods)
         if missing_data_mcmc and not return_feature_array:
             return self._fit_catalogue_missing(observations, columns_to_feature_names, missing_data_flag, flux_units,
                                                override_transformations, missing_data_mcmc_params, missing_data_sigma, quantiles,
                                                append_to_input, return_samples, seed,
                                                dict(num_samples=num_samples, quantiles=quantiles, sample_method=sample_method,
                                                     log_times=log_times, seed=seed, device_quantiles=device_quantiles,
-                                                    timeout_seconds_per_row=timeout_seconds_per_row))
+                                                    timeout_seconds_per_row=timeout_seconds_per_row, **ood_kw))
         if flux_units is not None and getattr(self, "feature_array_flags", None):
             df0 = pd.DataFrame(observations) if isinstance(observations, dict) else observations
             feats_ok, removed = self.create_features_from_observations(df0, columns_to_feature_names, flux_units,
                                                                        missing_data_flag, override_transformations)
             if return_feature_array:
+                if check_out_of_distribution and len(feats_ok):
+                    removed = removed.copy()
+                    removed[~removed] |= self._catalogue_outliers(feats_ok, outlier_methods)
                 return feats_ok, removed
             full = np.full((len(df0), feats_ok.shape[1]), np.nan, dtype=np.float32)
             full[~removed] = feats_ok
             out = self.fit_catalogue(full, columns_to_feature_names=None, num_samples=num_samples, quantiles=quantiles,
                                      sample_method=sample_method, append_to_input=False, return_samples=return_samples,
                                      log_times=log_times, seed=seed, device_quantiles=device_quantiles,
-                                     timeout_seconds_per_row=timeout_seconds_per_row)
+                                     timeout_seconds_per_row=timeout_seconds_per_row, **ood_kw)
             qt = out[0] if return_samples else out
             table = df0.copy() if append_to_input else pd.DataFrame({"ID": np.arange(len(df0)) + 1})
             for c in qt.columns:
@@ -989,9 +1004,20 @@ class SBI_Fitter:
         if missing:
             raise ValueError(f"observations lack the feature columns {missing}")
         feats = df[cols].to_numpy(dtype=np.float32)
-        obs_mask = ~np.isfinite(feats).all(1)
+        finite = np.isfinite(feats).all(1)
+        obs_mask = ~finite
+        good = feats[finite]                      # the rows' positions here key their random streams, flagged or not
+        keep = np.ones(len(good), bool)
+        if check_out_of_distribution and len(good):
+            keep = ~self._catalogue_outliers(good, outlier_methods)
+            obs_mask = obs_mask.copy()
+            obs_mask[~obs_mask] = ~keep
         if return_feature_array:
-            return feats[~obs_mask], obs_mask
+            return good, obs_mask                    # sbi_runner.py:3093-3095: the features as built, the mask with the outliers
+        edges = np.flatnonzero(np.diff(np.concatenate([[False], keep, [False]]).astype(np.int8)))
+        runs = list(zip(edges[0::2].tolist(), edges[1::2].tolist()))   # [a, b) blocks of rows to sample
+        if seed is None and len(runs) > 1:
+            seed = self.posteriors._next_seed(None)
         tmo = float(timeout_seconds_per_row) * max(1, int((~obs_mask).sum())) if timeout_seconds_per_row else None
         if device_quantiles and not return_samples and num_samples <= 8192:
             # f3: quantiles reduced on the GPU; only (N, D, Q) floats cross PCIe
@@ -1003,28 +1029,50 @@ class SBI_Fitter:
                     raise ValueError("Invalid sample method for the HIP backend. Use 'direct'.")
                 from .posterior import all_gather_rows, broadcast_seed, dist_world, shard_bounds
                 rank, world = dist_world()
-                good = feats[~obs_mask]
+                def block(lo, hi):
+                    """quantiles of rows [lo, hi) of `good`, NaN for flagged rows: one sampler call per run of kept rows"""
+                    if runs == [(lo, hi)]:
+                        s_dev = self.posteriors.sample_catalogue(torch.as_tensor(good[lo:hi]), num_samples, seed,
+                                                                 timeout_seconds=tmo, row_offset=lo)
+                        return _dq(s_dev, quantiles)
+                    q = None
+                    for a, b in runs:
+                        a, b = max(a, lo), min(b, hi)
+                        if b <= a:
+                            continue
+                        s_dev = self.posteriors.sample_catalogue(torch.as_tensor(good[a:b]), num_samples, seed,
+                                                                 timeout_seconds=tmo, row_offset=a)
+                        qr = _dq(s_dev, quantiles)
+                        if q is None:
+                            q = torch.full((hi - lo,) + tuple(qr.shape[1:]), float("nan"), dtype=qr.dtype, device=qr.device)
+                        q[a - lo:b - lo] = qr
+                    if q is None:
+                        q = torch.full((hi - lo, len(self.fitted_parameter_names), len(quantiles)), float("nan"),
+                                       dtype=torch.float32, device=self.posteriors.device)
+                    return q
                 if world > 1 and len(good) >= world:   # rank r: its row block; only the (n, D, Q) quantiles are gathered
                     if seed is None:
                         seed = self.posteriors._next_seed(None)
                     seed = broadcast_seed(seed)
                     b = shard_bounds(len(good), world)
-                    s_dev = self.posteriors.sample_catalogue(torch.as_tensor(good[b[rank]:b[rank + 1]]), num_samples, seed,
-                                                             timeout_seconds=tmo, row_offset=b[rank])
-                    qarr[~obs_mask] = all_gather_rows(_dq(s_dev, quantiles).contiguous(), b).double().cpu().numpy()
+                    if runs == [(0, len(good))]:
+                        runs = [(int(b[rank]), int(b[rank + 1]))]
+                    qarr[finite] = all_gather_rows(block(int(b[rank]), int(b[rank + 1])).contiguous(), b).double().cpu().numpy()
                 else:
-                    s_dev = self.posteriors.sample_catalogue(torch.as_tensor(good), num_samples, seed, timeout_seconds=tmo)
-                    qarr[~obs_mask] = _dq(s_dev, quantiles).double().cpu().numpy()
+                    qarr[finite] = block(0, len(good)).double().cpu().numpy()
             for i, param in enumerate(self.simple_fitted_parameter_names):
                 for j, qv in enumerate(quantiles):
                     table[f"{param}_{int(qv * 100)}"] = qarr[:, i, j]
+            if check_out_of_distribution:
+                table["is_outlier"] = obs_mask
             return table
         samples = np.full((len(df), num_samples, len(self.fitted_parameter_names)), np.nan)
-        if (~obs_mask).any():
-            samples[~obs_mask] = self.sample_posterior(feats[~obs_mask], sample_method=sample_method,
-                                                       num_samples=num_samples, log_times=log_times, seed=seed,
-                                                       timeout_seconds_per_test=timeout_seconds_per_row,
-                                                       gather="all")   # every rank fills the whole table
+        pos = np.flatnonzero(finite)
+        for a, b in runs:
+            samples[pos[a:b]] = self.sample_posterior(good[a:b], sample_method=sample_method,
+                                                      num_samples=num_samples, log_times=log_times, seed=seed,
+                                                      timeout_seconds_per_test=timeout_seconds_per_row,
+                                                      gather="all", row_offset=a)   # every rank fills the whole table
         samples_quant = samples.transpose(2, 0, 1)
         table = df.copy() if append_to_input else pd.DataFrame({"ID": np.arange(len(df)) + 1})
         for i, param in enumerate(self.simple_fitted_parameter_names):
@@ -1035,7 +1083,62 @@ class SBI_Fitter:
                 col = np.asarray(quant, dtype=np.float64)
                 col[obs_mask] = np.nan
                 table[f"{param}_{int(quantiles[j] * 100)}"] = col
+        if check_out_of_distribution:
+            table["is_outlier"] = obs_mask
         return (table, samples) if return_samples else table
+
+    # ---- out-of-distribution check (synference_amd/ood.py) ------------------------------------------------------------------
+    def _ood_base(self):
+        """The fitted base side of the detectors for ``self.feature_array``: kept until the array is replaced."""
+        from .ood import FittedBase
+        cache = getattr(self, "_ood_cache", None)
+        if cache is None or cache[0] is not self.feature_array:
+            cache = (self.feature_array, FittedBase(self.feature_array, self.device))
+            self._ood_cache = cache
+        return cache[1]
+
+    def _catalogue_outliers(self, rows, outlier_methods=None) -> np.ndarray:
+        methods = ("knn", "lof", "kde") if outlier_methods is None else outlier_methods
+        outliers = np.asarray(self.test_in_distribution_pyod(np.asarray(rows), direction="in", methods=methods,
+                                                             contamination=0.01), bool)
+        if outliers.any():
+            logger.warning(f"{int(outliers.sum())} outlier(s) detected in the observational data.")
+        return outliers
+
+    def _ood_sides(self, X_test, direction):
+        assert self.has_features, "Feature array not created. Please create the feature array first."
+        if not isinstance(X_test, np.ndarray):
+            raise TypeError("X_test must be a numpy array.")
+        assert direction in ["in", "out"], "Direction must be either 'in' or 'out'."
+        if X_test.ndim != 2 or X_test.shape[1] != self.feature_array.shape[1]:
+            raise ValueError("Base distribution and observations must have same number of features")
+        return (self._ood_base, X_test) if direction == "in" else (lambda: X_test, self.feature_array)
+
+    def test_in_distribution_pyod(self, X_test: np.ndarray, methods=("knn", "lof", "kde"), contamination=0.01, direction="in",
+                                  combination_method="majority"):
+        """ref sbi_runner.py:3777-3831: is ``X_test`` inside the distribution of ``self.feature_array`` (``direction="in"``) or
+        the feature array inside that of ``X_test`` ("out")?  pyod's knn / lof / kde restated on the device
+        (``ood.detect_outliers_pyod``); the reference's default methods ("lof", "isolation_forest") include one that is not
+        built, so the default here is the three that are.  Returns the combined boolean mask."""
+        from .ood import _validate_pyod, detect_outliers_pyod
+        _validate_pyod(methods, combination_method)
+        base, obs = self._ood_sides(X_test, direction)
+        return detect_outliers_pyod(base(), obs, methods=methods, contamination=contamination, combination=combination_method,
+                                    return_scores=False, device=self.device)
+
+    def test_in_distribution(self, X_test: np.ndarray, method="mahalanobis", direction="in", contamination=0.1, n_neighbors=20,
+                             threshold=None, confidence=0.95, n_components=None, plot=True, feature_breakdown=False, **kwargs):
+        """ref sbi_runner.py:3833-3945, a wrapper of ``ood.detect_outliers``: ``outlier_mask``, ``scores``, ``threshold_used``,
+        ``method_info``.  The reference's default method, robust_mahalanobis, is not built (``ValueError`` when asked for), so
+        the default here is mahalanobis; ``feature_breakdown`` is presentation and raises ``ValueError``."""
+        from .ood import _validate, detect_outliers
+        if feature_breakdown:
+            raise ValueError("feature_breakdown is outside the accelerated path (presentation; DESIGN.md section 7)")
+        _validate(method, 1, 1)
+        base, obs = self._ood_sides(X_test, direction)
+        return detect_outliers(base(), obs, method=method, contamination=contamination, n_neighbors=n_neighbors,
+                               threshold=threshold, confidence=confidence, n_components=n_components, plot=plot,
+                               device=self.device, **kwargs)
 
     def _fit_catalogue_missing(self, observations, columns_to_feature_names, missing_data_flag, flux_units,
                                override_transformations, params, sigma_spec, quantiles, append_to_input, return_samples, seed,
@@ -1091,6 +1194,8 @@ class SBI_Fitter:
         for c in qt.columns:
             if c != "ID" and c not in names:
                 table[c] = qt[c].to_numpy()
+        if "is_outlier" in table.columns:       # rows with missing bands are not checked: NaN rows in the inner call
+            table["is_outlier"] = table["is_outlier"].to_numpy(dtype=bool) & ~has_missing
         self.missing_handler = None
         if has_missing.any():
             logger.info(f"{int(has_missing.sum())} rows with missing data found. Marginalizing over missing data.")
