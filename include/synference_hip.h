@@ -142,6 +142,34 @@ int sf_flow_describe(const sf_flow* f, char* buf, size_t buflen);
 int sf_flow_log_prob(sf_flow* f, const float* theta /*[B,D]*/, const float* x /*[B,C]*/,
                      int64_t B, float* out /*[B]*/, void* stream);
 
+/* ---- posterior mode ------------------------------------------------------------------
+ * lp[b] = log q(theta[b] | x[b / rows_per_x]);  dtheta[b, :] = d lp[b] / d theta[b, :]   (raw estimator density, fp32)
+ * x is [ceil(B / rows_per_x), C]: rows_per_x consecutive rows of theta share one context row (rows_per_x = 1: aligned
+ * rows).  lp or dtheta may be NULL (dtheta NULL: the forward half only).
+ * Kinds: SF_MAF and the coupling SF_NSF with D >= 2; the one-parameter NSF and SF_NSF_AR / SF_MAF_AR return
+ * SF_ERR_INVALID with a message that names the kind.
+ * The backward products read a transposed operand image of the handle's OWN parameter vector: it is built on the first
+ * gradient call after sf_flow_set_params and kept until the next sf_flow_set_params.  After sf_flow_loss_grad* /
+ * sf_flow_train_epoch* the handle holds no vector of its own and the call returns SF_ERR_STATE, as sf_flow_get_params does:
+ * call sf_flow_set_params first.  sf_flow_log_prob, the samplers and training do not see that image.
+ * Replaces: the potential's autograd gradient inside DirectPosterior.map -> gradient_ascent [UPSTREAM sbi]. */
+int sf_flow_log_prob_grad(sf_flow* f, const float* theta /*[B,D]*/, const float* x, int64_t rows_per_x, int64_t B,
+                          float* lp /*[B]*/, float* dtheta /*[B,D]*/, void* stream);
+
+/* One fused ascent step of the mode search for B independent candidates (no handle: elementwise).
+ *   theta[b,:]  in: the point at which lp[b] and g_theta[b,:] were evaluated; out: the next point
+ *   phi         unconstrained coordinates, theta = lo + (hi - lo) * sigmoid(phi); lo / hi NULL (both): theta = phi
+ *   a candidate whose lp or gradient is not finite is frozen: nothing of it is written
+ *   save_best != 0 and lp[b] > best_lp[b] (strictly): best_lp[b] = lp[b], best_theta[b,:] = theta[b,:] (the input point)
+ *   then torch.optim.Adam's update of phi for the loss -lp (betas 0.9 / 0.999, eps 1e-8, no weight decay, bias
+ *   correction for the 1-based `step`) with g_phi = g_theta * (hi - lo) * s * (1 - s)
+ *   g_theta NULL: score only (the evaluation after the last step); phi and the moments are not read then.
+ * For an ensemble, lp / g_theta are the already combined mixture values. */
+int sf_map_step(int64_t B, int64_t D, float* phi /*[B,D]*/, float* exp_avg /*[B,D]*/, float* exp_avg_sq /*[B,D]*/,
+                float* theta /*[B,D]*/, const float* lp /*[B]*/, const float* g_theta /*[B,D]*/, const float* lo /*[D]*/,
+                const float* hi /*[D]*/, float* best_theta /*[B,D]*/, float* best_lp /*[B]*/, float learning_rate,
+                int64_t step, int save_best, void* stream);
+
 /* ---- sampling direction -------------------------------------------------------------
  * Parity hook: theta = inverse(z | x), logdet = log|det d theta / d z|  (may be NULL). */
 int sf_flow_inverse_from_noise(sf_flow* f, const float* z /*[B,D]*/, const float* x /*[B,C]*/,

@@ -158,6 +158,7 @@ void sf_flow_destroy(sf_flow* f) {
     (void)hipFree(f->d_flat); (void)hipFree(f->d_gpacked); (void)hipFree(f->d_gdst);
     (void)hipFree(f->d_imgC); (void)hipFree(f->d_sC1); (void)hipFree(f->d_sC2); (void)hipFree(f->d_gdstC); (void)hipFree(f->d_gsrcC); (void)hipFree(f->d_gzeroC); (void)hipFree(f->d_gpartC); (void)hipFree(f->d_gfixC); (void)hipFree(f->d_ustash);
     (void)hipFree(f->d_queue); (void)hipFree(f->d_ring); (void)hipFree(f->d_galacc); (void)hipFree(f->d_sqpart); (void)hipFree(f->d_losspart_mem); (void)hipFree(f->d_best); (void)hipHostFree(f->h_queue);
+    (void)hipFree(f->d_gtT); (void)hipFree(f->d_gt1); (void)hipFree(f->d_gt2);
     (void)hipFree(f->d_act); (void)hipFree(f->d_rej[0]); (void)hipFree(f->d_rej[1]); (void)hipFree(f->d_cnt);
   }
   delete f;
@@ -305,6 +306,7 @@ int sf_flow_set_params(sf_flow* f, const float* flat, int64_t n, int is_device, 
   SF_HIP(hipMemcpyAsync(f->d_flat, flat, (size_t)n * sizeof(float), is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
   const float* src = f->d_flat;
   f->flat_valid = true;
+  f->gt_image_valid = false;  // (sf_flow_log_prob_grad rebuilds its transposed image on its next call)
   if (f->nsf1) { f->params_set = true; return SF_OK; }   // (the MLP engine re-tiles per call)
   if (f->nsfar) {
     std::string err;
@@ -956,7 +958,10 @@ int sf_flow_loss_grad_weighted(sf_flow* f, const float* flat, const float* theta
   std::string err;
   rc = sf_train_loss_grad(f, flat, theta, x, nullptr, (long)B, grad_scale, weights, loss, nullptr, grad, dctx,
                           (hipStream_t)stream, err);
-  if (rc) return fail(rc, err);
+  if (rc) {
+    if (rc == SF_ERR_HIP) f->flat_valid = false;  // failed part-way: the forward image may already hold the caller's vector
+    return fail(rc, err);
+  }
   f->params_set = true;  // the forward image now holds `flat`
   f->flat_valid = false; // ... but the handle's own copy of the logical vector does not
   f->ctab_x = nullptr;
@@ -974,7 +979,10 @@ int sf_flow_loss_grad_rows(sf_flow* f, const float* flat, const float* theta, co
   std::string err;
   rc = sf_train_loss_grad(f, flat, theta, x, reinterpret_cast<const long long*>(rows), (long)B, grad_scale, weights, loss,
                           loss_sum, grad, dctx, (hipStream_t)stream, err);
-  if (rc) return fail(rc, err);
+  if (rc) {
+    if (rc == SF_ERR_HIP) f->flat_valid = false;  // (as above)
+    return fail(rc, err);
+  }
   f->params_set = true;
   f->flat_valid = false;
   f->ctab_x = nullptr;

@@ -147,6 +147,12 @@ struct sf_flow {
   bool flat_valid = false;      // d_flat holds the vector last given to sf_flow_set_params
   float* d_packed = nullptr;    // forward operand image
   float* d_packedT = nullptr;   // transposed operand image (training, lazily built)
+  // transposed INFERENCE image of sf_flow_log_prob_grad (sf_gradtheta.hip): built from d_flat on the first gradient call after
+  // sf_flow_set_params, valid until the next one; buffers of its own, training's d_packedT is rebuilt per call from the caller's vector
+  float* d_gtT = nullptr;
+  int32_t *d_gt1 = nullptr, *d_gt2 = nullptr;
+  bool gt_image_valid = false;
+  long gt_simds = 0;            // SIMDs of the handle's device (4 per CU), asked once: the width a stash-bounded launch keeps
   float* d_cst = nullptr;
   unsigned short* d_packedB = nullptr;  // bf16 hidden operand image (hidden_bf16)
   int32_t* d_bsrc = nullptr;

@@ -41,6 +41,11 @@ def _f32c(t, device) -> torch.Tensor:
     return t.to(device=device, dtype=torch.float32).contiguous()
 
 
+def spec_supports_log_prob_grad(spec) -> bool:
+    """Whether the theta-gradient kernel (sf_flow_log_prob_grad) is built for this flow: MAF and the coupling NSF (D >= 2)."""
+    return spec.kind == "maf" or (spec.kind == "nsf" and spec.D >= 2)
+
+
 class HipFlow:
     """Owner of an ``sf_flow`` handle."""
 
@@ -165,6 +170,30 @@ class HipFlow:
         out = torch.empty(B, dtype=torch.float32, device=self.device)
         _lib.check(self.lib.sf_flow_log_prob(self.handle, _ptr(theta), _ptr(x), B, _ptr(out), _stream(self.device)))
         return out
+
+    GRAD_KINDS = ("maf", "nsf")
+
+    def supports_log_prob_grad(self) -> bool:
+        """Whether ``log_prob_grad`` exists for this flow: MAF and the coupling NSF (D >= 2)."""
+        return spec_supports_log_prob_grad(self.spec)
+
+    def log_prob_grad(self, theta, x, rows_per_x: int = 1, want_lp: bool = True, want_grad: bool = True):
+        """(lp [B], dtheta [B, D]) = log q(theta_b | x[b // rows_per_x]) and its gradient in theta (sf_flow_log_prob_grad).
+        ``x`` is [ceil(B / rows_per_x), C]: ``rows_per_x`` consecutive rows of theta share a context row.  An output that
+        is not wanted is None (without the gradient only the forward half runs)."""
+        self._dev()
+        theta, x = _f32c(theta, self.device), _f32c(x, self.device)
+        B, R = theta.shape[0], int(rows_per_x)
+        if R < 1:
+            raise ValueError("rows_per_x must be >= 1")
+        if theta.dim() != 2 or theta.shape[1] != self.spec.D or x.shape != ((B + R - 1) // R, self.spec.C):
+            raise ValueError(f"theta {tuple(theta.shape)} / x {tuple(x.shape)} do not match (B,{self.spec.D}) / "
+                             f"(ceil(B/{R}),{self.spec.C})")
+        lp = torch.empty(B, dtype=torch.float32, device=self.device) if want_lp else None
+        g = torch.empty_like(theta) if want_grad else None
+        _lib.check(self.lib.sf_flow_log_prob_grad(self.handle, _ptr(theta), _ptr(x), R, B, _ptr(lp), _ptr(g),
+                                                  _stream(self.device)))
+        return lp, g
 
     def inverse(self, z, x) -> Tuple[torch.Tensor, torch.Tensor]:
         self._dev()

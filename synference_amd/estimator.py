@@ -17,7 +17,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from .engine import HipFlow
+from .engine import HipFlow, spec_supports_log_prob_grad
 from .spec import FlowSpec, init_params, num_params, random_perms, state_dict_views, zscore_stats
 
 SUPPORTED_MODELS = ("maf", "nsf")
@@ -25,7 +25,8 @@ SUPPORTED_MODELS = ("maf", "nsf")
 
 class _NegLogProb(torch.autograd.Function):
     """loss_b = -log p(theta_b | x_b); backward is the weighted HIP backward sweep
-    (vector-Jacobian product with the incoming per-sample gradient)."""
+    (vector-Jacobian product with the incoming per-sample gradient).  The gradient with respect to theta comes from
+    the theta-gradient kernel (HipFlow.log_prob_grad) for the kinds that have one, and stays None for the others."""
 
     @staticmethod
     def forward(ctx, flat, theta, x, est):
@@ -37,10 +38,18 @@ class _NegLogProb(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout):
         flat, theta, x = ctx.saved_tensors
-        dctx = torch.empty_like(x) if ctx.needs_input_grad[2] else None
-        _, grad = ctx.est.flow.loss_grad(flat.detach(), theta, x, 1.0, weights=gout.contiguous(), dctx_out=dctx)
-        ctx.est._packed_version = None  # loss_grad re-tiled the image from `flat`; re-check next call
-        return (grad if ctx.needs_input_grad[0] else None), None, dctx, None
+        est = ctx.est
+        dtheta = None
+        if ctx.needs_input_grad[1] and est.flow.supports_log_prob_grad():
+            est._sync_params()   # (the handle's own vector: the gradient kernel's transposed image is built from it)
+            _, g = est.flow.log_prob_grad(theta.detach(), x.detach(), want_lp=False)
+            dtheta = -g * gout[:, None]
+        grad = dctx = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[2]:
+            dctx = torch.empty_like(x) if ctx.needs_input_grad[2] else None
+            _, grad = est.flow.loss_grad(flat.detach(), theta.detach(), x, 1.0, weights=gout.contiguous(), dctx_out=dctx)
+            est._packed_version = None  # loss_grad re-tiled the image from `flat`; re-check next call
+        return (grad if ctx.needs_input_grad[0] else None), dtheta, dctx, None
 
 
 class FlowEstimator(nn.Module):
@@ -119,7 +128,10 @@ class FlowEstimator(nn.Module):
         x = context if context is not None else condition
         theta = torch.as_tensor(inputs, dtype=torch.float32, device=self.flat.device)
         e = self.embed(x)
-        if torch.is_grad_enabled() and (self.flat.requires_grad or e.requires_grad):
+        # (theta alone asks for the autograd path only where the theta gradient exists: for the other kinds the result
+        #  carries no graph, as before, and a backward() through it raises instead of leaving theta.grad at None)
+        theta_grad = theta.requires_grad and spec_supports_log_prob_grad(self.spec)
+        if torch.is_grad_enabled() and (self.flat.requires_grad or e.requires_grad or theta_grad):
             return -_NegLogProb.apply(self.flat, theta, e.contiguous(), self)
         self._sync_params()
         return self.flow.log_prob(theta, e)

@@ -3,7 +3,8 @@
 Same method names, argument meaning and error behaviour as ref: src/synference/sbi_runner.py for
   run_single_sbi (4392-4435), create_priors (3442-3450), split_dataset (3407-3440),
   sample_posterior (6350-6474), log_prob (7162-7198), fit_catalogue sampling + quantile section
-  (2948-2989, 3230-3282), evaluate_model's flow-derived metrics (6484-6735).
+  (2948-2989, 3230-3282), evaluate_model's flow-derived metrics (6484-6735), calculate_MAP (7204-7207: a stub there;
+  here [UPSTREAM] sbi ``posterior.map`` per catalogue row, synference_amd/map.py).
 What is NOT here (out of scope): library generation, feature engineering from
 raw fluxes, noise models, Optuna search, MDN / likelihood / ratio engines, MCMC / VI samplers,
 plotting.  Asking for them raises ``ValueError`` rather than falling through to another backend.
@@ -726,6 +727,56 @@ class SBI_Fitter:
         lp = posteriors.log_prob_catalogue(yt, Xt, norm_posterior, num_rejection_samples)
         return lp.double().cpu().numpy()
 
+    def _map_rows(self, X, posteriors, row_offset: int = 0, **map_kwargs):
+        """(theta_map (N, D), log_prob_map (N,)) float64 of the rows of X; under a process group rank r works rows
+        [r N / W, (r+1) N / W) and the blocks are gathered on every rank (streams keyed by the row's position)."""
+        from .map import check_map_args
+        from .posterior import all_gather_rows, broadcast_seed, dist_world, shard_bounds
+        kw = dict(num_iter=1000, num_to_optimize=100, learning_rate=0.01, init_method="posterior", num_init_samples=1000,
+                  save_best_every=10, seed=None)
+        unknown = {k: v for k, v in map_kwargs.items() if k not in kw and k not in ("show_progress_bars", "force_update")}
+        if unknown:
+            raise TypeError(f"calculate_MAP: unknown keyword(s) {sorted(unknown)}")
+        kw.update({k: v for k, v in map_kwargs.items() if k in kw})
+        check_map_args(kw["num_iter"], kw["num_to_optimize"], kw["learning_rate"], kw["init_method"], kw["num_init_samples"],
+                       kw["save_best_every"])
+        Xt = torch.as_tensor(np.asarray(X, dtype=np.float32))
+        rank, world = dist_world()
+        if world > 1 and len(Xt) >= world:
+            if kw["seed"] is None:
+                kw["seed"] = posteriors._next_seed(None)
+            kw["seed"] = broadcast_seed(kw["seed"])
+            b = shard_bounds(len(Xt), world)
+            sl = slice(b[rank], b[rank + 1])
+            if torch.is_tensor(kw["init_method"]):
+                kw["init_method"] = kw["init_method"][sl]
+            th, lp = posteriors.map_catalogue(Xt[sl], row_offset=int(row_offset) + b[rank], **kw)
+            th, lp = all_gather_rows(th.contiguous(), b), all_gather_rows(lp.contiguous(), b)
+        else:
+            th, lp = posteriors.map_catalogue(Xt, row_offset=int(row_offset), **kw)
+        return th.double().cpu().numpy(), lp.double().cpu().numpy()
+
+    def calculate_MAP(self, X: np.ndarray = None, posteriors: object = None, **map_kwargs) -> np.ndarray:
+        """(N, D) float64 posterior mode of every row of X (default: the test split).  The reference names the method and
+        leaves it empty (sbi_runner.py:7204-7207); this is [UPSTREAM] sbi ``posterior.map`` per row, with its keywords
+        (``num_iter``, ``num_to_optimize``, ``learning_rate``, ``init_method``, ``num_init_samples``, ``save_best_every``)
+        plus ``seed``.  The log-density at the modes is kept in ``self.last_map_log_prob``.  Like ``sample_posterior``
+        the result is in the units the posterior was trained in (``prior_method="manual"``: nothing un-scales, as there);
+        under a process group the rows are sharded like ``sample_posterior``'s and every rank returns the whole array."""
+        if posteriors is None:
+            posteriors = self.posteriors
+        if X is None:
+            if getattr(self, "_X_test", None) is not None:
+                X = self._X_test
+            else:
+                raise ValueError("X must be provided or set in the object.")
+        X = np.asarray(X, dtype=np.float32)
+        if X.ndim == 1:
+            X = X[None, :]
+        th, lp = self._map_rows(X, posteriors, **map_kwargs)
+        self.last_map_log_prob = lp
+        return th
+
     def save_state(self, out_dir, name_append: str = "", save_method: str = "joblib", has_grid: bool = True, **extras):
         """ref: sbi_runner.py:693-830 -- what a later session needs next to ``{name}_{append}_posterior.pkl``: feature /
         parameter names and units, the prior, the feature-array flags and (``has_grid``) the feature and parameter
@@ -932,8 +983,14 @@ class SBI_Fitter:
                       override_transformations: dict = {}, timeout_seconds_per_row: float = 5,
                       return_feature_array: bool = False, return_full_samples: bool = False,
                       missing_data_mcmc: bool = False, missing_data_mcmc_params: Optional[dict] = None,
-                      missing_data_sigma=None, check_out_of_distribution: bool = False, outlier_methods=None, **unknown):
+                      missing_data_sigma=None, check_out_of_distribution: bool = False, outlier_methods=None,
+                      map_estimate: bool = False, map_kwargs: Optional[dict] = None, **unknown):
         """Sampling + quantile section of the reference's fit_catalogue (sbi_runner.py:3230-3282).
+
+        ``map_estimate=True`` (an addition; default False: the call is what it was): the table gains ``{param}_map`` per
+        parameter and ``map_log_prob`` -- the posterior mode of every row by ``calculate_MAP`` (``map_kwargs``: its
+        keywords) -- NaN for masked rows, out-of-distribution rows and rows with missing bands.  The quantile columns are
+        those of the same call without the switch: the MAP inits are drawn on a seed stream of their own.
 
         ``observations`` is a pandas DataFrame / dict of columns / (N, C) array.  With ``flux_units`` given and a feature
         array that was built by ``create_feature_array_from_raw_photometry`` the table goes through
@@ -963,6 +1020,7 @@ class SBI_Fitter:
         _warn_unknown("fit_catalogue", unknown)
         return_samples = return_samples or return_full_samples
         ood_kw = dict(check_out_of_distribution=check_out_of_distribution, outlier_methods=outlier_methods)
+        ood_kw.update(map_estimate=map_estimate, map_kwargs=map_kwargs)   # (both travel with the check to the inner call)
         if missing_data_mcmc and not return_feature_array:
             return self._fit_catalogue_missing(observations, columns_to_feature_names, missing_data_flag, flux_units,
                                                override_transformations, missing_data_mcmc_params, missing_data_sigma, quantiles,
@@ -1016,6 +1074,7 @@ class SBI_Fitter:
             return good, obs_mask                    # sbi_runner.py:3093-3095: the features as built, the mask with the outliers
         edges = np.flatnonzero(np.diff(np.concatenate([[False], keep, [False]]).astype(np.int8)))
         runs = list(zip(edges[0::2].tolist(), edges[1::2].tolist()))   # [a, b) blocks of rows to sample
+        kept_runs, seed_given = list(runs), seed     # (for the MAP columns: the runs and the seed as the caller gave them)
         if seed is None and len(runs) > 1:
             seed = self.posteriors._next_seed(None)
         tmo = float(timeout_seconds_per_row) * max(1, int((~obs_mask).sum())) if timeout_seconds_per_row else None
@@ -1065,6 +1124,8 @@ class SBI_Fitter:
                     table[f"{param}_{int(qv * 100)}"] = qarr[:, i, j]
             if check_out_of_distribution:
                 table["is_outlier"] = obs_mask
+            if map_estimate:
+                self._add_map_columns(table, good, np.flatnonzero(finite), kept_runs, seed_given, map_kwargs)
             return table
         samples = np.full((len(df), num_samples, len(self.fitted_parameter_names)), np.nan)
         pos = np.flatnonzero(finite)
@@ -1085,7 +1146,32 @@ class SBI_Fitter:
                 table[f"{param}_{int(quantiles[j] * 100)}"] = col
         if check_out_of_distribution:
             table["is_outlier"] = obs_mask
+        if map_estimate:
+            self._add_map_columns(table, good, pos, kept_runs, seed_given, map_kwargs)
         return (table, samples) if return_samples else table
+
+    def _add_map_columns(self, table, good, pos, runs, seed, map_kwargs):
+        """fit_catalogue(map_estimate=True): ``{param}_map`` and ``map_log_prob`` from the rows the quantile path sampled --
+        ``good`` (table rows ``pos``), its ``runs`` [a, b) of kept rows -- NaN elsewhere.  One ``_map_rows`` call per run,
+        streams keyed by the row's position in ``good``; an (N, R0, D) ``init_method`` tensor is indexed by table row."""
+        th = np.full((len(table), len(self.fitted_parameter_names)), np.nan)
+        lp = np.full(len(table), np.nan)
+        mk = dict(map_kwargs or {})
+        if "seed" not in mk:   # a stream of its own: the quantile draws of this call do not move
+            mk["seed"] = None if seed is None else (int(seed) + 0xD1B54A32D192ED03) & (2 ** 63 - 1)
+        if mk["seed"] is None and len(runs) > 1:
+            mk["seed"] = self.posteriors._next_seed(None)
+        inits = mk.get("init_method")
+        if torch.is_tensor(inits) and (inits.dim() != 3 or inits.shape[0] != len(table)):
+            raise ValueError(f"map_kwargs['init_method']: an (N = {len(table)}, R0, D) tensor, one block of inits per table row, "
+                             f"not {tuple(inits.shape)}")
+        for a, b in runs:
+            if torch.is_tensor(inits):
+                mk["init_method"] = inits[torch.as_tensor(pos[a:b])]
+            th[pos[a:b]], lp[pos[a:b]] = self._map_rows(good[a:b], self.posteriors, row_offset=a, **mk)
+        for i, param in enumerate(self.simple_fitted_parameter_names):
+            table[f"{param}_map"] = th[:, i]
+        table["map_log_prob"] = lp
 
     # ---- out-of-distribution check (synference_amd/ood.py) ------------------------------------------------------------------
     def _ood_base(self):

@@ -242,6 +242,24 @@ class FlowPosterior:
     def potential_fn(self, theta, x):
         return self.log_prob_catalogue(theta, x, norm_posterior=False)
 
+    # ---- posterior mode ---------------------------------------------------------------------
+    def map_catalogue(self, X, num_iter=1000, num_to_optimize=100, learning_rate=0.01, init_method="posterior",
+                      num_init_samples=1000, save_best_every=10, seed: Optional[int] = None, row_offset: int = 0):
+        """Posterior mode of every row of X: (theta_map [N, D], log_prob_map [N]) float32 device tensors; a row without a
+        finite init is NaN.  [UPSTREAM] ``DirectPosterior.map`` -> ``gradient_ascent`` (arguments as there) on the
+        device: see synference_amd/map.py.  ``log_prob_map`` is the raw estimator density (no leakage term: it is
+        constant in theta).  ``init_method``: "posterior" (accepted draws, keyed by ``seed`` and the row's position
+        ``row_offset`` + i in the whole catalogue) or an (N, R0, D) tensor of inits."""
+        from .map import map_catalogue
+        return map_catalogue(self, [self], None, X, num_iter, num_to_optimize, learning_rate, init_method, num_init_samples,
+                             save_best_every, seed, row_offset)
+
+    def map(self, x=None, num_iter=1000, num_to_optimize=100, learning_rate=0.01, init_method="posterior",
+            num_init_samples=1000, save_best_every=10, show_progress_bars=False, force_update=False, seed: Optional[int] = None):
+        from .map import map_one
+        return map_one(self, x, num_iter, num_to_optimize, learning_rate, init_method, num_init_samples, save_best_every,
+                       show_progress_bars, force_update, seed)
+
 
 class EnsemblePosterior:
     """Weighted mixture of posteriors ([UPSTREAM] sbi EnsemblePosterior; built in the reference at
@@ -347,6 +365,21 @@ class EnsemblePosterior:
 
     def potential_fn(self, theta, x):
         return self.log_prob_catalogue(theta, x, norm_posterior=False)
+
+    # ---- posterior mode ---------------------------------------------------------------------
+    def map_catalogue(self, X, num_iter=1000, num_to_optimize=100, learning_rate=0.01, init_method="posterior",
+                      num_init_samples=1000, save_best_every=10, seed: Optional[int] = None, row_offset: int = 0):
+        """Mode of the mixture potential logsumexp_e(log w_e + log q_e(theta | x)) of every row of X (its gradient: the
+        softmax-weighted sum of the members' gradients); see FlowPosterior.map_catalogue."""
+        from .map import map_catalogue
+        return map_catalogue(self, self.posteriors, self._weights, X, num_iter, num_to_optimize, learning_rate, init_method,
+                             num_init_samples, save_best_every, seed, row_offset)
+
+    def map(self, x=None, num_iter=1000, num_to_optimize=100, learning_rate=0.01, init_method="posterior",
+            num_init_samples=1000, save_best_every=10, show_progress_bars=False, force_update=False, seed: Optional[int] = None):
+        from .map import map_one
+        return map_one(self, x, num_iter, num_to_optimize, learning_rate, init_method, num_init_samples, save_best_every,
+                       show_progress_bars, force_update, seed)
 
 
 def device_quantiles(samples: torch.Tensor, quantiles) -> torch.Tensor:
