@@ -169,6 +169,17 @@ def load() -> C.CDLL:
     return lib
 
 
+def ptr(t):
+    """A tensor's device address for a ``void*`` argument (None -> NULL)."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def stream_ptr(device):
+    """The ``hipStream_t`` of torch's current stream on ``device``."""
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
 def check(rc: int) -> None:
     if rc != 0:
         msg = load().sf_last_error().decode("utf-8", "replace")

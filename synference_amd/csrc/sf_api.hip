@@ -19,25 +19,16 @@
 namespace {
 thread_local std::string g_err;
 
-int fail(int code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
 int hip_fail(hipError_t e, const char* what) {
-  return fail(SF_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+  return sf_fail(SF_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
-#define SF_HIP(call)                                  \
-  do {                                                \
-    hipError_t e_ = (call);                           \
-    if (e_ != hipSuccess) return hip_fail(e_, #call); \
-  } while (0)
 }  // namespace
 
 static int ensure_device(sf_flow* f) {
   if (f->nsf1 || f->nsfar) {
     if (f->dev_ready) return SF_OK;
     int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || nd == 0) return fail(SF_ERR_NO_DEVICE, "no HIP device visible");
+    if (hipGetDeviceCount(&nd) != hipSuccess || nd == 0) return sf_fail(SF_ERR_NO_DEVICE, "no HIP device visible");
     hipError_t e = hipMalloc(&f->d_flat, (size_t)f->L.n_params * sizeof(float));
     if (e != hipSuccess) return hip_fail(e, "hipMalloc(d_flat)");
     f->dev_ready = true;
@@ -46,40 +37,40 @@ static int ensure_device(sf_flow* f) {
   if (f->dev_ready) return SF_OK;
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
-    return fail(SF_ERR_NO_DEVICE, "no HIP device visible: the gfx950 flow engine has no CPU fallback");
+    return sf_fail(SF_ERR_NO_DEVICE, "no HIP device visible: the gfx950 flow engine has no CPU fallback");
   const size_t np = (size_t)f->L.n_packed;
-  SF_HIP(hipMalloc(&f->d_packed, np * sizeof(float)));
-  SF_HIP(hipMemset(f->d_packed, 0, np * sizeof(float)));
-  SF_HIP(hipMalloc(&f->d_cst, f->L.cst.size() * sizeof(float)));
-  SF_HIP(hipMemcpy(f->d_cst, f->L.cst.data(), f->L.cst.size() * sizeof(float), hipMemcpyHostToDevice));
-  SF_HIP(hipMalloc(&f->d_s1, np * sizeof(int32_t)));
-  SF_HIP(hipMalloc(&f->d_s2, np * sizeof(int32_t)));
-  SF_HIP(hipMemcpy(f->d_s1, f->L.src1.data(), np * sizeof(int32_t), hipMemcpyHostToDevice));
-  SF_HIP(hipMemcpy(f->d_s2, f->L.src2.data(), np * sizeof(int32_t), hipMemcpyHostToDevice));
+  SF_TRY_SET(hipMalloc(&f->d_packed, np * sizeof(float)));
+  SF_TRY_SET(hipMemset(f->d_packed, 0, np * sizeof(float)));
+  SF_TRY_SET(hipMalloc(&f->d_cst, f->L.cst.size() * sizeof(float)));
+  SF_TRY_SET(hipMemcpy(f->d_cst, f->L.cst.data(), f->L.cst.size() * sizeof(float), hipMemcpyHostToDevice));
+  SF_TRY_SET(hipMalloc(&f->d_s1, np * sizeof(int32_t)));
+  SF_TRY_SET(hipMalloc(&f->d_s2, np * sizeof(int32_t)));
+  SF_TRY_SET(hipMemcpy(f->d_s1, f->L.src1.data(), np * sizeof(int32_t), hipMemcpyHostToDevice));
+  SF_TRY_SET(hipMemcpy(f->d_s2, f->L.src2.data(), np * sizeof(int32_t), hipMemcpyHostToDevice));
   if ((f->L.dev.m16_ok || f->L.nsfS.ok) && f->L.n_packed16 > 0) {
     const size_t n16 = (size_t)f->L.n_packed16;
-    SF_HIP(hipMalloc(&f->d_packed16, n16 * sizeof(float)));
-    SF_HIP(hipMalloc(&f->d_s16a, n16 * sizeof(int32_t)));
-    SF_HIP(hipMalloc(&f->d_s16b, n16 * sizeof(int32_t)));
-    SF_HIP(hipMemcpy(f->d_s16a, f->L.src16a.data(), n16 * sizeof(int32_t), hipMemcpyHostToDevice));
-    SF_HIP(hipMemcpy(f->d_s16b, f->L.src16b.data(), n16 * sizeof(int32_t), hipMemcpyHostToDevice));
+    SF_TRY_SET(hipMalloc(&f->d_packed16, n16 * sizeof(float)));
+    SF_TRY_SET(hipMalloc(&f->d_s16a, n16 * sizeof(int32_t)));
+    SF_TRY_SET(hipMalloc(&f->d_s16b, n16 * sizeof(int32_t)));
+    SF_TRY_SET(hipMemcpy(f->d_s16a, f->L.src16a.data(), n16 * sizeof(int32_t), hipMemcpyHostToDevice));
+    SF_TRY_SET(hipMemcpy(f->d_s16b, f->L.src16b.data(), n16 * sizeof(int32_t), hipMemcpyHostToDevice));
   }
   if ((f->L.dev.m16_ok || f->L.nsfS.ok) && f->L.n_packed16B > 0) {
     const size_t nB = (size_t)f->L.n_packed16B;
-    SF_HIP(hipMalloc(&f->d_packed16B, nB * sizeof(unsigned short)));
-    SF_HIP(hipMalloc(&f->d_s16B, nB * sizeof(int32_t)));
-    SF_HIP(hipMemcpy(f->d_s16B, f->L.src16B.data(), nB * sizeof(int32_t), hipMemcpyHostToDevice));
+    SF_TRY_SET(hipMalloc(&f->d_packed16B, nB * sizeof(unsigned short)));
+    SF_TRY_SET(hipMalloc(&f->d_s16B, nB * sizeof(int32_t)));
+    SF_TRY_SET(hipMemcpy(f->d_s16B, f->L.src16B.data(), nB * sizeof(int32_t), hipMemcpyHostToDevice));
   }
   if (f->L.n_packedB > 0) {
-    SF_HIP(hipMalloc(&f->d_packedB, (size_t)f->L.n_packedB * sizeof(unsigned short)));
-    SF_HIP(hipMalloc(&f->d_bsrc, (size_t)f->L.n_packedB * sizeof(int32_t)));
-    SF_HIP(hipMemcpy(f->d_bsrc, f->L.srcB.data(), (size_t)f->L.n_packedB * sizeof(int32_t), hipMemcpyHostToDevice));
+    SF_TRY_SET(hipMalloc(&f->d_packedB, (size_t)f->L.n_packedB * sizeof(unsigned short)));
+    SF_TRY_SET(hipMalloc(&f->d_bsrc, (size_t)f->L.n_packedB * sizeof(int32_t)));
+    SF_TRY_SET(hipMemcpy(f->d_bsrc, f->L.srcB.data(), (size_t)f->L.n_packedB * sizeof(int32_t), hipMemcpyHostToDevice));
   }
-  SF_HIP(hipMalloc(&f->d_flat, (size_t)f->L.n_params * sizeof(float)));
-  SF_HIP(hipMalloc(&f->d_cnt, SF_MAX_ROUNDS * sizeof(uint32_t)));
-  SF_HIP(hipHostMalloc((void**)&f->h_cnt, SF_MAX_ROUNDS * sizeof(uint32_t), hipHostMallocDefault));
-  SF_HIP(hipEventCreate(&f->ev_dense[0]));
-  SF_HIP(hipEventCreate(&f->ev_dense[1]));
+  SF_TRY_SET(hipMalloc(&f->d_flat, (size_t)f->L.n_params * sizeof(float)));
+  SF_TRY_SET(hipMalloc(&f->d_cnt, SF_MAX_ROUNDS * sizeof(uint32_t)));
+  SF_TRY_SET(hipHostMalloc((void**)&f->h_cnt, SF_MAX_ROUNDS * sizeof(uint32_t), hipHostMallocDefault));
+  SF_TRY_SET(hipEventCreate(&f->ev_dense[0]));
+  SF_TRY_SET(hipEventCreate(&f->ev_dense[1]));
   f->dev_ready = true;
   return SF_OK;
 }
@@ -95,12 +86,12 @@ int sf_device_count(void) {
 }
 
 int sf_flow_create(const sf_flow_desc* desc, sf_flow** out) {
-  if (!desc || !out) return fail(SF_ERR_INVALID, "null argument");
+  if (!desc || !out) return sf_fail(SF_ERR_INVALID, "null argument");
   if (desc->kind == SF_NSF && desc->D == 1) {  // sbi's ContextSplineMap flow (sf_nsf1.hip)
     sf_flow* f1 = new sf_flow();
     std::string err;
     int rc = sf_nsf1_create(*desc, &f1->nsf1, err);
-    if (rc) { delete f1; return fail(rc, err); }
+    if (rc) { delete f1; return sf_fail(rc, err); }
     std::memset(&f1->L.dev, 0, sizeof(f1->L.dev));
     std::memset(&f1->L.trc, 0, sizeof(f1->L.trc));
     std::memset(&f1->L.nsc, 0, sizeof(f1->L.nsc));
@@ -115,7 +106,7 @@ int sf_flow_create(const sf_flow_desc* desc, sf_flow** out) {
     sf_flow* fa = new sf_flow();
     std::string err;
     int rc = sf_nsfar_create(*desc, &fa->nsfar, err);
-    if (rc) { delete fa; return fail(rc, err); }
+    if (rc) { delete fa; return sf_fail(rc, err); }
     std::memset(&fa->L.dev, 0, sizeof(fa->L.dev));
     std::memset(&fa->L.trc, 0, sizeof(fa->L.trc));
     std::memset(&fa->L.nsc, 0, sizeof(fa->L.nsc));
@@ -130,7 +121,7 @@ int sf_flow_create(const sf_flow_desc* desc, sf_flow** out) {
   if (!sf_build_layout(*desc, f->L)) {
     std::string e = f->L.error;
     delete f;
-    return fail(SF_ERR_INVALID, e);
+    return sf_fail(SF_ERR_INVALID, e);
   }
   *out = f;
   return SF_OK;
@@ -168,14 +159,14 @@ int64_t sf_flow_num_params(const sf_flow* f) { return f ? f->L.n_params : 0; }
 int64_t sf_flow_packed_size(const sf_flow* f) { return !f ? 0 : (f->nsfar ? (int64_t)f->nsfar->src.size() : f->L.n_packed); }
 
 int sf_flow_pack_table(const sf_flow* f, int32_t* src1, int32_t* src2, int64_t n_packed) {
-  if (!f || !src1 || !src2) return fail(SF_ERR_INVALID, "null argument");
+  if (!f || !src1 || !src2) return sf_fail(SF_ERR_INVALID, "null argument");
   if (f->nsfar) {   // one gather table (sf_nsfar.hip); the second is "none" everywhere
-    if (n_packed != (int64_t)f->nsfar->src.size()) return fail(SF_ERR_INVALID, "n_packed mismatch");
+    if (n_packed != (int64_t)f->nsfar->src.size()) return sf_fail(SF_ERR_INVALID, "n_packed mismatch");
     std::memcpy(src1, f->nsfar->src.data(), (size_t)n_packed * sizeof(int32_t));
     for (int64_t i = 0; i < n_packed; ++i) src2[i] = -1;
     return SF_OK;
   }
-  if (n_packed != f->L.n_packed) return fail(SF_ERR_INVALID, "n_packed mismatch");
+  if (n_packed != f->L.n_packed) return sf_fail(SF_ERR_INVALID, "n_packed mismatch");
   if (n_packed == 0) return SF_OK;   // (empty tables have no storage to copy from)
   std::memcpy(src1, f->L.src1.data(), (size_t)n_packed * sizeof(int32_t));
   std::memcpy(src2, f->L.src2.data(), (size_t)n_packed * sizeof(int32_t));
@@ -185,8 +176,8 @@ int sf_flow_pack_table(const sf_flow* f, int32_t* src1, int32_t* src2, int64_t n
 int64_t sf_flow_packed16_size(const sf_flow* f) { return (f && f->L.dev.m16_ok) ? f->L.n_packed16 : 0; }
 
 int sf_flow_pack_table16(const sf_flow* f, int32_t* src1, int32_t* src2, int64_t n_packed16) {
-  if (!f || !src1 || !src2) return fail(SF_ERR_INVALID, "null argument");
-  if (!f->L.dev.m16_ok || n_packed16 != f->L.n_packed16) return fail(SF_ERR_INVALID, "no 16-row image or size mismatch");
+  if (!f || !src1 || !src2) return sf_fail(SF_ERR_INVALID, "null argument");
+  if (!f->L.dev.m16_ok || n_packed16 != f->L.n_packed16) return sf_fail(SF_ERR_INVALID, "no 16-row image or size mismatch");
   std::memcpy(src1, f->L.src16a.data(), (size_t)n_packed16 * sizeof(int32_t));
   std::memcpy(src2, f->L.src16b.data(), (size_t)n_packed16 * sizeof(int32_t));
   return SF_OK;
@@ -195,8 +186,8 @@ int sf_flow_pack_table16(const sf_flow* f, int32_t* src1, int32_t* src2, int64_t
 int64_t sf_flow_packed16b_size(const sf_flow* f) { return (f && f->L.dev.m16_ok) ? f->L.n_packed16B : 0; }
 
 int sf_flow_pack_table16b(const sf_flow* f, int32_t* src, int64_t n) {
-  if (!f || !src) return fail(SF_ERR_INVALID, "null argument");
-  if (!f->L.dev.m16_ok || n != f->L.n_packed16B) return fail(SF_ERR_INVALID, "no split-bf16 image or size mismatch");
+  if (!f || !src) return sf_fail(SF_ERR_INVALID, "null argument");
+  if (!f->L.dev.m16_ok || n != f->L.n_packed16B) return sf_fail(SF_ERR_INVALID, "no split-bf16 image or size mismatch");
   std::memcpy(src, f->L.src16B.data(), (size_t)n * sizeof(int32_t));
   return SF_OK;
 }
@@ -206,9 +197,9 @@ int64_t sf_flow_trainc_grad_size(const sf_flow* f) { return (f && (f->L.trc.ok |
 int64_t sf_flow_cst_size(const sf_flow* f) { return f ? (int64_t)f->L.cst.size() : 0; }
 int sf_flow_trainc_table(const sf_flow* f, int32_t* src1, int32_t* src2, int64_t n, int32_t* gdst, int64_t n_params,
                          int32_t* desc, float* cst, int64_t n_cst) {
-  if (!f || !src1 || !src2 || !gdst || !desc || !cst) return fail(SF_ERR_INVALID, "null argument");
+  if (!f || !src1 || !src2 || !gdst || !desc || !cst) return sf_fail(SF_ERR_INVALID, "null argument");
   if ((!f->L.trc.ok && !f->L.nsc.ok) || n != f->L.n_imgC || n_params != f->L.n_params || n_cst != (int64_t)f->L.cst.size())
-    return fail(SF_ERR_INVALID, "no cooperative training image or size mismatch");
+    return sf_fail(SF_ERR_INVALID, "no cooperative training image or size mismatch");
   static_assert(sizeof(SfTrcDev) <= 64 * sizeof(int32_t) && sizeof(SfNscDev) <= 64 * sizeof(int32_t), "descriptor words");
   std::memcpy(src1, f->L.srcC1.data(), (size_t)n * sizeof(int32_t));
   std::memcpy(src2, f->L.srcC2.data(), (size_t)n * sizeof(int32_t));
@@ -221,7 +212,7 @@ int sf_flow_trainc_table(const sf_flow* f, int32_t* src1, int32_t* src2, int64_t
 }
 
 int sf_flow_describe(const sf_flow* f, char* buf, size_t buflen) {
-  if (!f || !buf) return fail(SF_ERR_INVALID, "null argument");
+  if (!f || !buf) return sf_fail(SF_ERR_INVALID, "null argument");
   const SfDev& v = f->L.dev;
   std::string s = "{";
   auto add = [&](const char* k, long val) { s += "\"" + std::string(k) + "\": " + std::to_string(val) + ", "; };
@@ -239,7 +230,7 @@ int sf_flow_describe(const sf_flow* f, char* buf, size_t buflen) {
       s += last ? "]}" : "], ";
     };
     arr("perm", n.perm, false); arr("ptype", n.ptype, false); arr("tend", n.tend, false); arr("ord", n.ord, false); arr("dimof", n.dimof, true);
-    if (s.size() + 1 > buflen) return fail(SF_ERR_INVALID, "buffer too small");
+    if (s.size() + 1 > buflen) return sf_fail(SF_ERR_INVALID, "buffer too small");
     std::memcpy(buf, s.c_str(), s.size() + 1);
     return SF_OK;
   }
@@ -291,19 +282,19 @@ int sf_flow_describe(const sf_flow* f, char* buf, size_t buflen) {
     s += t;
   }
   s += "]}";
-  if (s.size() + 1 > buflen) return fail(SF_ERR_INVALID, "buffer too small");
+  if (s.size() + 1 > buflen) return sf_fail(SF_ERR_INVALID, "buffer too small");
   std::memcpy(buf, s.c_str(), s.size() + 1);
   return SF_OK;
 }
 
 int sf_flow_set_params(sf_flow* f, const float* flat, int64_t n, int is_device, void* stream) {
-  if (!f || !flat) return fail(SF_ERR_INVALID, "null argument");
-  if (n != f->L.n_params) return fail(SF_ERR_INVALID, "parameter count mismatch");
+  if (!f || !flat) return sf_fail(SF_ERR_INVALID, "null argument");
+  if (n != f->L.n_params) return sf_fail(SF_ERR_INVALID, "parameter count mismatch");
   int rc = ensure_device(f);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   // the handle keeps its own copy of the logical vector (sf_flow_get_params)
-  SF_HIP(hipMemcpyAsync(f->d_flat, flat, (size_t)n * sizeof(float), is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+  SF_TRY_SET(hipMemcpyAsync(f->d_flat, flat, (size_t)n * sizeof(float), is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
   const float* src = f->d_flat;
   f->flat_valid = true;
   f->gt_image_valid = false;  // (sf_flow_log_prob_grad rebuilds its transposed image on its next call)
@@ -311,82 +302,82 @@ int sf_flow_set_params(sf_flow* f, const float* flat, int64_t n, int is_device, 
   if (f->nsfar) {
     std::string err;
     rc = sf_nsfar_pack(f->nsfar, src, st, err);
-    if (rc) return fail(rc, err);
+    if (rc) return sf_fail(rc, err);
     f->params_set = true;
     return SF_OK;
   }
-  SF_HIP(sf_launch_pack(src, f->d_s1, f->d_s2, f->d_packed, (long)f->L.n_packed, st));
-  if (f->d_packed16) SF_HIP(sf_launch_pack(src, f->d_s16a, f->d_s16b, f->d_packed16, (long)f->L.n_packed16, st));
+  SF_TRY_SET(sf_launch_pack(src, f->d_s1, f->d_s2, f->d_packed, (long)f->L.n_packed, st));
+  if (f->d_packed16) SF_TRY_SET(sf_launch_pack(src, f->d_s16a, f->d_s16b, f->d_packed16, (long)f->L.n_packed16, st));
   f->wp_stale = true;
-  if (f->d_packed16B) SF_HIP(sf_launch_pack_bf16_split(src, f->d_s16B, f->d_packed16B, (long)f->L.n_packed16B, st));
+  if (f->d_packed16B) SF_TRY_SET(sf_launch_pack_bf16_split(src, f->d_s16B, f->d_packed16B, (long)f->L.n_packed16B, st));
   f->packed16_stale = false;
-  if (f->L.n_packedB > 0) SF_HIP(sf_launch_pack_bf16(src, f->d_bsrc, f->d_packedB, (long)f->L.n_packedB, st));
+  if (f->L.n_packedB > 0) SF_TRY_SET(sf_launch_pack_bf16(src, f->d_bsrc, f->d_packedB, (long)f->L.n_packedB, st));
   f->params_set = true;
   f->ctab_x = nullptr;  // a context table built from the old parameters is stale
   return SF_OK;
 }
 
 int sf_flow_get_params(sf_flow* f, float* flat, int64_t n, int is_device, void* stream) {
-  if (!f || !flat) return fail(SF_ERR_INVALID, "null argument");
-  if (n != f->L.n_params) return fail(SF_ERR_INVALID, "parameter count mismatch");
+  if (!f || !flat) return sf_fail(SF_ERR_INVALID, "null argument");
+  if (n != f->L.n_params) return sf_fail(SF_ERR_INVALID, "parameter count mismatch");
   if (!f->params_set || !f->flat_valid)
-    return fail(SF_ERR_STATE, "no parameters held by the handle: after sf_flow_loss_grad the caller's vector is the master copy "
+    return sf_fail(SF_ERR_STATE, "no parameters held by the handle: after sf_flow_loss_grad the caller's vector is the master copy "
                               "(call sf_flow_set_params first)");
   hipStream_t st = (hipStream_t)stream;
-  SF_HIP(hipMemcpyAsync(flat, f->d_flat, (size_t)n * sizeof(float), is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
-  if (!is_device) SF_HIP(hipStreamSynchronize(st));
+  SF_TRY_SET(hipMemcpyAsync(flat, f->d_flat, (size_t)n * sizeof(float), is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+  if (!is_device) SF_TRY_SET(hipStreamSynchronize(st));
   return SF_OK;
 }
 
 int sf_flow_log_prob(sf_flow* f, const float* theta, const float* x, int64_t B, float* out, void* stream) {
-  if (!f) return fail(SF_ERR_INVALID, "null handle");
+  if (!f) return sf_fail(SF_ERR_INVALID, "null handle");
   if (B == 0) return SF_OK;
-  if (!theta || !x || !out) return fail(SF_ERR_INVALID, "null argument");
-  if (!f->params_set) return fail(SF_ERR_STATE, "sf_flow_set_params has not been called");
-  if (B < 0) return fail(SF_ERR_INVALID, "B < 0");
+  if (!theta || !x || !out) return sf_fail(SF_ERR_INVALID, "null argument");
+  if (!f->params_set) return sf_fail(SF_ERR_STATE, "sf_flow_set_params has not been called");
+  if (B < 0) return sf_fail(SF_ERR_INVALID, "B < 0");
   if (f->nsf1) {
     std::string err;
     int rc = sf_nsf1_log_prob(f->nsf1, f->d_flat, theta, x, (long)B, out, (hipStream_t)stream, err);
-    return rc ? fail(rc, err) : SF_OK;
+    return rc ? sf_fail(rc, err) : SF_OK;
   }
   if (f->nsfar) {
     std::string err;
     int rc = sf_nsfar_log_prob(f->nsfar, theta, x, (long)B, out, (hipStream_t)stream, err);
-    return rc ? fail(rc, err) : SF_OK;
+    return rc ? sf_fail(rc, err) : SF_OK;
   }
-  SF_HIP(sf_launch_logprob(f->dev(), theta, x, (long)B, out, (hipStream_t)stream));
+  SF_TRY_SET(sf_launch_logprob(f->dev(), theta, x, (long)B, out, (hipStream_t)stream));
   return SF_OK;
 }
 
 int sf_flow_inverse_from_noise(sf_flow* f, const float* z, const float* x, int64_t B, float* theta,
                                float* logdet, void* stream) {
-  if (!f) return fail(SF_ERR_INVALID, "null handle");
+  if (!f) return sf_fail(SF_ERR_INVALID, "null handle");
   if (B == 0) return SF_OK;
-  if (!z || !x || !theta) return fail(SF_ERR_INVALID, "null argument");
-  if (!f->params_set) return fail(SF_ERR_STATE, "sf_flow_set_params has not been called");
+  if (!z || !x || !theta) return sf_fail(SF_ERR_INVALID, "null argument");
+  if (!f->params_set) return sf_fail(SF_ERR_STATE, "sf_flow_set_params has not been called");
   if (f->nsf1) {
     std::string err;
     int rc = sf_nsf1_inverse(f->nsf1, f->d_flat, z, x, (long)B, theta, logdet, (hipStream_t)stream, err);
-    return rc ? fail(rc, err) : SF_OK;
+    return rc ? sf_fail(rc, err) : SF_OK;
   }
   if (f->nsfar) {
     std::string err;
     int rc = sf_nsfar_inverse(f->nsfar, z, x, (long)B, theta, logdet, (hipStream_t)stream, err);
-    return rc ? fail(rc, err) : SF_OK;
+    return rc ? sf_fail(rc, err) : SF_OK;
   }
   SfSampleArgsHost a;
   a.x = x; a.z_in = z; a.n_items = (long)B; a.out = theta; a.logdet_out = logdet;
-  SF_HIP(sf_launch_inverse(f->dev(), a, (hipStream_t)stream));
+  SF_TRY_SET(sf_launch_inverse(f->dev(), a, (hipStream_t)stream));
   return SF_OK;
 }
 
 static void nsf_sampler_view(const sf_flow* f, SfDev& m);
 static SfDev sampler_dev(const sf_flow* f, const float* x);
 int sf_flow_inverse_from_noise_sampler(sf_flow* f, const float* z, const float* x, int64_t B, float* theta, void* stream) {
-  if (!f) return fail(SF_ERR_INVALID, "null handle");
+  if (!f) return sf_fail(SF_ERR_INVALID, "null handle");
   if (B == 0) return SF_OK;
-  if (!z || !x || !theta) return fail(SF_ERR_INVALID, "null argument");
-  if (!f->params_set) return fail(SF_ERR_STATE, "sf_flow_set_params has not been called");
+  if (!z || !x || !theta) return sf_fail(SF_ERR_INVALID, "null argument");
+  if (!f->params_set) return sf_fail(SF_ERR_STATE, "sf_flow_set_params has not been called");
   if (f->nsf1 || f->nsfar) {  // one fp32 path
     int rc = sf_flow_inverse_from_noise(f, z, x, B, theta, nullptr, stream);
     return rc ? rc : 1;
@@ -396,14 +387,14 @@ int sf_flow_inverse_from_noise_sampler(sf_flow* f, const float* z, const float* 
     nsf_sampler_view(f, ms);
     SfSampleArgsHost a;
     a.x = x; a.z_in = z; a.n_items = (long)B; a.out = theta;
-    SF_HIP(sf_launch_inverse(ms, a, (hipStream_t)stream));
+    SF_TRY_SET(sf_launch_inverse(ms, a, (hipStream_t)stream));
     return ms.hidden_bf16 == 2 ? SF_OK : 1;
   }
   const SfDev m = f->dev();
   if (!sf_maf16b_available(m)) {  // the sampler of this flow is the 32-row fp32 path
     SfSampleArgsHost a;
     a.x = x; a.z_in = z; a.n_items = (long)B; a.out = theta;
-    SF_HIP(sf_launch_inverse(m, a, (hipStream_t)stream));
+    SF_TRY_SET(sf_launch_inverse(m, a, (hipStream_t)stream));
     return 1;  // (positive: "fp32 path", not an error)
   }
   if (sf_sampler_fp32_for(SF_MAF)) {
@@ -422,7 +413,7 @@ int sf_flow_inverse_from_noise_sampler(sf_flow* f, const float* z, const float* 
     }
     (void)sf_flow_release_context(f);
   }
-  SF_HIP(sf_launch_maf_inv16b_hook(m, z, x, (long)B, theta, (hipStream_t)stream));
+  SF_TRY_SET(sf_launch_maf_inv16b_hook(m, z, x, (long)B, theta, (hipStream_t)stream));
   return sf_sampler_fp32_for(SF_MAF) ? 2 : SF_OK;   // 2: the 16-row sampler's fp32 pass functions
 }
 
@@ -432,7 +423,7 @@ int sf_set_sampler_fp32(int on) {
 }
 
 int sf_flow_train_path(const sf_flow* f, int64_t B, int want_dctx) {
-  if (!f) return fail(SF_ERR_INVALID, "null handle");
+  if (!f) return sf_fail(SF_ERR_INVALID, "null handle");
   if (f->nsf1) return 4;   // MLP engine + scalar spline chain (sf_nsf1.hip)
   if (f->nsfar) return 5;  // thread-per-sample masked hyper-network (sf_nsfar.hip)
   if (B > 0 && sf_trainc_eligible(f->L, want_dctx != 0)) return sf_trainc_groups((long)B, &f->L.trc, f->L.dev.T);
@@ -456,13 +447,13 @@ static size_t ctab_limit_bytes() {
 }
 
 int sf_flow_prepare_context(sf_flow* f, const float* x, int64_t M, void* stream) {
-  if (!f) return fail(SF_ERR_INVALID, "null handle");
+  if (!f) return sf_fail(SF_ERR_INVALID, "null handle");
   f->ctab_x = nullptr;
   f->ctab_M = 0;
   if (M == 0) return SF_OK;
-  if (!x) return fail(SF_ERR_INVALID, "null argument");
-  if (M < 0) return fail(SF_ERR_INVALID, "M < 0");
-  if (!f->params_set) return fail(SF_ERR_STATE, "sf_flow_set_params has not been called");
+  if (!x) return sf_fail(SF_ERR_INVALID, "null argument");
+  if (M < 0) return sf_fail(SF_ERR_INVALID, "M < 0");
+  if (!f->params_set) return sf_fail(SF_ERR_STATE, "sf_flow_set_params has not been called");
   if (f->nsf1 || f->nsfar) return SF_OK;   // (no per-row table: nsf1 evaluates the conditioner once per row anyway, nsf_ar's depends on theta)
   SfDev m = f->dev();
   int R = 0, NV = 0;
@@ -473,22 +464,22 @@ int sf_flow_prepare_context(sf_flow* f, const float* x, int64_t M, void* stream)
     (void)hipFree(f->d_ctab);
     f->d_ctab = nullptr;
     f->ctab_cap = 0;
-    SF_HIP(hipMalloc(&f->d_ctab, need * sizeof(float)));
+    SF_TRY_SET(hipMalloc(&f->d_ctab, need * sizeof(float)));
     f->ctab_cap = need;
   }
   m.ctab_R = R; m.ctab_NV = NV;
   if (f->wp_stale && m.kind == SF_MAF && m.m16_ok && m.packed16 && m.o16_wp >= 0) {   // the fused first layer follows the parameters
-    SF_HIP(sf_launch_maf_fuse16(m, (hipStream_t)stream));
+    SF_TRY_SET(sf_launch_maf_fuse16(m, (hipStream_t)stream));
     f->wp_stale = false;
   }
-  SF_HIP(sf_launch_ctab(m, x, (long)M, f->d_ctab, (hipStream_t)stream));
+  SF_TRY_SET(sf_launch_ctab(m, x, (long)M, f->d_ctab, (hipStream_t)stream));
   f->ctab_x = x;
   f->ctab_M = M;
   return SF_OK;
 }
 
 int sf_flow_release_context(sf_flow* f) {
-  if (!f) return fail(SF_ERR_INVALID, "null handle");
+  if (!f) return sf_fail(SF_ERR_INVALID, "null handle");
   f->ctab_x = nullptr;
   f->ctab_M = 0;
   return SF_OK;
@@ -532,23 +523,23 @@ int sf_flow_sample_round(sf_flow* f, const float* x, int64_t S, const uint32_t* 
                          uint32_t stream_id,
                          const float* lo, const float* hi, float* out, uint32_t* rejected,
                          uint32_t* n_rejected, int32_t* n_drawn, void* stream) {
-  if (!f || !x || !out || !rejected || !n_rejected) return fail(SF_ERR_INVALID, "null argument");
-  if (f->nsf1 || f->nsfar) return fail(SF_ERR_INVALID, "sf_flow_sample_round is not offered for the one-parameter / autoregressive NSF: use sf_flow_sample / sf_flow_sample_slots");
-  if (!f->params_set) return fail(SF_ERR_STATE, "sf_flow_set_params has not been called");
-  if (S < 1 || S > 0x7fffffffll) return fail(SF_ERR_INVALID, "S must be in 1 .. 2^31-1");
-  if ((lo == nullptr) != (hi == nullptr)) return fail(SF_ERR_INVALID, "lo and hi must be given together");
+  if (!f || !x || !out || !rejected || !n_rejected) return sf_fail(SF_ERR_INVALID, "null argument");
+  if (f->nsf1 || f->nsfar) return sf_fail(SF_ERR_INVALID, "sf_flow_sample_round is not offered for the one-parameter / autoregressive NSF: use sf_flow_sample / sf_flow_sample_slots");
+  if (!f->params_set) return sf_fail(SF_ERR_STATE, "sf_flow_set_params has not been called");
+  if (S < 1 || S > 0x7fffffffll) return sf_fail(SF_ERR_INVALID, "S must be in 1 .. 2^31-1");
+  if ((lo == nullptr) != (hi == nullptr)) return sf_fail(SF_ERR_INVALID, "lo and hi must be given together");
   if ((uint64_t)(slot_base + n_slots) > 0xffffffffull)
-    return fail(SF_ERR_INVALID, "slot ids must fit 32 bits: split the catalogue");
+    return sf_fail(SF_ERR_INVALID, "slot ids must fit 32 bits: split the catalogue");
   const int A = attempts_per_slot;
-  if (A < 1 || A > 32 || (A & (A - 1))) return fail(SF_ERR_INVALID, "attempts_per_slot must be 1,2,4,8,16 or 32");
+  if (A < 1 || A > 32 || (A & (A - 1))) return sf_fail(SF_ERR_INVALID, "attempts_per_slot must be 1,2,4,8,16 or 32");
   SfSampleArgsHost a;
   a.x = x; a.S = (long)S; a.slots = slots; a.slot_base = (long)slot_base; a.n_items = (long)n_slots * A;
   a.attempts_per_slot = A; a.attempt = attempt; seed_keys(seed, stream_id, a.k0, a.k1);
   a.rng_slot_offset = (unsigned long long)f->sample_row_offset * (unsigned long long)S;
   a.lo = lo; a.hi = hi; a.out = out; a.rejected = rejected; a.n_rejected = n_rejected; a.n_drawn = n_drawn;
   if (f->ctab_x == x && (uint64_t)(slot_base + n_slots) > (uint64_t)f->ctab_M * (uint64_t)S && slots == nullptr)
-    return fail(SF_ERR_INVALID, "slots reach past the rows given to sf_flow_prepare_context");
-  SF_HIP(sf_launch_inverse(sampler_dev(f, x), a, (hipStream_t)stream));
+    return sf_fail(SF_ERR_INVALID, "slots reach past the rows given to sf_flow_prepare_context");
+  SF_TRY_SET(sf_launch_inverse(sampler_dev(f, x), a, (hipStream_t)stream));
   return SF_OK;
 }
 
@@ -562,8 +553,8 @@ int sf_flow_sample_round(sf_flow* f, const float* x, int64_t S, const uint32_t* 
 // 1 / (window x open slots) and its open slots become NaN rows, which is what the reference's timeout / error path
 // produces (ref: sbi_runner.py:6443-6460); [UPSTREAM] accept_reject_sample itself would loop forever on such a galaxy.
 static int ensure_queue(sf_flow* f, int64_t n_slots, int64_t M) {
-  if (!f->d_queue) SF_HIP(hipMalloc(&f->d_queue, sizeof(SfQueue)));
-  if (!f->h_queue) SF_HIP(hipHostMalloc((void**)&f->h_queue, sizeof(SfQueue), hipHostMallocDefault));
+  if (!f->d_queue) SF_TRY_SET(hipMalloc(&f->d_queue, sizeof(SfQueue)));
+  if (!f->h_queue) SF_TRY_SET(hipHostMalloc((void**)&f->h_queue, sizeof(SfQueue), hipHostMallocDefault));
   // ring positions are tickets of idle workgroups: at most (resident workgroups x items per iteration) are in flight at a
   // time (<= 2048 x 256), whatever the size of the catalogue -- 2^20 entries (8 MiB) never alias
   uint64_t cap = 1u << 16;
@@ -571,22 +562,22 @@ static int ensure_queue(sf_flow* f, int64_t n_slots, int64_t M) {
   if (f->ring_cap < cap) {
     (void)hipFree(f->d_ring);
     f->d_ring = nullptr; f->ring_cap = 0;
-    SF_HIP(hipMalloc(&f->d_ring, cap * sizeof(unsigned long long)));
-    SF_HIP(hipMemset(f->d_ring, 0, cap * sizeof(unsigned long long)));  // consumers clear what they take: stays zero
+    SF_TRY_SET(hipMalloc(&f->d_ring, cap * sizeof(unsigned long long)));
+    SF_TRY_SET(hipMemset(f->d_ring, 0, cap * sizeof(unsigned long long)));  // consumers clear what they take: stays zero
     f->ring_cap = cap;
     f->ring_dirty = false;
   }
   if (f->rej_cap < (size_t)n_slots) {
     (void)hipFree(f->d_rej[0]); (void)hipFree(f->d_rej[1]);
     f->d_rej[0] = f->d_rej[1] = nullptr; f->rej_cap = 0;
-    SF_HIP(hipMalloc(&f->d_rej[0], (size_t)n_slots * sizeof(uint32_t)));
-    SF_HIP(hipMalloc(&f->d_rej[1], (size_t)n_slots * sizeof(uint32_t)));
+    SF_TRY_SET(hipMalloc(&f->d_rej[0], (size_t)n_slots * sizeof(uint32_t)));
+    SF_TRY_SET(hipMalloc(&f->d_rej[1], (size_t)n_slots * sizeof(uint32_t)));
     f->rej_cap = (size_t)n_slots;
   }
   if (f->galacc_cap < (size_t)M) {
     (void)hipFree(f->d_galacc);
     f->d_galacc = nullptr; f->galacc_cap = 0;
-    SF_HIP(hipMalloc(&f->d_galacc, (size_t)M * sizeof(int32_t)));
+    SF_TRY_SET(hipMalloc(&f->d_galacc, (size_t)M * sizeof(int32_t)));
     f->galacc_cap = (size_t)M;
   }
   return SF_OK;
@@ -598,7 +589,7 @@ static int sample_persistent(sf_flow* f, const float* x, int64_t M, int64_t S, c
                              int32_t* n_drawn, int64_t* n_unfilled, hipStream_t st) {
   if (n_unfilled) *n_unfilled = 0;
   if (n_slots == 0) return SF_OK;
-  if ((uint64_t)(M * S) > 0xfff00000ull) return fail(SF_ERR_INVALID, "M*S must stay below 2^32 - 2^20: split the catalogue");
+  if ((uint64_t)(M * S) > 0xfff00000ull) return sf_fail(SF_ERR_INVALID, "M*S must stay below 2^32 - 2^20: split the catalogue");
   int rc = ensure_queue(f, n_slots, M);
   if (rc) return rc;
   const bool capped = max_attempts > 0;
@@ -660,13 +651,13 @@ static int sample_persistent(sf_flow* f, const float* x, int64_t M, int64_t S, c
   for (;;) {
     // The retry ring stays all-zero only while every launch ends cleanly (consumers clear what they take).  A launch that
     // ended on a queue error, or never completed, may have left donated entries behind: clear the ring before it is reused.
-    if (f->ring_dirty) SF_HIP(hipMemsetAsync(f->d_ring, 0, f->ring_cap * sizeof(unsigned long long), st));
+    if (f->ring_dirty) SF_TRY_SET(hipMemsetAsync(f->d_ring, 0, f->ring_cap * sizeof(unsigned long long), st));
     f->ring_dirty = true;
-    SF_HIP(hipMemsetAsync(f->d_queue, 0, sizeof(SfQueue), st));
+    SF_TRY_SET(hipMemsetAsync(f->d_queue, 0, sizeof(SfQueue), st));
 #ifdef SF_Q_STATS
-    SF_HIP(hipMemsetAsync(&f->d_queue->stats[10], 0xff, sizeof(unsigned long long), st));  // atomicMin target
+    SF_TRY_SET(hipMemsetAsync(&f->d_queue->stats[10], 0xff, sizeof(unsigned long long), st));  // atomicMin target
 #endif
-    if (progress_rule && stage == 0) SF_HIP(hipMemsetAsync(f->d_galacc, 0, (size_t)M * sizeof(int32_t), st));  // (later: carried over)
+    if (progress_rule && stage == 0) SF_TRY_SET(hipMemsetAsync(f->d_galacc, 0, (size_t)M * sizeof(int32_t), st));  // (later: carried over)
     a.slots = cur; a.slot_base = 0; a.n_items = (long)pending; a.n_total = (uint32_t)pending;
     {
       static int env_il = -1;  // developer knob: SF_INTERLEAVE=<galaxies per block>, 0 = plain slot order (A-B runs)
@@ -694,25 +685,25 @@ static int sample_persistent(sf_flow* f, const float* x, int64_t M, int64_t S, c
     static uint32_t* d_qtrace = nullptr;
     const size_t qtrace_bytes = (size_t)2048 * 256 * 4 * sizeof(uint32_t);
     if (std::getenv("SF_Q_TRACE")) {
-      if (!d_qtrace) SF_HIP(hipMalloc(&d_qtrace, qtrace_bytes));
-      SF_HIP(hipMemsetAsync(d_qtrace, 0, qtrace_bytes, st));
+      if (!d_qtrace) SF_TRY_SET(hipMalloc(&d_qtrace, qtrace_bytes));
+      SF_TRY_SET(hipMemsetAsync(d_qtrace, 0, qtrace_bytes, st));
       a.qtrace = d_qtrace;
     }
 #endif
-    if (stage == 0) SF_HIP(hipEventRecord(f->ev_dense[0], st));  // (the reported launch time is the first window's)
+    if (stage == 0) SF_TRY_SET(hipEventRecord(f->ev_dense[0], st));  // (the reported launch time is the first window's)
     hipError_t e = sf_launch_inverse(m, a, st);
     if (e != hipSuccess) { f->ctab_x = nullptr; return hip_fail(e, "persistent sampler launch"); }
-    if (stage == 0) SF_HIP(hipEventRecord(f->ev_dense[1], st));
+    if (stage == 0) SF_TRY_SET(hipEventRecord(f->ev_dense[1], st));
     if (limit >= 1024u && rule_due(limit)) {  // drop the open slots of galaxies that made no progress (NaN rows), in place
-      SF_HIP(sf_launch_filter_survivors(f->d_rej[buf], &f->d_queue->n_surv, (long)S, f->d_galacc, out, f->L.dev.D, st, a.out_f64));
-      SF_HIP(hipMemsetAsync(f->d_galacc, 0, (size_t)M * sizeof(int32_t), st));
+      SF_TRY_SET(sf_launch_filter_survivors(f->d_rej[buf], &f->d_queue->n_surv, (long)S, f->d_galacc, out, f->L.dev.D, st, a.out_f64));
+      SF_TRY_SET(hipMemsetAsync(f->d_galacc, 0, (size_t)M * sizeof(int32_t), st));
       acc_from = limit;
     }
-    SF_HIP(hipMemcpyAsync(f->h_queue, f->d_queue, sizeof(SfQueue), hipMemcpyDeviceToHost, st));  // pinned
-    SF_HIP(hipStreamSynchronize(st));
+    SF_TRY_SET(hipMemcpyAsync(f->h_queue, f->d_queue, sizeof(SfQueue), hipMemcpyDeviceToHost, st));  // pinned
+    SF_TRY_SET(hipStreamSynchronize(st));
     if (f->h_queue->error) {
       f->ctab_x = nullptr;
-      return fail(SF_ERR_STATE, "persistent sampler: work queue inconsistent (code " + std::to_string(f->h_queue->error) +
+      return sf_fail(SF_ERR_STATE, "persistent sampler: work queue inconsistent (code " + std::to_string(f->h_queue->error) +
                                     ": 1 = a device-side wait exceeded its bound, 2 = foreign ring entry, 3 = survivor "
                                     "list overflow, 4 = listed slot outside M*S, 5 = claimed entry never arrived, 6/7 = "
                                     "claim contention); head " + std::to_string(f->h_queue->head) + " reserve " +
@@ -726,7 +717,7 @@ static int sample_persistent(sf_flow* f, const float* x, int64_t M, int64_t S, c
 #ifdef SF_Q_STATS
     if (a.qtrace) {  // the last launch's trace stays in the file
       std::vector<uint32_t> h(qtrace_bytes / sizeof(uint32_t));
-      SF_HIP(hipMemcpy(h.data(), a.qtrace, qtrace_bytes, hipMemcpyDeviceToHost));
+      SF_TRY_SET(hipMemcpy(h.data(), a.qtrace, qtrace_bytes, hipMemcpyDeviceToHost));
       if (h[1] != 0u) {  // (kernels without the trace code leave the buffer empty: keep the previous file)
         if (FILE* fp = std::fopen(std::getenv("SF_Q_TRACE"), "wb")) { std::fwrite(h.data(), 1, qtrace_bytes, fp); std::fclose(fp); }
       }
@@ -764,7 +755,7 @@ static int sample_persistent(sf_flow* f, const float* x, int64_t M, int64_t S, c
     if (f->best_cap < (size_t)pending) {
       (void)hipFree(f->d_best);
       f->d_best = nullptr; f->best_cap = 0;
-      SF_HIP(hipMalloc(&f->d_best, (size_t)pending * sizeof(uint32_t)));
+      SF_TRY_SET(hipMalloc(&f->d_best, (size_t)pending * sizeof(uint32_t)));
       f->best_cap = (size_t)pending;
     }
     SfSampleArgsHost p = a;  // plain launches
@@ -779,14 +770,14 @@ static int sample_persistent(sf_flow* f, const float* x, int64_t M, int64_t S, c
       const uint32_t a_max = attempt < 64u ? 64u : attempt;
       while ((uint64_t)(2u * A) * (uint64_t)pending <= (1ull << 22) && 2u * A <= 65536u && 2u * A <= a_max) A *= 2;
       while (A > 1 && (uint64_t)attempt + A > (uint64_t)window_end) A /= 2;  // windows (and the caller's ceiling) are exact
-      SF_HIP(hipMemsetAsync(f->d_best, 0xff, (size_t)pending * sizeof(uint32_t), st));
+      SF_TRY_SET(hipMemsetAsync(f->d_best, 0xff, (size_t)pending * sizeof(uint32_t), st));
       p.slots = cur; p.slot_base = 0; p.n_items = (long)pending * A; p.attempts_per_slot = (int)A; p.attempt = attempt;
       p.best = f->d_best; p.att_list = nullptr; p.rejected = nullptr; p.n_rejected = nullptr;
       hipError_t e = sf_launch_inverse(m, p, st);
       if (e != hipSuccess) { f->ctab_x = nullptr; return hip_fail(e, "find launch"); }
-      SF_HIP(sf_launch_account_window(cur, f->d_best, (long)pending, (long)S, attempt, A, n_drawn,
+      SF_TRY_SET(sf_launch_account_window(cur, f->d_best, (long)pending, (long)S, attempt, A, n_drawn,
                                       progress_rule ? f->d_galacc : nullptr, st));
-      SF_HIP(hipMemsetAsync(&f->d_queue->n_surv, 0, 2 * sizeof(unsigned int), st));  // n_surv, dropped
+      SF_TRY_SET(hipMemsetAsync(&f->d_queue->n_surv, 0, 2 * sizeof(unsigned int), st));  // n_surv, dropped
       p.n_items = (long)pending; p.attempts_per_slot = 1; p.best = nullptr; p.att_list = f->d_best;
       p.rejected = f->d_rej[buf]; p.n_rejected = &f->d_queue->n_surv;
       e = sf_launch_inverse(m, p, st);
@@ -796,12 +787,12 @@ static int sample_persistent(sf_flow* f, const float* x, int64_t M, int64_t S, c
       const bool window_done = attempt >= window_end || attempt >= ceiling;
       const bool look = window_done && rule_due(attempt);
       if (look) {
-        SF_HIP(sf_launch_filter_survivors(f->d_rej[buf], &f->d_queue->n_surv, (long)S, f->d_galacc, out, f->L.dev.D, st, a.out_f64));
-        SF_HIP(hipMemsetAsync(f->d_galacc, 0, (size_t)M * sizeof(int32_t), st));
+        SF_TRY_SET(sf_launch_filter_survivors(f->d_rej[buf], &f->d_queue->n_surv, (long)S, f->d_galacc, out, f->L.dev.D, st, a.out_f64));
+        SF_TRY_SET(hipMemsetAsync(f->d_galacc, 0, (size_t)M * sizeof(int32_t), st));
         acc_from = attempt;
       }
-      SF_HIP(hipMemcpyAsync(f->h_queue, f->d_queue, sizeof(SfQueue), hipMemcpyDeviceToHost, st));
-      SF_HIP(hipStreamSynchronize(st));
+      SF_TRY_SET(hipMemcpyAsync(f->h_queue, f->d_queue, sizeof(SfQueue), hipMemcpyDeviceToHost, st));
+      SF_TRY_SET(hipStreamSynchronize(st));
       if (look) dropped += (int64_t)f->h_queue->dropped;
       if (window_done) window_end = (window_end > ceiling / 16u) ? ceiling : window_end * 16u;
       pending = (int64_t)f->h_queue->n_surv;
@@ -816,7 +807,7 @@ static int sample_persistent(sf_flow* f, const float* x, int64_t M, int64_t S, c
     f->last_stats[0] = ms; f->last_stats[1] = (float)stage; f->last_stats[2] = rej0; f->last_stats[3] = (float)evals;
   }
   f->ctab_x = nullptr;
-  if (pending > 0) SF_HIP(sf_launch_fill_nan_rows(out, cur, (long)pending, f->L.dev.D, st, a.out_f64));
+  if (pending > 0) SF_TRY_SET(sf_launch_fill_nan_rows(out, cur, (long)pending, f->L.dev.D, st, a.out_f64));
   if (n_unfilled) *n_unfilled = pending + dropped;
   return SF_OK;
 }
@@ -824,54 +815,54 @@ static int sample_persistent(sf_flow* f, const float* x, int64_t M, int64_t S, c
 int sf_flow_sample(sf_flow* f, const float* x, int64_t M, int64_t S, const float* lo, const float* hi,
                    uint64_t seed, int32_t max_attempts, float* out, int32_t* n_drawn, int64_t* n_unfilled,
                    void* stream) {
-  if (!f) return fail(SF_ERR_INVALID, "null handle");
+  if (!f) return sf_fail(SF_ERR_INVALID, "null handle");
   if (n_unfilled) *n_unfilled = 0;
   if (M == 0) return SF_OK;
-  if (!x || !out) return fail(SF_ERR_INVALID, "null argument");
-  if (!f->params_set) return fail(SF_ERR_STATE, "sf_flow_set_params has not been called");
-  if (M < 0 || S < 1) return fail(SF_ERR_INVALID, "bad M or S");
-  if ((lo == nullptr) != (hi == nullptr)) return fail(SF_ERR_INVALID, "lo and hi must be given together");
+  if (!x || !out) return sf_fail(SF_ERR_INVALID, "null argument");
+  if (!f->params_set) return sf_fail(SF_ERR_STATE, "sf_flow_set_params has not been called");
+  if (M < 0 || S < 1) return sf_fail(SF_ERR_INVALID, "bad M or S");
+  if ((lo == nullptr) != (hi == nullptr)) return sf_fail(SF_ERR_INVALID, "lo and hi must be given together");
   hipStream_t st = (hipStream_t)stream;
   if (f->nsf1) {
-    if (n_drawn) SF_HIP(sf_launch_fill_i32(n_drawn, (long)M, 0, st));
+    if (n_drawn) SF_TRY_SET(sf_launch_fill_i32(n_drawn, (long)M, 0, st));
     uint32_t k0, k1;
     seed_keys(seed, 0u, k0, k1);
     std::string err;
     int rc = sf_nsf1_sample(f->nsf1, f->d_flat, x, (long)M, (long)S, nullptr, (long)(M * S), lo, hi, k0, k1,
                             (unsigned long long)f->sample_row_offset * (unsigned long long)S, max_attempts, out, n_drawn, n_unfilled, st, err);
-    return rc ? fail(rc, err) : SF_OK;
+    return rc ? sf_fail(rc, err) : SF_OK;
   }
   if (f->nsfar) {
-    if (n_drawn) SF_HIP(sf_launch_fill_i32(n_drawn, (long)M, 0, st));
+    if (n_drawn) SF_TRY_SET(sf_launch_fill_i32(n_drawn, (long)M, 0, st));
     uint32_t k0, k1;
     seed_keys(seed, 0u, k0, k1);
     std::string err;
-    if (!f->ev_dense[0]) { SF_HIP(hipEventCreate(&f->ev_dense[0])); SF_HIP(hipEventCreate(&f->ev_dense[1])); }
+    if (!f->ev_dense[0]) { SF_TRY_SET(hipEventCreate(&f->ev_dense[0])); SF_TRY_SET(hipEventCreate(&f->ev_dense[1])); }
     int64_t unf = 0;
     int rc = sf_nsfar_sample(f->nsfar, x, (long)M, (long)S, nullptr, (long)(M * S), lo, hi, k0, k1,
                              (unsigned long long)f->sample_row_offset * (unsigned long long)S, max_attempts, out, n_drawn, nullptr, &unf, st, err,
                              f->ev_dense[0], f->ev_dense[1]);
-    if (rc) return fail(rc, err);
+    if (rc) return sf_fail(rc, err);
     if (n_unfilled) *n_unfilled = unf;
     float ms = 0.f;   // (the counters' read-back has synchronised the stream)
-    SF_HIP(hipEventElapsedTime(&ms, f->ev_dense[0], f->ev_dense[1]));
+    SF_TRY_SET(hipEventElapsedTime(&ms, f->ev_dense[0], f->ev_dense[1]));
     f->last_stats[0] = ms; f->last_stats[1] = 1.f; f->last_stats[2] = (float)f->nsfar->last_rej0; f->last_stats[3] = (float)f->nsfar->last_evals;
     return SF_OK;
   }
-  if (n_drawn) SF_HIP(sf_launch_fill_i32(n_drawn, (long)M, (int32_t)S, st));
+  if (n_drawn) SF_TRY_SET(sf_launch_fill_i32(n_drawn, (long)M, (int32_t)S, st));
   return sample_persistent(f, x, M, S, nullptr, M * S, lo, hi, seed, max_attempts, out, n_drawn, n_unfilled, st);
 }
 
 int sf_flow_sample_slots(sf_flow* f, const float* x, int64_t M, int64_t S, const uint32_t* slots, int64_t n_slots,
                          const float* lo, const float* hi, uint64_t seed, int32_t max_attempts, float* out,
                          int64_t* n_unfilled, void* stream) {
-  if (!f) return fail(SF_ERR_INVALID, "null handle");
+  if (!f) return sf_fail(SF_ERR_INVALID, "null handle");
   if (n_unfilled) *n_unfilled = 0;
   if (n_slots == 0) return SF_OK;
-  if (!x || !out || !slots) return fail(SF_ERR_INVALID, "null argument");
-  if (!f->params_set) return fail(SF_ERR_STATE, "sf_flow_set_params has not been called");
-  if (M < 1 || S < 1 || n_slots < 0 || n_slots > M * S) return fail(SF_ERR_INVALID, "bad M, S or n_slots");
-  if ((lo == nullptr) != (hi == nullptr)) return fail(SF_ERR_INVALID, "lo and hi must be given together");
+  if (!x || !out || !slots) return sf_fail(SF_ERR_INVALID, "null argument");
+  if (!f->params_set) return sf_fail(SF_ERR_STATE, "sf_flow_set_params has not been called");
+  if (M < 1 || S < 1 || n_slots < 0 || n_slots > M * S) return sf_fail(SF_ERR_INVALID, "bad M, S or n_slots");
+  if ((lo == nullptr) != (hi == nullptr)) return sf_fail(SF_ERR_INVALID, "lo and hi must be given together");
   if (f->nsf1) {
     uint32_t k0, k1;
     seed_keys(seed, 0u, k0, k1);
@@ -879,7 +870,7 @@ int sf_flow_sample_slots(sf_flow* f, const float* x, int64_t M, int64_t S, const
     int rc = sf_nsf1_sample(f->nsf1, f->d_flat, x, (long)M, (long)S, slots, (long)n_slots, lo, hi, k0, k1,
                             (unsigned long long)f->sample_row_offset * (unsigned long long)S, max_attempts, out, nullptr, n_unfilled,
                             (hipStream_t)stream, err);
-    return rc ? fail(rc, err) : SF_OK;
+    return rc ? sf_fail(rc, err) : SF_OK;
   }
   if (f->nsfar) {
     uint32_t k0, k1;
@@ -888,33 +879,33 @@ int sf_flow_sample_slots(sf_flow* f, const float* x, int64_t M, int64_t S, const
     int rc = sf_nsfar_sample(f->nsfar, x, (long)M, (long)S, slots, (long)n_slots, lo, hi, k0, k1,
                              (unsigned long long)f->sample_row_offset * (unsigned long long)S, max_attempts, out, nullptr, nullptr, n_unfilled,
                              (hipStream_t)stream, err);
-    return rc ? fail(rc, err) : SF_OK;
+    return rc ? sf_fail(rc, err) : SF_OK;
   }
   return sample_persistent(f, x, M, S, slots, n_slots, lo, hi, seed, max_attempts, out, nullptr, n_unfilled,
                            (hipStream_t)stream);
 }
 
 int sf_flow_sample_stats(const sf_flow* f, float* stats4) {
-  if (!f || !stats4) return fail(SF_ERR_INVALID, "null argument");
+  if (!f || !stats4) return sf_fail(SF_ERR_INVALID, "null argument");
   for (int i = 0; i < 4; ++i) stats4[i] = f->last_stats[i];
   return SF_OK;
 }
 
 int sf_flow_acceptance(sf_flow* f, const float* x, int64_t M, int64_t n, const float* lo, const float* hi,
                        uint64_t seed, int32_t* count, void* stream) {
-  if (!f || !x || !count || !lo || !hi) return fail(SF_ERR_INVALID, "null argument");
-  if (!f->params_set) return fail(SF_ERR_STATE, "sf_flow_set_params has not been called");
-  if (M < 0 || n < 1 || n > 0x7fffffffll) return fail(SF_ERR_INVALID, "bad M or n");
-  if ((uint64_t)(M * n) > 0xffffffffull) return fail(SF_ERR_INVALID, "M*n must fit 32 bits");
+  if (!f || !x || !count || !lo || !hi) return sf_fail(SF_ERR_INVALID, "null argument");
+  if (!f->params_set) return sf_fail(SF_ERR_STATE, "sf_flow_set_params has not been called");
+  if (M < 0 || n < 1 || n > 0x7fffffffll) return sf_fail(SF_ERR_INVALID, "bad M or n");
+  if ((uint64_t)(M * n) > 0xffffffffull) return sf_fail(SF_ERR_INVALID, "M*n must fit 32 bits");
   hipStream_t st = (hipStream_t)stream;
-  SF_HIP(sf_launch_fill_i32(count, (long)M, 0, st));
+  SF_TRY_SET(sf_launch_fill_i32(count, (long)M, 0, st));
   if (f->nsf1) {
     uint32_t k0, k1;
     seed_keys(seed, 1u, k0, k1);
     std::string err;
     int rc = sf_nsf1_acceptance(f->nsf1, f->d_flat, x, (long)M, (long)n, lo, hi, k0, k1,
                                 (unsigned long long)f->sample_row_offset * (unsigned long long)n, count, st, err);
-    return rc ? fail(rc, err) : SF_OK;
+    return rc ? sf_fail(rc, err) : SF_OK;
   }
   if (f->nsfar) {
     uint32_t k0, k1;
@@ -922,7 +913,7 @@ int sf_flow_acceptance(sf_flow* f, const float* x, int64_t M, int64_t n, const f
     std::string err;
     int rc = sf_nsfar_sample(f->nsfar, x, (long)M, (long)n, nullptr, (long)(M * n), lo, hi, k0, k1,
                              (unsigned long long)f->sample_row_offset * (unsigned long long)n, 1, nullptr, nullptr, count, nullptr, st, err);
-    return rc ? fail(rc, err) : SF_OK;
+    return rc ? sf_fail(rc, err) : SF_OK;
   }
   SfSampleArgsHost a;
   a.x = x; a.S = (long)n; a.n_items = (long)(M * n); seed_keys(seed, 1u, a.k0, a.k1);
@@ -934,25 +925,25 @@ int sf_flow_acceptance(sf_flow* f, const float* x, int64_t M, int64_t n, const f
   }
   const SfDev m = sampler_dev(f, x);
   f->ctab_x = nullptr;
-  SF_HIP(sf_launch_inverse(m, a, st));
+  SF_TRY_SET(sf_launch_inverse(m, a, st));
   return SF_OK;
 }
 
 int sf_copy_to_host_f64(const float* dev_src, double* host_dst, int64_t n, void* stream) {
   if (n == 0) return SF_OK;
-  if (!dev_src || !host_dst || n < 0) return fail(SF_ERR_INVALID, "null argument or n < 0");
+  if (!dev_src || !host_dst || n < 0) return sf_fail(SF_ERR_INVALID, "null argument or n < 0");
   std::string err;
   int rc = sf_hostio_copy_f64(dev_src, host_dst, n, (hipStream_t)stream, err);
-  return rc ? fail(rc, err) : SF_OK;
+  return rc ? sf_fail(rc, err) : SF_OK;
 }
 
 // ---- training ------------------------------------------------------------------------------
 int sf_flow_loss_grad_weighted(sf_flow* f, const float* flat, const float* theta, const float* x, int64_t B,
                                float grad_scale, const float* weights, float* loss, float* grad,
                                float* dctx, void* stream) {
-  if (!f || !flat || !grad) return fail(SF_ERR_INVALID, "null argument");
-  if (B > 0 && (!theta || !x)) return fail(SF_ERR_INVALID, "null argument");
-  if (B < 0) return fail(SF_ERR_INVALID, "B < 0");
+  if (!f || !flat || !grad) return sf_fail(SF_ERR_INVALID, "null argument");
+  if (B > 0 && (!theta || !x)) return sf_fail(SF_ERR_INVALID, "null argument");
+  if (B < 0) return sf_fail(SF_ERR_INVALID, "B < 0");
   int rc = ensure_device(f);
   if (rc) return rc;
   std::string err;
@@ -960,7 +951,7 @@ int sf_flow_loss_grad_weighted(sf_flow* f, const float* flat, const float* theta
                           (hipStream_t)stream, err);
   if (rc) {
     if (rc == SF_ERR_HIP) f->flat_valid = false;  // failed part-way: the forward image may already hold the caller's vector
-    return fail(rc, err);
+    return sf_fail(rc, err);
   }
   f->params_set = true;  // the forward image now holds `flat`
   f->flat_valid = false; // ... but the handle's own copy of the logical vector does not
@@ -971,9 +962,9 @@ int sf_flow_loss_grad_weighted(sf_flow* f, const float* flat, const float* theta
 int sf_flow_loss_grad_rows(sf_flow* f, const float* flat, const float* theta, const float* x, const int64_t* rows,
                            int64_t B, float grad_scale, const float* weights, float* loss, double* loss_sum,
                            float* grad, float* dctx, void* stream) {
-  if (!f || !flat || !grad) return fail(SF_ERR_INVALID, "null argument");
-  if (B > 0 && (!theta || !x || !rows)) return fail(SF_ERR_INVALID, "null argument");
-  if (B < 0) return fail(SF_ERR_INVALID, "B < 0");
+  if (!f || !flat || !grad) return sf_fail(SF_ERR_INVALID, "null argument");
+  if (B > 0 && (!theta || !x || !rows)) return sf_fail(SF_ERR_INVALID, "null argument");
+  if (B < 0) return sf_fail(SF_ERR_INVALID, "B < 0");
   int rc = ensure_device(f);
   if (rc) return rc;
   std::string err;
@@ -981,7 +972,7 @@ int sf_flow_loss_grad_rows(sf_flow* f, const float* flat, const float* theta, co
                           loss_sum, grad, dctx, (hipStream_t)stream, err);
   if (rc) {
     if (rc == SF_ERR_HIP) f->flat_valid = false;  // (as above)
-    return fail(rc, err);
+    return sf_fail(rc, err);
   }
   f->params_set = true;
   f->flat_valid = false;
@@ -1002,8 +993,8 @@ int sf_flow_train_epoch_dp(sf_flow* f, float* flat, const float* theta, const fl
                            const sf_adam_desc* d, int64_t step0, float max_norm, float* scratch, float* grad,
                            double* loss_sum, sf_comm* comm, void* stream) {
   if (!f || !flat || !theta || !x || !order || !exp_avg || !exp_avg_sq || !d || !scratch || !grad)
-    return fail(SF_ERR_INVALID, "null argument");
-  if (n_batches < 0 || batch < 1 || step0 < 0) return fail(SF_ERR_INVALID, "bad n_batches, batch or step0");
+    return sf_fail(SF_ERR_INVALID, "null argument");
+  if (n_batches < 0 || batch < 1 || step0 < 0) return sf_fail(SF_ERR_INVALID, "bad n_batches, batch or step0");
   // (the gather of the step leaves |grad|^2 in per-block shares for the clip: the optimiser kernel then skips its pass over the
   //  whole gradient -- one L2 round trip less in a step that is a chain of them)
   //  (data parallel: the norm that clips is the REDUCED gradient's, so the optimiser kernel takes its own pass over it)
@@ -1049,39 +1040,39 @@ int sf_flow_train_epoch_dp(sf_flow* f, float* flat, const float* theta, const fl
 }
 
 int sf_flow_set_sample_row_offset(sf_flow* f, int64_t row_offset) {
-  if (!f) return fail(SF_ERR_INVALID, "null handle");
-  if (row_offset < 0) return fail(SF_ERR_INVALID, "row_offset < 0");
+  if (!f) return sf_fail(SF_ERR_INVALID, "null handle");
+  if (row_offset < 0) return sf_fail(SF_ERR_INVALID, "row_offset < 0");
   f->sample_row_offset = (long long)row_offset;
   return SF_OK;
 }
 
 int sf_flow_set_sample_output_f64(sf_flow* f, int on) {
-  if (!f) return fail(SF_ERR_INVALID, "null handle");
+  if (!f) return sf_fail(SF_ERR_INVALID, "null handle");
   if (on && (f->nsf1 || f->nsfar))
-    return fail(SF_ERR_INVALID, "float64 sampler output is not offered for the one-parameter / autoregressive NSF: sample fp32 and "
+    return sf_fail(SF_ERR_INVALID, "float64 sampler output is not offered for the one-parameter / autoregressive NSF: sample fp32 and "
                                 "use sf_copy_to_host_f64");
   f->sample_out_f64 = on != 0;
   return SF_OK;
 }
 
 int sf_flow_set_sample_time_limit(sf_flow* f, double seconds) {
-  if (!f) return fail(SF_ERR_INVALID, "null handle");
+  if (!f) return sf_fail(SF_ERR_INVALID, "null handle");
   f->sample_time_limit_s = seconds > 0.0 ? seconds : 0.0;
   return SF_OK;
 }
 
 int sf_flow_set_profiling(sf_flow* f, int on) {
-  if (!f) return fail(SF_ERR_INVALID, "null handle");
+  if (!f) return sf_fail(SF_ERR_INVALID, "null handle");
   f->profiling = on != 0;
   f->ev_train_valid = false;
   return SF_OK;
 }
 
 int sf_flow_train_stats(sf_flow* f, float* kernel_ms) {
-  if (!f || !kernel_ms) return fail(SF_ERR_INVALID, "null argument");
-  if (!f->profiling || !f->ev_train_valid) return fail(SF_ERR_STATE, "no profiled training call yet (sf_flow_set_profiling)");
-  SF_HIP(hipEventSynchronize(f->ev_train[1]));
-  SF_HIP(hipEventElapsedTime(kernel_ms, f->ev_train[0], f->ev_train[1]));
+  if (!f || !kernel_ms) return sf_fail(SF_ERR_INVALID, "null argument");
+  if (!f->profiling || !f->ev_train_valid) return sf_fail(SF_ERR_STATE, "no profiled training call yet (sf_flow_set_profiling)");
+  SF_TRY_SET(hipEventSynchronize(f->ev_train[1]));
+  SF_TRY_SET(hipEventElapsedTime(kernel_ms, f->ev_train[0], f->ev_train[1]));
   return SF_OK;
 }
 
@@ -1092,6 +1083,10 @@ int sf_flow_loss_grad(sf_flow* f, const float* flat, const float* theta, const f
 
 }  // extern "C"
 void sf_set_error(const std::string& msg) { g_err = msg; }
+int sf_fail(int code, const std::string& msg) {
+  g_err = msg;
+  return code;
+}
 extern "C" {
 
 struct sf_opt {
@@ -1105,9 +1100,9 @@ struct sf_opt {
 
 void sf_opt_destroy(sf_opt* o);
 int sf_opt_create(int64_t n, const sf_adam_desc* d, sf_opt** out) {
-  if (n < 1 || !d || !out) return fail(SF_ERR_INVALID, "bad argument");
+  if (n < 1 || !d || !out) return sf_fail(SF_ERR_INVALID, "bad argument");
   int nd = 0;
-  if (hipGetDeviceCount(&nd) != hipSuccess || nd == 0) return fail(SF_ERR_NO_DEVICE, "no HIP device visible");
+  if (hipGetDeviceCount(&nd) != hipSuccess || nd == 0) return sf_fail(SF_ERR_NO_DEVICE, "no HIP device visible");
   sf_opt* o = new sf_opt();
   o->n = n;
   o->d = *d;
@@ -1129,7 +1124,7 @@ void sf_opt_destroy(sf_opt* o) {
   delete o;
 }
 int sf_adam_step(sf_opt* o, float* params, const float* grad, float max_norm, float* grad_norm_out, void* stream) {
-  if (!o || !params || !grad) return fail(SF_ERR_INVALID, "null argument");
+  if (!o || !params || !grad) return sf_fail(SF_ERR_INVALID, "null argument");
   o->step += 1;
   const double bc1 = 1.0 - std::pow((double)o->d.beta1, (double)o->step);
   const double bc2 = 1.0 - std::pow((double)o->d.beta2, (double)o->step);
@@ -1140,8 +1135,8 @@ int sf_adam_step(sf_opt* o, float* params, const float* grad, float max_norm, fl
 }
 int sf_adam_apply(float* params, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                   const sf_adam_desc* d, int64_t step, float max_norm, float* scratch, void* stream) {
-  if (!params || !grad || !exp_avg || !exp_avg_sq || !d || !scratch) return fail(SF_ERR_INVALID, "null argument");
-  if (n < 1 || step < 1) return fail(SF_ERR_INVALID, "bad n or step");
+  if (!params || !grad || !exp_avg || !exp_avg_sq || !d || !scratch) return sf_fail(SF_ERR_INVALID, "null argument");
+  if (n < 1 || step < 1) return sf_fail(SF_ERR_INVALID, "bad n or step");
   const double bc1 = 1.0 - std::pow((double)d->beta1, (double)step);
   const double bc2 = 1.0 - std::pow((double)d->beta2, (double)step);
   hipError_t e = sf_launch_adam(params, grad, exp_avg, exp_avg_sq, scratch, (long)n, *d, (float)bc1, (float)bc2,
@@ -1150,7 +1145,7 @@ int sf_adam_apply(float* params, const float* grad, float* exp_avg, float* exp_a
   return SF_OK;
 }
 int sf_opt_state(sf_opt* o, float** exp_avg, float** exp_avg_sq, int64_t** step_host) {
-  if (!o) return fail(SF_ERR_INVALID, "null argument");
+  if (!o) return sf_fail(SF_ERR_INVALID, "null argument");
   if (exp_avg) *exp_avg = o->m;
   if (exp_avg_sq) *exp_avg_sq = o->v;
   if (step_host) *step_host = &o->step;

@@ -21,15 +21,6 @@
 SF_GDECL(1) SF_GDECL(2) SF_GDECL(3) SF_GDECL(4)
 
 namespace {
-int gt_fail(int code, const std::string& msg) {
-  sf_set_error(msg);
-  return code;
-}
-#define SF_GT_HIP(call)                                                                        \
-  do {                                                                                         \
-    hipError_t e_ = (call);                                                                    \
-    if (e_ != hipSuccess) return gt_fail(SF_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-  } while (0)
 
 // The stash of one launch is bounded; a larger batch runs as several launches over consecutive tiles.  The bound is 256 MiB,
 // or one tile per SIMD of the device where that is more: the kernels run one wave per SIMD, so a launch of fewer tiles than
@@ -121,11 +112,11 @@ int sf_map_step(int64_t B, int64_t D, float* phi, float* exp_avg, float* exp_avg
                 const float* g_theta, const float* lo, const float* hi, float* best_theta, float* best_lp,
                 float learning_rate, int64_t step, int save_best, void* stream) {
   if (B == 0) return SF_OK;
-  if (B < 0 || D < 1 || D > SF_DMAX) return gt_fail(SF_ERR_INVALID, "sf_map_step: B < 0 or D outside 1..16");
-  if (!theta || !lp || !best_theta || !best_lp) return gt_fail(SF_ERR_INVALID, "sf_map_step: null argument");
+  if (B < 0 || D < 1 || D > SF_DMAX) return sf_fail(SF_ERR_INVALID, "sf_map_step: B < 0 or D outside 1..16");
+  if (!theta || !lp || !best_theta || !best_lp) return sf_fail(SF_ERR_INVALID, "sf_map_step: null argument");
   if (g_theta && (!phi || !exp_avg || !exp_avg_sq || step < 1))
-    return gt_fail(SF_ERR_INVALID, "sf_map_step: a step needs phi, both moments and step >= 1");
-  if ((lo == nullptr) != (hi == nullptr)) return gt_fail(SF_ERR_INVALID, "sf_map_step: lo and hi come together");
+    return sf_fail(SF_ERR_INVALID, "sf_map_step: a step needs phi, both moments and step >= 1");
+  if ((lo == nullptr) != (hi == nullptr)) return sf_fail(SF_ERR_INVALID, "sf_map_step: lo and hi come together");
   SfMapStepArgs a;
   a.B = (long)B; a.D = (int)D; a.phi = phi; a.m = exp_avg; a.v = exp_avg_sq; a.theta = theta; a.lp = lp; a.g = g_theta;
   a.lo = lo; a.hi = hi; a.best_theta = best_theta; a.best_lp = best_lp;
@@ -135,23 +126,23 @@ int sf_map_step(int64_t B, int64_t D, float* phi, float* exp_avg, float* exp_avg
   a.inv_sqrt_bc2 = (float)(1.0 / std::sqrt(1.0 - std::pow(0.999, t)));
   a.save_best = save_best;
   hipLaunchKernelGGL(k_map_step, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-  SF_GT_HIP(hipGetLastError());
+  SF_TRY_SET(hipGetLastError());
   return SF_OK;
 }
 
 int sf_flow_log_prob_grad(sf_flow* f, const float* theta, const float* x, int64_t rows_per_x, int64_t B, float* lp,
                           float* dtheta, void* stream) {
-  if (!f) return gt_fail(SF_ERR_INVALID, "null handle");
-  if (f->nsf1) return gt_fail(SF_ERR_INVALID, "sf_flow_log_prob_grad: the one-parameter NSF has no theta-gradient path");
+  if (!f) return sf_fail(SF_ERR_INVALID, "null handle");
+  if (f->nsf1) return sf_fail(SF_ERR_INVALID, "sf_flow_log_prob_grad: the one-parameter NSF has no theta-gradient path");
   if (f->nsfar)
-    return gt_fail(SF_ERR_INVALID, std::string("sf_flow_log_prob_grad: the autoregressive ") +
+    return sf_fail(SF_ERR_INVALID, std::string("sf_flow_log_prob_grad: the autoregressive ") +
                                        (f->L.dev.kind == SF_MAF_AR ? "MAF (maf_ar)" : "NSF (nsf_ar)") +
                                        " has no theta-gradient path");
   if (B == 0 || (!lp && !dtheta)) return SF_OK;
-  if (B < 0 || rows_per_x < 1) return gt_fail(SF_ERR_INVALID, "sf_flow_log_prob_grad: B < 0 or rows_per_x < 1");
-  if (!theta || !x) return gt_fail(SF_ERR_INVALID, "null argument");
+  if (B < 0 || rows_per_x < 1) return sf_fail(SF_ERR_INVALID, "sf_flow_log_prob_grad: B < 0 or rows_per_x < 1");
+  if (!theta || !x) return sf_fail(SF_ERR_INVALID, "null argument");
   if (!f->params_set || !f->flat_valid)
-    return gt_fail(SF_ERR_STATE, "sf_flow_log_prob_grad: no parameters held by the handle (after sf_flow_loss_grad the caller's "
+    return sf_fail(SF_ERR_STATE, "sf_flow_log_prob_grad: no parameters held by the handle (after sf_flow_loss_grad the caller's "
                                  "vector is the master copy: call sf_flow_set_params first)");
   hipStream_t st = (hipStream_t)stream;
   const SfLayout& L = f->L;
@@ -170,10 +161,10 @@ int sf_flow_log_prob_grad(sf_flow* f, const float* theta, const float* x, int64_
       if (e == hipSuccess) e = hipMemcpy(f->d_gt2, L.srcT2.data(), n * sizeof(int32_t), hipMemcpyHostToDevice);
       if (e != hipSuccess) {
         undo();
-        return gt_fail(SF_ERR_HIP, std::string("transposed inference image: ") + hipGetErrorString(e));
+        return sf_fail(SF_ERR_HIP, std::string("transposed inference image: ") + hipGetErrorString(e));
       }
     }
-    SF_GT_HIP(sf_launch_pack(f->d_flat, f->d_gt1, f->d_gt2, f->d_gtT, (long)n, st));
+    SF_TRY_SET(sf_launch_pack(f->d_flat, f->d_gt1, f->d_gt2, f->d_gtT, (long)n, st));
     f->gt_image_valid = true;
   }
   SfDev m = f->dev();
@@ -195,10 +186,10 @@ int sf_flow_log_prob_grad(sf_flow* f, const float* theta, const float* x, int64_
     }
     const size_t need = (size_t)per_launch * per_tile;
     if (need > f->act_cap) {  // (the stash is scratch shared with the training kernels)
-      if (f->d_act) SF_GT_HIP(hipFree(f->d_act));
+      if (f->d_act) SF_TRY_SET(hipFree(f->d_act));
       f->d_act = nullptr;
       f->act_cap = 0;
-      SF_GT_HIP(hipMalloc(&f->d_act, need * sizeof(float)));
+      SF_TRY_SET(hipMalloc(&f->d_act, need * sizeof(float)));
       f->act_cap = need;
     }
     a.act = reinterpret_cast<float4*>(f->d_act);
@@ -208,11 +199,11 @@ int sf_flow_log_prob_grad(sf_flow* f, const float* theta, const float* x, int64_
     a.tile0 = t0;
     const long n = tiles - t0 < per_launch ? tiles - t0 : per_launch;
     switch (m.HT) {
-      case 1: SF_GT_HIP(maf ? sf_launch_maf_gradtheta_h1(m, a, n, st) : sf_launch_nsf_gradtheta_h1(m, a, n, st)); break;
-      case 2: SF_GT_HIP(maf ? sf_launch_maf_gradtheta_h2(m, a, n, st) : sf_launch_nsf_gradtheta_h2(m, a, n, st)); break;
-      case 3: SF_GT_HIP(maf ? sf_launch_maf_gradtheta_h3(m, a, n, st) : sf_launch_nsf_gradtheta_h3(m, a, n, st)); break;
-      case 4: SF_GT_HIP(maf ? sf_launch_maf_gradtheta_h4(m, a, n, st) : sf_launch_nsf_gradtheta_h4(m, a, n, st)); break;
-      default: return gt_fail(SF_ERR_INVALID, "bad HT");
+      case 1: SF_TRY_SET(maf ? sf_launch_maf_gradtheta_h1(m, a, n, st) : sf_launch_nsf_gradtheta_h1(m, a, n, st)); break;
+      case 2: SF_TRY_SET(maf ? sf_launch_maf_gradtheta_h2(m, a, n, st) : sf_launch_nsf_gradtheta_h2(m, a, n, st)); break;
+      case 3: SF_TRY_SET(maf ? sf_launch_maf_gradtheta_h3(m, a, n, st) : sf_launch_nsf_gradtheta_h3(m, a, n, st)); break;
+      case 4: SF_TRY_SET(maf ? sf_launch_maf_gradtheta_h4(m, a, n, st) : sf_launch_nsf_gradtheta_h4(m, a, n, st)); break;
+      default: return sf_fail(SF_ERR_INVALID, "bad HT");
     }
   }
   return SF_OK;

@@ -121,14 +121,6 @@ struct State {
   std::condition_variable dcv;
 };
 State g;
-#define HIO(call)                                                            \
-  do {                                                                       \
-    hipError_t e_ = (call);                                                  \
-    if (e_ != hipSuccess) {                                                  \
-      err = std::string(#call) + ": " + hipGetErrorString(e_);               \
-      return SF_ERR_HIP;                                                     \
-    }                                                                        \
-  } while (0)
 
 void wait_slot(int b) {
   std::unique_lock<std::mutex> lk(g.dm);
@@ -140,7 +132,7 @@ void wait_slot(int b) {
 int sf_hostio_copy_f64(const float* dev_src, double* host_dst, int64_t n, hipStream_t stream, std::string& err) {
   std::lock_guard<std::mutex> call(g.call);
   int dev = 0;
-  HIO(hipGetDevice(&dev));
+  SF_TRY_ERR(hipGetDevice(&dev));
   const size_t pb = piece_bytes();
   if (g.device != dev || g.stage_bytes != pb) {   // first call (or another device / piece size): build the pipeline
     for (int b = 0; b < NBUF; ++b) {
@@ -156,11 +148,11 @@ int sf_hostio_copy_f64(const float* dev_src, double* host_dst, int64_t n, hipStr
     g.ev_src = nullptr;
     g.stage_bytes = 0;
     for (int b = 0; b < NBUF; ++b) {
-      HIO(hipHostMalloc((void**)&g.stage[b], pb, hipHostMallocDefault));
-      HIO(hipEventCreateWithFlags(&g.ev[b], hipEventDisableTiming));
+      SF_TRY_ERR(hipHostMalloc((void**)&g.stage[b], pb, hipHostMallocDefault));
+      SF_TRY_ERR(hipEventCreateWithFlags(&g.ev[b], hipEventDisableTiming));
     }
-    HIO(hipStreamCreateWithFlags(&g.cs, hipStreamNonBlocking));
-    HIO(hipEventCreateWithFlags(&g.ev_src, hipEventDisableTiming));
+    SF_TRY_ERR(hipStreamCreateWithFlags(&g.cs, hipStreamNonBlocking));
+    SF_TRY_ERR(hipEventCreateWithFlags(&g.ev_src, hipEventDisableTiming));
     g.device = dev;
     g.stage_bytes = pb;
   }
@@ -172,8 +164,8 @@ int sf_hostio_copy_f64(const float* dev_src, double* host_dst, int64_t n, hipStr
     g.workers = w;
   }
   // the draws were written on the caller's stream
-  HIO(hipEventRecord(g.ev_src, stream));
-  HIO(hipStreamWaitEvent(g.cs, g.ev_src, 0));
+  SF_TRY_ERR(hipEventRecord(g.ev_src, stream));
+  SF_TRY_ERR(hipStreamWaitEvent(g.cs, g.ev_src, 0));
   const size_t per = pb / sizeof(float);
   const int64_t n_pieces = (int64_t)(((size_t)n + per - 1) / per);
   auto issue = [&](int64_t k) -> hipError_t {

@@ -26,12 +26,13 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
-#include <mutex>
 #include <string>
 #include <vector>
 
+#include "sf_block.h"
 #include "sf_internal.h"
 #include "sf_rng.h"
+#include "sf_scratch.h"
 
 #define SF_IMP_BMAX 32
 #define SF_IMP_FMAX 64
@@ -132,29 +133,7 @@ __global__ __launch_bounds__(256) void k_imp_count(const float* __restrict__ tra
   }
 }
 
-// ---- block helpers (256 threads, fixed order: the same bits on every call) ----------------------------------------------
-__device__ __forceinline__ int sf_imp_sum_int(int v, int* s_red) {
-  const int tid = threadIdx.x;
-  __syncthreads();
-  s_red[tid] = v;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) s_red[tid] += s_red[tid + o];
-    __syncthreads();
-  }
-  return s_red[0];
-}
-__device__ __forceinline__ double sf_imp_sum_dbl(double v, double* s_red) {
-  const int tid = threadIdx.x;
-  __syncthreads();
-  s_red[tid] = v;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) s_red[tid] += s_red[tid + o];
-    __syncthreads();
-  }
-  return s_red[0];
-}
+// ---- block helpers (256 threads, fixed order: the same bits on every call); the sums are sf_block.h's ------------------
 // ordered rank of the set flags of the workgroup: returns this thread's exclusive rank, *total = flags set
 __device__ __forceinline__ int sf_imp_rank(bool flag, int* s_w, int* total) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -189,7 +168,7 @@ __global__ __launch_bounds__(256) void k_imp_decide(const float* __restrict__ tr
   for (int l = 0; l < L; ++l) {
     int v = 0;
     for (int c = tid; c < NCH; c += 256) v += co[(long)c * LC + l];
-    v = sf_imp_sum_int(v, s_red);
+    v = sf_block_sum(v, s_red);
     if (tid == 0) s_tot[l] = v;
   }
   __syncthreads();
@@ -239,8 +218,8 @@ __global__ __launch_bounds__(256) void k_imp_decide(const float* __restrict__ tr
           eq += u == P ? 1 : 0;
         }
       }
-      less = sf_imp_sum_int(less, s_red);
-      eq = sf_imp_sum_int(eq, s_red);
+      less = sf_block_sum(less, s_red);
+      eq = sf_block_sum(eq, s_red);
       if (tid == 0) {
         const int left = need_eq - s_eq_taken;
         const int quota = eq < left ? eq : left;
@@ -281,30 +260,6 @@ __global__ __launch_bounds__(256) void k_imp_decide(const float* __restrict__ tr
     pbits[o] = fb ? s_pre : 0u;
     n_used[m] = ok ? n : (dof == 0.f ? -2 : -1);
     if (thr_used) thr_used[m] = lad.thr[fb ? L - 1 : lvl];
-  }
-}
-
-// exclusive scan of n <= 2^31 counts by one workgroup (group offsets of the lists)
-__global__ __launch_bounds__(1024) void k_imp_scan(const int32_t* __restrict__ cnt, int N, int32_t* __restrict__ offs) {
-  __shared__ int part[1024];
-  const int tid = threadIdx.x;
-  const int chunk = (N + 1023) / 1024;
-  const long lo = (long)tid * chunk;
-  const long hi = lo + chunk < N ? lo + chunk : N;
-  int s = 0;
-  for (long i = lo; i < hi; ++i) s += cnt[i];
-  part[tid] = s;
-  __syncthreads();
-  for (int o = 1; o < 1024; o <<= 1) {
-    const int v = tid >= o ? part[tid - o] : 0;
-    __syncthreads();
-    part[tid] += v;
-    __syncthreads();
-  }
-  int run = part[tid] - s;
-  for (long i = lo; i < hi; ++i) {
-    offs[i] = run;
-    run += cnt[i];
   }
 }
 
@@ -433,16 +388,16 @@ __global__ __launch_bounds__(256) void k_imp_draw(const float* __restrict__ trai
   const double W = C[n - 1];
   double v = 0.0;
   for (int j = tid; j < n; j += 256) { const double wn = w[j] / W; v += wn * wn; }
-  const double sw2 = sf_imp_sum_dbl(v, s_red);
+  const double sw2 = sf_block_sum(v, s_red);
   for (int b = 0; b < B; ++b) {
     if (!((mm >> b) & 1u)) continue;
     const int col = cols.bc[b];
     v = 0.0;
     for (int j = tid; j < n; j += 256) v += (w[j] / W) * (double)train[(long)lst[j] * F + col];
-    const double mu = sf_imp_sum_dbl(v, s_red);
+    const double mu = sf_block_sum(v, s_red);
     v = 0.0;
     for (int j = tid; j < n; j += 256) { const double d = (double)train[(long)lst[j] * F + col] - mu; v += (w[j] / W) * d * d; }
-    const double var = (double)bw * (double)bw * sf_imp_sum_dbl(v, s_red) / (1.0 - sw2);
+    const double var = (double)bw * (double)bw * sf_block_sum(v, s_red) / (1.0 - sw2);
     if (tid == 0) {
       s_sd[b] = (float)sqrt(var);
       if (kde_var) kde_var[m * B + b] = var;
@@ -499,19 +454,9 @@ __global__ __launch_bounds__(256) void k_imp_draw(const float* __restrict__ trai
   }
 }
 
-// ---- scratch: per device, grown when a call needs more; a call on another stream waits for the previous call ------------
+// ---- scratch (sf_scratch.h): region 0 = counts, chunk offsets, per-object words; region 1 = lists, weights, running sums -
 namespace {
-struct SfImpWs {
-  void* a = nullptr;   // counts, chunk offsets, per-object words
-  size_t cap_a = 0;
-  void* b = nullptr;   // lists, weights, running sums
-  size_t cap_b = 0;
-  hipEvent_t ev = nullptr;
-  bool used = false;
-};
-std::mutex g_imp_mu;
-SfImpWs g_imp_ws[16];
-inline size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
+SfScratch g_imp_scratch;
 }  // namespace
 
 extern "C" int sf_impute_missing(const float* train, int64_t NT, int32_t F, const int32_t* band_col, const int32_t* err_col,
@@ -559,12 +504,6 @@ extern "C" int sf_impute_missing(const float* train, int64_t NT, int32_t F, cons
   }
   if (M == 0) return SF_OK;
   hipStream_t st = (hipStream_t)stream;
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess || dev < 0 || dev >= 16) {
-    sf_set_error(std::string("sf_impute_missing: no usable device: ") + hipGetErrorString(e));
-    return SF_ERR_NO_DEVICE;
-  }
   size_t budget = (size_t)256 << 20;
   if (const char* s = std::getenv("SF_IMPUTE_SCRATCH_BYTES")) {
     const long long v = std::atoll(s);
@@ -577,38 +516,20 @@ extern "C" int sf_impute_missing(const float* train, int64_t NT, int32_t F, cons
   int64_t MB = ((int64_t)64 << 20) / ((int64_t)NCH * LC * 4);
   MB = MB < 1 ? 1 : (MB > M ? M : MB);
   MB = MB > 65535ll * SF_IMP_OT ? 65535ll * SF_IMP_OT : MB;
-  const size_t b_cnt = up256((size_t)MB * NCH * LC * 4), b_off = up256((size_t)MB * NCH * 4), b_obj = up256((size_t)MB * 4);
-  const size_t need_a = b_cnt + b_off + 4 * b_obj;
 
-  std::lock_guard<std::mutex> lock(g_imp_mu);
-  SfImpWs& ws = g_imp_ws[dev];
-  auto fail = [&](const char* what, hipError_t err) {
-    if (ws.ev && ws.used) (void)hipEventRecord(ws.ev, st);
-    sf_set_error(std::string("sf_impute_missing: ") + what + ": " + hipGetErrorString(err));
-    return SF_ERR_HIP;
-  };
-  if (!ws.ev && (e = hipEventCreateWithFlags(&ws.ev, hipEventDisableTiming)) != hipSuccess) return fail("event", e);
-  auto grow = [&](void*& p, size_t& cap, size_t need) -> hipError_t {
-    if (cap >= need) return hipSuccess;
-    hipError_t r;
-    if (p && (r = hipFree(p)) != hipSuccess) return r;   // waits for the work that uses it
-    p = nullptr;
-    cap = 0;
-    if ((r = hipMalloc(&p, need)) != hipSuccess) return r;
-    cap = need;
-    return hipSuccess;
-  };
-  if ((e = grow(ws.a, ws.cap_a, need_a)) != hipSuccess) return fail("hipMalloc", e);
-  if (ws.used && (e = hipStreamWaitEvent(st, ws.ev, 0)) != hipSuccess) return fail("hipStreamWaitEvent", e);
-  ws.used = true;
-  char* p = (char*)ws.a;
-  auto take = [&](size_t bytes) { char* q = p; p += bytes; return q; };
-  int32_t* cnt = (int32_t*)take(b_cnt);
-  int32_t* choff = (int32_t*)take(b_off);
-  int32_t* lvlsel = (int32_t*)take(b_obj);
-  int32_t* nsel = (int32_t*)take(b_obj);
-  uint32_t* pbits = (uint32_t*)take(b_obj);
-  int32_t* goff = (int32_t*)take(b_obj);
+  SfScratchCall ws(g_imp_scratch, "sf_impute_missing", st);
+  const int sub_cnt = ws.add((size_t)MB * NCH * LC * 4), sub_choff = ws.add((size_t)MB * NCH * 4);
+  const int sub_lvlsel = ws.add((size_t)MB * 4), sub_nsel = ws.add((size_t)MB * 4), sub_pbits = ws.add((size_t)MB * 4);
+  const int sub_goff = ws.add((size_t)MB * 4);
+  if (int rc = ws.reserve()) return rc;
+  int32_t* cnt = ws.get<int32_t>(sub_cnt);
+  int32_t* choff = ws.get<int32_t>(sub_choff);
+  int32_t* lvlsel = ws.get<int32_t>(sub_lvlsel);
+  int32_t* nsel = ws.get<int32_t>(sub_nsel);
+  uint32_t* pbits = ws.get<uint32_t>(sub_pbits);
+  int32_t* goff = ws.get<int32_t>(sub_goff);
+  if (int rc = ws.check()) return rc;
+  hipError_t e;
   const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32) ^ 5u;
   std::vector<int32_t> h_nsel((size_t)MB);
 
@@ -620,9 +541,9 @@ extern "C" int sf_impute_missing(const float* train, int64_t NT, int32_t F, cons
     hipLaunchKernelGGL(k_imp_decide, dim3((unsigned)Mb), dim3(256), 0, st, train, (long)NT, (int)F, (int)B, cols, obs, sigma,
                        missing, (long)m0, lad, NCH, LC, (int)min_neighbours, (int)fallback_k, cnt, choff, lvlsel, nsel, pbits,
                        n_used, thr_used);
-    if ((e = hipGetLastError()) != hipSuccess) return fail("launch", e);
-    if ((e = hipMemcpyAsync(h_nsel.data(), nsel, (size_t)Mb * 4, hipMemcpyDeviceToHost, st)) != hipSuccess) return fail("hipMemcpyAsync", e);
-    if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail("hipStreamSynchronize", e);
+    if ((e = hipGetLastError()) != hipSuccess) return ws.fail("launch", e);
+    if ((e = hipMemcpyAsync(h_nsel.data(), nsel, (size_t)Mb * 4, hipMemcpyDeviceToHost, st)) != hipSuccess) return ws.fail("hipMemcpyAsync", e);
+    if ((e = hipStreamSynchronize(st)) != hipSuccess) return ws.fail("hipStreamSynchronize", e);
     int g0 = 0;
     while (g0 < Mb) {
       // a group: consecutive objects whose lists fit the budget (one object on its own may exceed it)
@@ -630,23 +551,25 @@ extern "C" int sf_impute_missing(const float* train, int64_t NT, int32_t F, cons
       int g1 = g0 + 1;
       while (g1 < Mb && g1 - g0 < 65535 && entries + (size_t)h_nsel[g1] <= budget_entries) entries += (size_t)h_nsel[g1++];
       const size_t cap_e = entries > 0 ? entries : 1;
-      const size_t b_list = up256(cap_e * 4), b_dbl = up256(cap_e * 8);
-      if ((e = grow(ws.b, ws.cap_b, b_list + 2 * b_dbl)) != hipSuccess) return fail("hipMalloc", e);
-      int32_t* list = (int32_t*)ws.b;
-      double* wraw = (double*)((char*)ws.b + b_list);
-      double* cdf = (double*)((char*)ws.b + b_list + b_dbl);
+      ws.clear(1);
+      const int sub_list = ws.add(cap_e * 4, 1), sub_wraw = ws.add(cap_e * 8, 1), sub_cdf = ws.add(cap_e * 8, 1);
+      if (int rc = ws.reserve(1)) return rc;
+      int32_t* list = ws.get<int32_t>(sub_list);
+      double* wraw = ws.get<double>(sub_wraw);
+      double* cdf = ws.get<double>(sub_cdf);
+      if (int rc = ws.check()) return rc;
       const int ng = g1 - g0;
-      hipLaunchKernelGGL(k_imp_scan, dim3(1), dim3(1024), 0, st, nsel + g0, ng, goff + g0);
+      // (no total: goff + g0 has no spare element behind a group)
+      if ((e = sf_launch_exclusive_scan_i32(nsel + g0, ng, goff + g0, nullptr, st)) != hipSuccess) return ws.fail("launch", e);
       if (entries > 0)
         hipLaunchKernelGGL(k_imp_compact, dim3((unsigned)NCH, (unsigned)ng), dim3(256), 0, st, train, (long)NT, (int)F, (int)B, cols,
                            obs, sigma, missing, (long)m0, g0, lad, NCH, LC, cnt, choff, lvlsel, pbits, goff, list);
       hipLaunchKernelGGL(k_imp_draw, dim3((unsigned)ng), dim3(256), 0, st, train, (int)F, (int)B, cols, err_col ? 1 : 0, obs, missing,
                          (long)m0, g0, (long)row_offset, bw, (int)nmc, k0, k1, nsel, goff, list, wraw, cdf, imputed, recon, kde_var,
                          nbr_idx, (long)nbr_cap, draw_idx);
-      if ((e = hipGetLastError()) != hipSuccess) return fail("launch", e);
+      if ((e = hipGetLastError()) != hipSuccess) return ws.fail("launch", e);
       g0 = g1;
     }
   }
-  if ((e = hipEventRecord(ws.ev, st)) != hipSuccess) return fail("hipEventRecord", e);
-  return SF_OK;
+  return ws.finish();
 }

@@ -96,6 +96,8 @@ hipError_t sf_launch_pack_bf16(const float* flat, const int32_t* src, unsigned s
 hipError_t sf_launch_pack_bf16_split(const float* flat, const int32_t* src, unsigned short* out, long n, hipStream_t st);
 hipError_t sf_launch_fill_nan_rows(float* out, const uint32_t* slots, long n, int D, hipStream_t st, int out_f64 = 0);
 hipError_t sf_launch_fill_i32(int32_t* p, long n, int32_t v, hipStream_t st);
+// exclusive scan of n int32 counts by one workgroup (the sum stays below 2^31): offs[0..n), and the sum to *total unless null
+hipError_t sf_launch_exclusive_scan_i32(const int32_t* cnt, int n, int32_t* offs, int32_t* total, hipStream_t st);
 hipError_t sf_launch_account_window(const uint32_t* list, const uint32_t* best, long n, long S, uint32_t a_lo, uint32_t A,
                                     int32_t* n_drawn, int32_t* gal_acc, hipStream_t st);
 // survivors of galaxies with gal_acc == 0 become NaN rows; the others are compacted in place; *n_surv updated
@@ -103,16 +105,17 @@ hipError_t sf_launch_filter_survivors(uint32_t* list, unsigned int* n_surv, long
                                       int D, hipStream_t st, int out_f64 = 0);
 
 #include <string>
+#define SF_MAX_DEVICES 16   // devices of one process that per-device host state (attribute caches, tool scratch) has a slot for
 // per-device "attribute already set" cache for hipFuncSetAttribute(MaxDynamicSharedMemorySize): function attributes are
 // per device, so a process that launches on a second device must set them there too
 struct SfAttrCache {
-  bool done[16] = {false};
+  bool done[SF_MAX_DEVICES] = {false};
   bool need(int& dev) {
     dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return true;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= SF_MAX_DEVICES) return true;
     return !done[dev];
   }
-  void set(int dev) { if (dev >= 0 && dev < 16) done[dev] = true; }
+  void set(int dev) { if (dev >= 0 && dev < SF_MAX_DEVICES) done[dev] = true; }
 };
 // resident workgroups of a persistent kernel, cached per (device, dynamic LDS bytes): the occupancy of one template instance
 // depends on the flow's LDS footprint and the grid on the device's CU count -- a process that samples flows of different
@@ -129,9 +132,25 @@ struct SfResidentCache {
   }
   void put(int d, size_t s, int v) { dev[n & 7] = d; sh[n & 7] = s; val[n & 7] = v; ++n; }
 };
-void sf_set_error(const std::string& msg);
+void sf_set_error(const std::string& msg);          // thread-local message behind sf_last_error()
+int sf_fail(int code, const std::string& msg);      // sf_set_error(msg), then `code` for the caller to return
+// a HIP call that must succeed: on failure the message "<call>: <hip error>" and return SF_ERR_HIP.  _ERR writes the message
+// to the enclosing function's `std::string err` (helpers whose caller reports it), _SET makes it the thread's last error.
+#define SF_TRY_ERR(call)                                                     \
+  do {                                                                       \
+    hipError_t e_ = (call);                                                  \
+    if (e_ != hipSuccess) {                                                  \
+      err = std::string(#call) + ": " + hipGetErrorString(e_);               \
+      return SF_ERR_HIP;                                                     \
+    }                                                                        \
+  } while (0)
+#define SF_TRY_SET(call)                                                                                   \
+  do {                                                                                                     \
+    hipError_t e_ = (call);                                                                                \
+    if (e_ != hipSuccess) return sf_fail(SF_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));   \
+  } while (0)
 struct sf_comm;
-int sf_comm_all_reduce_impl(sf_comm* c, float* buf, long n, hipStream_t st);  // sf_comm.hip: ncclAllReduce(SUM, fp32) in place  // thread-local message behind sf_last_error()
+int sf_comm_all_reduce_impl(sf_comm* c, float* buf, long n, hipStream_t st);  // sf_comm.hip: ncclAllReduce(SUM, fp32) in place
 
 // ---- the handle (shared by sf_api.hip and sf_train.hip) -------------------------------------
 #define SF_LOSS_PARTS 64

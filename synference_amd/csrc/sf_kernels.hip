@@ -2,6 +2,7 @@
 // of sf_inst.hip.
 #include <hip/hip_runtime.h>
 
+#include "sf_block.h"
 #include "sf_device.h"
 #include "sf_internal.h"
 
@@ -43,6 +44,25 @@ __global__ void k_pack_bf16_split(const float* __restrict__ flat, const int32_t*
     r = __builtin_bit_cast(unsigned short, (a >> 30) & 1 ? (__bf16)(w - (float)hi) : hi);
   }
   out[i] = r;
+}
+
+// exclusive scan of n counts by one workgroup: thread t owns the counts [t * chunk, (t + 1) * chunk)
+__global__ __launch_bounds__(1024) void k_exclusive_scan_i32(const int32_t* __restrict__ cnt, int N, int32_t* __restrict__ offs,
+                                                             int32_t* __restrict__ total) {
+  __shared__ int part[1024];
+  const int tid = threadIdx.x;
+  const int chunk = (N + 1023) / 1024;
+  const long lo = (long)tid * chunk;
+  const long hi = lo + chunk < N ? lo + chunk : N;
+  int s = 0;
+  for (long i = lo; i < hi; ++i) s += cnt[i];
+  int tot;
+  int run = sf_block_exscan<1024>(s, part, &tot);
+  for (long i = lo; i < hi; ++i) {
+    offs[i] = run;
+    run += cnt[i];
+  }
+  if (total && tid == 1023) *total = tot;
 }
 
 __global__ void k_fill_nan_rows(float* __restrict__ out, const uint32_t* __restrict__ slots, long n, int D, int out_f64) {
@@ -233,5 +253,9 @@ hipError_t sf_launch_account_window(const uint32_t* list, const uint32_t* best, 
 hipError_t sf_launch_fill_i32(int32_t* p, long n, int32_t v, hipStream_t st) {
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_fill_i32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p, n, v);
+  return hipGetLastError();
+}
+hipError_t sf_launch_exclusive_scan_i32(const int32_t* cnt, int n, int32_t* offs, int32_t* total, hipStream_t st) {
+  hipLaunchKernelGGL(k_exclusive_scan_i32, dim3(1), dim3(1024), 0, st, cnt, n, offs, total);
   return hipGetLastError();
 }

@@ -176,14 +176,6 @@ __global__ void k_mlp_gather(const float* __restrict__ gimg, const int32_t* __re
 }
 
 namespace {
-#define SF_MTRY(call)                                                              \
-  do {                                                                             \
-    hipError_t e_ = (call);                                                        \
-    if (e_ != hipSuccess) {                                                        \
-      sf_set_error(std::string(#call) + ": " + hipGetErrorString(e_));             \
-      return SF_ERR_HIP;                                                           \
-    }                                                                              \
-  } while (0)
 
 int mlp_ensure(sf_mlp* m) {
   if (m->dev_ready) return SF_OK;
@@ -198,14 +190,14 @@ int mlp_ensure(sf_mlp* m) {
     if (e != hipSuccess) return e;
     return hipMemcpy(*d, v.data(), v.size() * sizeof(int32_t), hipMemcpyHostToDevice);
   };
-  SF_MTRY(hipMalloc(&m->d_packed, (size_t)L.n_packed * sizeof(float)));
-  SF_MTRY(hipMalloc(&m->d_packedT, std::max<size_t>((size_t)L.n_packedT, 64) * sizeof(float)));
-  SF_MTRY(hipMalloc(&m->d_gimg, (size_t)L.n_packed * sizeof(float)));
-  SF_MTRY(hipMalloc(&m->d_cst, L.cst.size() * sizeof(float)));
-  SF_MTRY(hipMemcpy(m->d_cst, L.cst.data(), L.cst.size() * sizeof(float), hipMemcpyHostToDevice));
-  SF_MTRY(up(L.src1, &m->d_s1)); SF_MTRY(up(L.src2, &m->d_s2));
-  SF_MTRY(up(L.srcT1, &m->d_t1)); SF_MTRY(up(L.srcT2, &m->d_t2));
-  SF_MTRY(up(L.gdst, &m->d_gdst));
+  SF_TRY_SET(hipMalloc(&m->d_packed, (size_t)L.n_packed * sizeof(float)));
+  SF_TRY_SET(hipMalloc(&m->d_packedT, std::max<size_t>((size_t)L.n_packedT, 64) * sizeof(float)));
+  SF_TRY_SET(hipMalloc(&m->d_gimg, (size_t)L.n_packed * sizeof(float)));
+  SF_TRY_SET(hipMalloc(&m->d_cst, L.cst.size() * sizeof(float)));
+  SF_TRY_SET(hipMemcpy(m->d_cst, L.cst.data(), L.cst.size() * sizeof(float), hipMemcpyHostToDevice));
+  SF_TRY_SET(up(L.src1, &m->d_s1)); SF_TRY_SET(up(L.src2, &m->d_s2));
+  SF_TRY_SET(up(L.srcT1, &m->d_t1)); SF_TRY_SET(up(L.srcT2, &m->d_t2));
+  SF_TRY_SET(up(L.gdst, &m->d_gdst));
   m->dev_ready = true;
   return SF_OK;
 }
@@ -262,15 +254,15 @@ int sf_mlp_forward(sf_mlp* m, const float* flat, const float* x, int64_t B, floa
   int rc = mlp_ensure(m);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  SF_MTRY(sf_launch_pack(flat, m->d_s1, m->d_s2, m->d_packed, (long)m->L.n_packed, st));
+  SF_TRY_SET(sf_launch_pack(flat, m->d_s1, m->d_s2, m->d_packed, (long)m->L.n_packed, st));
   SfMlpArgs a{};
   a.x = x; a.out = out; a.B = B;
   const SfMlpDev d = m->dev();
   switch (d.HT) {
-    case 1: SF_MTRY(launch_fwd<1>(d, a, st)); break;
-    case 2: SF_MTRY(launch_fwd<2>(d, a, st)); break;
-    case 3: SF_MTRY(launch_fwd<3>(d, a, st)); break;
-    default: SF_MTRY(launch_fwd<4>(d, a, st)); break;
+    case 1: SF_TRY_SET(launch_fwd<1>(d, a, st)); break;
+    case 2: SF_TRY_SET(launch_fwd<2>(d, a, st)); break;
+    case 3: SF_TRY_SET(launch_fwd<3>(d, a, st)); break;
+    default: SF_TRY_SET(launch_fwd<4>(d, a, st)); break;
   }
   return SF_OK;
 }
@@ -287,29 +279,29 @@ int sf_mlp_backward(sf_mlp* m, const float* flat, const float* x, const float* d
   const long act_per_wave = (long)std::max(1, (L.dev.L - 1) * L.dev.HT) * 4 * 64;
   const size_t need = (size_t)std::max<long>(waves, 1) * act_per_wave * 4;
   if (need > m->act_cap) {
-    if (m->d_act) SF_MTRY(hipFree(m->d_act));
+    if (m->d_act) SF_TRY_SET(hipFree(m->d_act));
     m->d_act = nullptr; m->act_cap = 0;
-    SF_MTRY(hipMalloc(&m->d_act, need * sizeof(float)));
+    SF_TRY_SET(hipMalloc(&m->d_act, need * sizeof(float)));
     m->act_cap = need;
   }
-  SF_MTRY(sf_launch_pack(flat, m->d_s1, m->d_s2, m->d_packed, (long)L.n_packed, st));
-  if (L.n_packedT > 0) SF_MTRY(sf_launch_pack(flat, m->d_t1, m->d_t2, m->d_packedT, (long)L.n_packedT, st));
-  SF_MTRY(hipMemsetAsync(m->d_gimg, 0, (size_t)L.n_packed * sizeof(float), st));
+  SF_TRY_SET(sf_launch_pack(flat, m->d_s1, m->d_s2, m->d_packed, (long)L.n_packed, st));
+  if (L.n_packedT > 0) SF_TRY_SET(sf_launch_pack(flat, m->d_t1, m->d_t2, m->d_packedT, (long)L.n_packedT, st));
+  SF_TRY_SET(hipMemsetAsync(m->d_gimg, 0, (size_t)L.n_packed * sizeof(float), st));
   if (B > 0) {
     SfMlpArgs a{};
     a.x = x; a.dout = dout; a.B = B; a.gimg = m->d_gimg;
     a.act = reinterpret_cast<float4*>(m->d_act); a.act_per_wave = act_per_wave;
     const SfMlpDev d = m->dev();
     switch (d.HT) {
-      case 1: SF_MTRY(launch_bwd<1>(d, a, st)); break;
-      case 2: SF_MTRY(launch_bwd<2>(d, a, st)); break;
-      case 3: SF_MTRY(launch_bwd<3>(d, a, st)); break;
-      default: SF_MTRY(launch_bwd<4>(d, a, st)); break;
+      case 1: SF_TRY_SET(launch_bwd<1>(d, a, st)); break;
+      case 2: SF_TRY_SET(launch_bwd<2>(d, a, st)); break;
+      case 3: SF_TRY_SET(launch_bwd<3>(d, a, st)); break;
+      default: SF_TRY_SET(launch_bwd<4>(d, a, st)); break;
     }
   }
   hipLaunchKernelGGL(k_mlp_gather, dim3((unsigned)((L.n_params + 255) / 256)), dim3(256), 0, st, m->d_gimg, m->d_gdst,
                      grad, (long)L.n_params);
-  SF_MTRY(hipGetLastError());
+  SF_TRY_SET(hipGetLastError());
   return SF_OK;
 }
 }  // extern "C"

@@ -205,14 +205,6 @@ Nsf1C consts_of(const SfNsf1& n) {
   return c;
 }
 
-#define N1_HIP(call)                                                        \
-  do {                                                                      \
-    hipError_t e_ = (call);                                                 \
-    if (e_ != hipSuccess) {                                                 \
-      err = std::string(#call) + ": " + hipGetErrorString(e_);              \
-      return SF_ERR_HIP;                                                    \
-    }                                                                       \
-  } while (0)
 #define N1_RC(call)                                                         \
   do {                                                                      \
     int rc_ = (call);                                                       \
@@ -224,10 +216,10 @@ Nsf1C consts_of(const SfNsf1& n) {
 
 int grow(float*& p, size_t& cap, size_t need, std::string& err) {
   if (need <= cap) return SF_OK;
-  if (p) N1_HIP(hipFree(p));
+  if (p) SF_TRY_ERR(hipFree(p));
   p = nullptr;
   cap = 0;
-  N1_HIP(hipMalloc(&p, need * sizeof(float)));
+  SF_TRY_ERR(hipMalloc(&p, need * sizeof(float)));
   cap = need;
   return SF_OK;
 }
@@ -277,7 +269,7 @@ int sf_nsf1_log_prob(SfNsf1* n, const float* flat, const float* theta, const flo
   rc = conditioner(*n, flat, x, B, n->d_q, st, err);
   if (rc) return rc;
   hipLaunchKernelGGL(k_nsf1_logprob, dim3((unsigned)((B + 127) / 128)), dim3(128), 0, st, n->d_q, theta, B, consts_of(*n), out);
-  N1_HIP(hipGetLastError());
+  SF_TRY_ERR(hipGetLastError());
   return SF_OK;
 }
 
@@ -288,7 +280,7 @@ int sf_nsf1_inverse(SfNsf1* n, const float* flat, const float* z, const float* x
   rc = conditioner(*n, flat, x, B, n->d_q, st, err);
   if (rc) return rc;
   hipLaunchKernelGGL(k_nsf1_inverse, dim3((unsigned)((B + 127) / 128)), dim3(128), 0, st, n->d_q, z, B, consts_of(*n), theta, logdet);
-  N1_HIP(hipGetLastError());
+  SF_TRY_ERR(hipGetLastError());
   return SF_OK;
 }
 
@@ -296,7 +288,7 @@ int sf_nsf1_loss_grad(SfNsf1* n, const float* flat, const float* theta, const fl
                       float grad_scale, const float* weights, float* loss, double* loss_sum, float* grad, hipStream_t st,
                       std::string& err) {
   if (B == 0) {
-    N1_HIP(hipMemsetAsync(grad, 0, (size_t)n->T * n->P_mlp * sizeof(float), st));
+    SF_TRY_ERR(hipMemsetAsync(grad, 0, (size_t)n->T * n->P_mlp * sizeof(float), st));
     return SF_OK;
   }
   int rc;
@@ -304,7 +296,7 @@ int sf_nsf1_loss_grad(SfNsf1* n, const float* flat, const float* theta, const fl
     if ((rc = grow(n->d_xg, n->xg_cap, (size_t)B * n->C, err)) || (rc = grow(n->d_thg, n->thg_cap, (size_t)B, err))) return rc;
     const long tot = B * (n->C + 1);
     hipLaunchKernelGGL(k_nsf1_gather, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, theta, x, idx, B, n->C, n->d_thg, n->d_xg);
-    N1_HIP(hipGetLastError());
+    SF_TRY_ERR(hipGetLastError());
     theta = n->d_thg;
     x = n->d_xg;
   }
@@ -313,7 +305,7 @@ int sf_nsf1_loss_grad(SfNsf1* n, const float* flat, const float* theta, const fl
   if (rc) return rc;
   hipLaunchKernelGGL(k_nsf1_train, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, n->d_q, theta, B, consts_of(*n), grad_scale, weights,
                      n->d_dq, loss, loss_sum);
-  N1_HIP(hipGetLastError());
+  SF_TRY_ERR(hipGetLastError());
   for (int t = 0; t < n->T; ++t)
     N1_RC(sf_mlp_backward(n->mlp, flat + (size_t)t * n->P_mlp, x, n->d_dq + (size_t)t * B * n->NP, B, grad + (size_t)t * n->P_mlp, st));
   return SF_OK;
@@ -326,17 +318,17 @@ int sf_nsf1_sample(SfNsf1* n, const float* flat, const float* x, long M, long S,
   if (rc) return rc;
   rc = conditioner(*n, flat, x, M, n->d_q, st, err);
   if (rc) return rc;
-  if (!n->d_cnt) N1_HIP(hipMalloc(&n->d_cnt, sizeof(unsigned int)));
-  N1_HIP(hipMemsetAsync(n->d_cnt, 0, sizeof(unsigned int), st));
+  if (!n->d_cnt) SF_TRY_ERR(hipMalloc(&n->d_cnt, sizeof(unsigned int)));
+  SF_TRY_ERR(hipMemsetAsync(n->d_cnt, 0, sizeof(unsigned int), st));
   // no ceiling asked for: 2^22 attempts per slot (the engine's other samplers give a galaxy up once 1e5 attempts of its open
   // slots brought no draw; a scalar slot that failed four million attempts is in the same state)
   const uint32_t cap = max_attempts > 0 ? (uint32_t)max_attempts : (1u << 22);
   hipLaunchKernelGGL(k_nsf1_sample, dim3((unsigned)((n_slots + 127) / 128)), dim3(128), 0, st, n->d_q, M, S, slots, n_slots, consts_of(*n),
                      lo, hi, k0, k1, slot_offset, cap, out, n_drawn, n->d_cnt);
-  N1_HIP(hipGetLastError());
+  SF_TRY_ERR(hipGetLastError());
   unsigned int h = 0;
-  N1_HIP(hipMemcpyAsync(&h, n->d_cnt, sizeof(h), hipMemcpyDeviceToHost, st));
-  N1_HIP(hipStreamSynchronize(st));
+  SF_TRY_ERR(hipMemcpyAsync(&h, n->d_cnt, sizeof(h), hipMemcpyDeviceToHost, st));
+  SF_TRY_ERR(hipStreamSynchronize(st));
   if (n_unfilled) *n_unfilled = (int64_t)h;
   return SF_OK;
 }
@@ -350,6 +342,6 @@ int sf_nsf1_acceptance(SfNsf1* n, const float* flat, const float* x, long M, lon
   const long tot = M * cnt;
   hipLaunchKernelGGL(k_nsf1_accept, dim3((unsigned)((tot + 127) / 128)), dim3(128), 0, st, n->d_q, M, cnt, consts_of(*n), lo, hi, k0, k1,
                      slot_offset, count);
-  N1_HIP(hipGetLastError());
+  SF_TRY_ERR(hipGetLastError());
   return SF_OK;
 }

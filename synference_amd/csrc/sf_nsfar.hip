@@ -930,14 +930,6 @@ __global__ __launch_bounds__(256) void k_ar_gather(const float* __restrict__ par
   grad[i] = (s0 + s1) + (s2 + s3);
 }
 
-#define AR_HIP(call)                                                        \
-  do {                                                                      \
-    hipError_t e_ = (call);                                                 \
-    if (e_ != hipSuccess) {                                                 \
-      err = std::string(#call) + ": " + hipGetErrorString(e_);              \
-      return SF_ERR_HIP;                                                    \
-    }                                                                       \
-  } while (0)
 
 ArArgs args_of(const SfNsfAr& n) {
   ArArgs a;
@@ -1170,26 +1162,26 @@ static int ar_ensure(SfNsfAr* n, std::string& err) {
     if (e != hipSuccess) return e;
     return hipMemcpy(dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
   };
-  AR_HIP(hipMalloc(&n->d_img, n->src.size() * sizeof(float)));
-  AR_HIP(up(n->d_src, n->src)); AR_HIP(up(n->d_perm, n->perm)); AR_HIP(up(n->d_ptype, n->ptype)); AR_HIP(up(n->d_tend, n->tend));
-  AR_HIP(up(n->d_ord, n->ord)); AR_HIP(up(n->d_dimof, n->dimof)); AR_HIP(up(n->d_dwave, n->dwave)); AR_HIP(up(n->d_xmean, n->h_xmean)); AR_HIP(up(n->d_xstd, n->h_xstd));
+  SF_TRY_ERR(hipMalloc(&n->d_img, n->src.size() * sizeof(float)));
+  SF_TRY_ERR(up(n->d_src, n->src)); SF_TRY_ERR(up(n->d_perm, n->perm)); SF_TRY_ERR(up(n->d_ptype, n->ptype)); SF_TRY_ERR(up(n->d_tend, n->tend));
+  SF_TRY_ERR(up(n->d_ord, n->ord)); SF_TRY_ERR(up(n->d_dimof, n->dimof)); SF_TRY_ERR(up(n->d_dwave, n->dwave)); SF_TRY_ERR(up(n->d_xmean, n->h_xmean)); SF_TRY_ERR(up(n->d_xstd, n->h_xstd));
   {   // live[i] = 1 where logical parameter i appears in an image (an unmasked weight or a bias): the entries a training workgroup writes
     std::vector<unsigned char> live((size_t)n->n_params, 0);
     for (int32_t v : n->src)
       if (v >= 0) live[(size_t)v] = 1;
-    AR_HIP(up(n->d_live, live));
+    SF_TRY_ERR(up(n->d_live, live));
   }
-  AR_HIP(hipMalloc(&n->d_ctr, 8 * sizeof(unsigned long long)));
-  AR_HIP(hipHostMalloc((void**)&n->h_ctr, 8 * sizeof(unsigned long long), hipHostMallocDefault));   // [0] cursor [1] unfilled [2] evaluations [3] rejected first attempts [4], [5] survivor counts
+  SF_TRY_ERR(hipMalloc(&n->d_ctr, 8 * sizeof(unsigned long long)));
+  SF_TRY_ERR(hipHostMalloc((void**)&n->h_ctr, 8 * sizeof(unsigned long long), hipHostMallocDefault));   // [0] cursor [1] unfilled [2] evaluations [3] rejected first attempts [4], [5] survivor counts
   {
     const std::vector<int32_t> none(n->src.size(), -1);
-    AR_HIP(up(n->d_none, none));
+    SF_TRY_ERR(up(n->d_none, none));
   }
   const size_t lds = (size_t)160 * 1024 - 1024;   // (k_ar_sample also has 768 static bytes)
-  AR_HIP(set_lds(k_ar_logprob<1>, lds)); AR_HIP(set_lds(k_ar_logprob<4>, lds)); AR_HIP(set_lds(k_ar_inverse, lds)); AR_HIP(set_lds(k_ar_sample, lds));
-  AR_HIP(set_lds(k_ar_train<1, false>, lds)); AR_HIP(set_lds(k_ar_train<4, false>, lds));
-  AR_HIP(set_lds(k_ar_train<1, true>, lds)); AR_HIP(set_lds(k_ar_train<4, true>, lds));
-  AR_HIP(set_lds(k_ar_find, lds)); AR_HIP(set_lds(k_ar_resolve, lds));
+  SF_TRY_ERR(set_lds(k_ar_logprob<1>, lds)); SF_TRY_ERR(set_lds(k_ar_logprob<4>, lds)); SF_TRY_ERR(set_lds(k_ar_inverse, lds)); SF_TRY_ERR(set_lds(k_ar_sample, lds));
+  SF_TRY_ERR(set_lds(k_ar_train<1, false>, lds)); SF_TRY_ERR(set_lds(k_ar_train<4, false>, lds));
+  SF_TRY_ERR(set_lds(k_ar_train<1, true>, lds)); SF_TRY_ERR(set_lds(k_ar_train<4, true>, lds));
+  SF_TRY_ERR(set_lds(k_ar_find, lds)); SF_TRY_ERR(set_lds(k_ar_resolve, lds));
   n->dev_ready = true;
   return SF_OK;
 }
@@ -1211,7 +1203,7 @@ int sf_nsfar_pack(SfNsfAr* n, const float* flat, hipStream_t st, std::string& er
   int rc = ar_ensure(n, err);
   if (rc) return rc;
   // (k_pack sums two gather tables; the second is "none" everywhere)
-  AR_HIP(sf_launch_pack(flat, n->d_src, n->d_none, n->d_img, (long)n->src.size(), st));
+  SF_TRY_ERR(sf_launch_pack(flat, n->d_src, n->d_none, n->d_img, (long)n->src.size(), st));
   return SF_OK;
 }
 
@@ -1219,17 +1211,17 @@ int sf_nsfar_log_prob(SfNsfAr* n, const float* theta, const float* x, long B, fl
 #ifdef SF_AR_TRACE
   {
     static unsigned long long* d_tr = nullptr;
-    if (!d_tr) AR_HIP(hipMalloc(&d_tr, 256 * 8));
-    AR_HIP(hipMemsetAsync(d_tr, 0, 256 * 8, st));
+    if (!d_tr) SF_TRY_ERR(hipMalloc(&d_tr, 256 * 8));
+    SF_TRY_ERR(hipMemsetAsync(d_tr, 0, 256 * 8, st));
     ArArgs aa = args_of(*n);
     aa.trace = d_tr;
     if (ar_waves(*n, 2) == 4)
       hipLaunchKernelGGL(k_ar_logprob<4>, dim3((unsigned)((B + 63) / 64)), dim3(256), sf_nsfar_lds_bytes(*n, 2, 4), st, aa, theta, x, B, out);
     else
       hipLaunchKernelGGL(k_ar_logprob<1>, dim3((unsigned)((B + 63) / 64)), dim3(64), sf_nsfar_lds_bytes(*n, 2, 1), st, aa, theta, x, B, out);
-    AR_HIP(hipStreamSynchronize(st));
+    SF_TRY_ERR(hipStreamSynchronize(st));
     unsigned long long h[256];
-    AR_HIP(hipMemcpy(h, d_tr, sizeof(h), hipMemcpyDeviceToHost));
+    SF_TRY_ERR(hipMemcpy(h, d_tr, sizeof(h), hipMemcpyDeviceToHost));
     static int calls = 0;
     if (++calls % 8 == 0) {
       fprintf(stderr, "[nsfar trace] B=%ld (units of 100 cycles since stamp 0):", B);
@@ -1243,20 +1235,20 @@ int sf_nsfar_log_prob(SfNsfAr* n, const float* theta, const float* x, long B, fl
     hipLaunchKernelGGL(k_ar_logprob<4>, dim3((unsigned)((B + 63) / 64)), dim3(256), sf_nsfar_lds_bytes(*n, 2, 4), st, args_of(*n), theta, x, B, out);
   else
     hipLaunchKernelGGL(k_ar_logprob<1>, dim3((unsigned)((B + 63) / 64)), dim3(64), sf_nsfar_lds_bytes(*n, 2, 1), st, args_of(*n), theta, x, B, out);
-  AR_HIP(hipGetLastError());
+  SF_TRY_ERR(hipGetLastError());
   return SF_OK;
 }
 
 int sf_nsfar_inverse(SfNsfAr* n, const float* z, const float* x, long B, float* theta, float* logdet, hipStream_t st, std::string& err) {
   hipLaunchKernelGGL(k_ar_inverse, dim3((unsigned)((B + 63) / 64)), dim3(64), sf_nsfar_lds_bytes(*n, 2, 1), st, args_of(*n), z, x, B, theta, logdet);
-  AR_HIP(hipGetLastError());
+  SF_TRY_ERR(hipGetLastError());
   return SF_OK;
 }
 
 int sf_nsfar_sample(SfNsfAr* n, const float* x, long M, long S, const uint32_t* slots, long n_slots, const float* lo, const float* hi,
                     uint32_t k0, uint32_t k1, unsigned long long slot_offset, int max_attempts, float* out, int32_t* n_drawn,
                     int32_t* count, int64_t* n_unfilled, hipStream_t st, std::string& err, hipEvent_t ev0, hipEvent_t ev1) {
-  AR_HIP(hipMemsetAsync(n->d_ctr, 0, 8 * sizeof(unsigned long long), st));
+  SF_TRY_ERR(hipMemsetAsync(n->d_ctr, 0, 8 * sizeof(unsigned long long), st));
   static int cus = 0;   // (asked once: the query costs more than a small sampling call)
   if (!cus) {
     int dev = 0;
@@ -1272,15 +1264,15 @@ int sf_nsfar_sample(SfNsfAr* n, const float* x, long M, long S, const uint32_t* 
   int32_t* g_try = nullptr;
   if (!count && max_attempts <= 0 && lo) {
     if ((size_t)(2 * M) > n->gal_cap) {
-      if (n->d_gal) AR_HIP(hipFree(n->d_gal));
+      if (n->d_gal) SF_TRY_ERR(hipFree(n->d_gal));
       n->d_gal = nullptr; n->gal_cap = 0;
-      AR_HIP(hipMalloc(&n->d_gal, (size_t)(2 * M) * sizeof(int32_t)));
+      SF_TRY_ERR(hipMalloc(&n->d_gal, (size_t)(2 * M) * sizeof(int32_t)));
       n->gal_cap = (size_t)(2 * M);
     }
-    AR_HIP(hipMemsetAsync(n->d_gal, 0, (size_t)(2 * M) * sizeof(int32_t), st));
+    SF_TRY_ERR(hipMemsetAsync(n->d_gal, 0, (size_t)(2 * M) * sizeof(int32_t), st));
     g_try = n->d_gal;
   }
-  if (ev0) AR_HIP(hipEventRecord(ev0, st));
+  if (ev0) SF_TRY_ERR(hipEventRecord(ev0, st));
   unsigned long long walk_R = 0, walk_C = 0;
   if (!count && n_slots >= 4096) {
     if (!slots && M > 1 && (long)(M * S) == n_slots) { walk_R = (unsigned long long)M; walk_C = (unsigned long long)S; }
@@ -1299,9 +1291,9 @@ int sf_nsfar_sample(SfNsfAr* n, const float* x, long M, long S, const uint32_t* 
     if ((size_t)n_slots > n->surv_cap) {
       (void)hipFree(n->d_surv[0]); (void)hipFree(n->d_surv[1]); (void)hipFree(n->d_best);
       n->d_surv[0] = n->d_surv[1] = n->d_best = nullptr; n->surv_cap = 0;
-      AR_HIP(hipMalloc(&n->d_surv[0], (size_t)n_slots * sizeof(uint32_t)));
-      AR_HIP(hipMalloc(&n->d_surv[1], (size_t)n_slots * sizeof(uint32_t)));
-      AR_HIP(hipMalloc(&n->d_best, (size_t)n_slots * sizeof(uint32_t)));
+      SF_TRY_ERR(hipMalloc(&n->d_surv[0], (size_t)n_slots * sizeof(uint32_t)));
+      SF_TRY_ERR(hipMalloc(&n->d_surv[1], (size_t)n_slots * sizeof(uint32_t)));
+      SF_TRY_ERR(hipMalloc(&n->d_best, (size_t)n_slots * sizeof(uint32_t)));
       n->surv_cap = (size_t)n_slots;
     }
   }
@@ -1310,22 +1302,22 @@ int sf_nsfar_sample(SfNsfAr* n, const float* x, long M, long S, const uint32_t* 
   const SfAr16Launch L = {x, S, slots, n_slots, lo, hi, k0, k1, slot_offset, cap, out, n_drawn, count, n->d_ctr,
                           reinterpret_cast<unsigned int*>(n->d_ctr + 1), g_try, g_try ? g_try + M : nullptr, walk_R, walk_C, window, n->d_surv[0], d_ns};
   if (tiles16) {
-    AR_HIP(sf_nsfar16_launch(*n, L, cus, st));
+    SF_TRY_ERR(sf_nsfar16_launch(*n, L, cus, st));
   } else {
     hipLaunchKernelGGL(k_ar_sample, dim3((unsigned)grid), dim3(64), lds, st, args_of(*n), x, S, slots, n_slots, lo, hi, k0, k1, slot_offset, cap, out,
                        n_drawn, count, n->d_ctr, reinterpret_cast<unsigned int*>(n->d_ctr + 1), g_try, g_try ? g_try + M : nullptr, walk_R, walk_C,
                        window, n->d_surv[0], d_ns);
   }
-  AR_HIP(hipGetLastError());
-  if (ev1) AR_HIP(hipEventRecord(ev1, st));
+  SF_TRY_ERR(hipGetLastError());
+  if (ev1) SF_TRY_ERR(hipEventRecord(ev1, st));
   unsigned long long* h = n->h_ctr;   // (pinned: a read-back into pageable memory is a staged, host-synchronous copy)
   for (int i = 0; i < 8; ++i) h[i] = 0;
   if (rounds) {
     int cur = 0;
     uint32_t base = window;
     for (;;) {
-      AR_HIP(hipMemcpyAsync(h, n->d_ctr, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-      AR_HIP(hipStreamSynchronize(st));
+      SF_TRY_ERR(hipMemcpyAsync(h, n->d_ctr, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+      SF_TRY_ERR(hipStreamSynchronize(st));
       const unsigned int ns = reinterpret_cast<const unsigned int*>(h + 4)[cur];
       if (ns == 0 || base >= cap) break;
       uint32_t A = 64;
@@ -1333,11 +1325,11 @@ int sf_nsfar_sample(SfNsfAr* n, const float* x, long M, long S, const uint32_t* 
       if ((uint64_t)base + A > cap) A = (uint32_t)(((uint64_t)cap - base + 63u) / 64u * 64u);
       const uint32_t att_end = (uint64_t)base + A > cap ? cap : base + A;
       const uint32_t chunks = A / 64u;
-      AR_HIP(hipMemsetAsync(n->d_best, 0xff, (size_t)ns * sizeof(uint32_t), st));
-      AR_HIP(hipMemsetAsync(d_ns + (cur ^ 1), 0, sizeof(unsigned int), st));
+      SF_TRY_ERR(hipMemsetAsync(n->d_best, 0xff, (size_t)ns * sizeof(uint32_t), st));
+      SF_TRY_ERR(hipMemsetAsync(d_ns + (cur ^ 1), 0, sizeof(unsigned int), st));
       if (tiles16) {
-        AR_HIP(sf_nsfar16_find(*n, L, n->d_surv[cur], ns, base, chunks, att_end, n->d_best, n->d_ctr, st));
-        AR_HIP(sf_nsfar16_resolve(*n, L, n->d_surv[cur], ns, n->d_best, att_end, att_end - base, n->d_surv[cur ^ 1], d_ns + (cur ^ 1), st));
+        SF_TRY_ERR(sf_nsfar16_find(*n, L, n->d_surv[cur], ns, base, chunks, att_end, n->d_best, n->d_ctr, st));
+        SF_TRY_ERR(sf_nsfar16_resolve(*n, L, n->d_surv[cur], ns, n->d_best, att_end, att_end - base, n->d_surv[cur ^ 1], d_ns + (cur ^ 1), st));
       } else {
         hipLaunchKernelGGL(k_ar_find, dim3(ns * chunks), dim3(64), lds, st, args_of(*n), x, S, n->d_surv[cur], ns, base, chunks, att_end, lo, hi, k0, k1,
                            slot_offset, n->d_best, n->d_ctr);
@@ -1345,29 +1337,29 @@ int sf_nsfar_sample(SfNsfAr* n, const float* x, long M, long S, const uint32_t* 
                            k0, k1, slot_offset, out, n_drawn, g_try, g_try ? g_try + M : nullptr, att_end - base, n->d_surv[cur ^ 1], d_ns + (cur ^ 1),
                            reinterpret_cast<unsigned int*>(n->d_ctr + 1));
       }
-      AR_HIP(hipGetLastError());
+      SF_TRY_ERR(hipGetLastError());
       base = att_end;
       cur ^= 1;
     }
     const unsigned int left = reinterpret_cast<const unsigned int*>(h + 4)[cur];
     if (left > 0) {   // (the ceiling was reached with slots still open: NaN rows)
-      AR_HIP(hipMemsetAsync(n->d_best, 0xff, (size_t)left * sizeof(uint32_t), st));
+      SF_TRY_ERR(hipMemsetAsync(n->d_best, 0xff, (size_t)left * sizeof(uint32_t), st));
       if (tiles16) {
         SfAr16Launch Lf = L;
         Lf.g_try = nullptr; Lf.g_acc = nullptr;
-        AR_HIP(sf_nsfar16_resolve(*n, Lf, n->d_surv[cur], left, n->d_best, cap, 0u, n->d_surv[cur ^ 1], d_ns + (cur ^ 1), st));
+        SF_TRY_ERR(sf_nsfar16_resolve(*n, Lf, n->d_surv[cur], left, n->d_best, cap, 0u, n->d_surv[cur ^ 1], d_ns + (cur ^ 1), st));
       } else {
         hipLaunchKernelGGL(k_ar_resolve, dim3((left + 63u) / 64u), dim3(64), lds, st, args_of(*n), x, S, n->d_surv[cur], left, n->d_best, cap, cap, lo, hi,
                            k0, k1, slot_offset, out, n_drawn, (int32_t*)nullptr, (int32_t*)nullptr, 0u, n->d_surv[cur ^ 1], d_ns + (cur ^ 1),
                            reinterpret_cast<unsigned int*>(n->d_ctr + 1));
       }
-      AR_HIP(hipGetLastError());
+      SF_TRY_ERR(hipGetLastError());
     }
-    AR_HIP(hipMemcpyAsync(h, n->d_ctr, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    AR_HIP(hipStreamSynchronize(st));
+    SF_TRY_ERR(hipMemcpyAsync(h, n->d_ctr, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    SF_TRY_ERR(hipStreamSynchronize(st));
   } else if (n_unfilled) {
-    AR_HIP(hipMemcpyAsync(h, n->d_ctr, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    AR_HIP(hipStreamSynchronize(st));
+    SF_TRY_ERR(hipMemcpyAsync(h, n->d_ctr, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    SF_TRY_ERR(hipStreamSynchronize(st));
   }
   if (n_unfilled) *n_unfilled = (int64_t)(unsigned int)h[1];
   n->last_evals = (double)h[2];
@@ -1381,14 +1373,14 @@ int sf_nsfar_loss_grad(SfNsfAr* n, const float* flat, const float* theta, const 
   int rc = sf_nsfar_pack(n, flat, st, err);
   if (rc) return rc;
   if (B == 0) {
-    AR_HIP(hipMemsetAsync(grad, 0, (size_t)n->n_params * sizeof(float), st));
+    SF_TRY_ERR(hipMemsetAsync(grad, 0, (size_t)n->n_params * sizeof(float), st));
     return SF_OK;
   }
   const size_t need = (size_t)B * n->T * n->D;
   if (need > n->ustash_cap) {
-    if (n->d_ustash) AR_HIP(hipFree(n->d_ustash));
+    if (n->d_ustash) SF_TRY_ERR(hipFree(n->d_ustash));
     n->d_ustash = nullptr; n->ustash_cap = 0;
-    AR_HIP(hipMalloc(&n->d_ustash, need * sizeof(float)));
+    SF_TRY_ERR(hipMalloc(&n->d_ustash, need * sizeof(float)));
     n->ustash_cap = need;
   }
   // Gradient accumulation: one partial per 64-row chunk + k_ar_gather (plain stores, summed in chunk order) while the partials fit
@@ -1404,24 +1396,24 @@ int sf_nsfar_loss_grad(SfNsfAr* n, const float* flat, const float* theta, const 
   const long nwg = n_chunks;
   if (part) {
     if (part_bytes > n->gpart_cap) {
-      if (n->d_gpart) AR_HIP(hipFree(n->d_gpart));
+      if (n->d_gpart) SF_TRY_ERR(hipFree(n->d_gpart));
       n->d_gpart = nullptr; n->gpart_cap = 0;
-      AR_HIP(hipMalloc(&n->d_gpart, part_bytes));
+      SF_TRY_ERR(hipMalloc(&n->d_gpart, part_bytes));
       n->gpart_cap = part_bytes;
     }
   } else {
-    AR_HIP(hipMemsetAsync(grad, 0, (size_t)n->n_params * sizeof(float), st));
+    SF_TRY_ERR(hipMemsetAsync(grad, 0, (size_t)n->n_params * sizeof(float), st));
   }
   float* gdst = part ? n->d_gpart : grad;
   const long gstride = part ? (long)n->n_params : 0;
   ArArgs aa = args_of(*n);
 #ifdef SF_AR_TRACE
   static unsigned long long* d_tr = nullptr;
-  if (!d_tr) AR_HIP(hipMalloc(&d_tr, 256 * 8));
-  AR_HIP(hipMemsetAsync(d_tr, 0, 256 * 8, st));
+  if (!d_tr) SF_TRY_ERR(hipMalloc(&d_tr, 256 * 8));
+  SF_TRY_ERR(hipMemsetAsync(d_tr, 0, 256 * 8, st));
   aa.trace = d_tr;
 #endif
-  if (ev0) AR_HIP(hipEventRecord(ev0, st));
+  if (ev0) SF_TRY_ERR(hipEventRecord(ev0, st));
   const int nwv = ar_waves(*n, 3);
   const dim3 grid((unsigned)nwg), block(64 * nwv);
   const size_t lds = sf_nsfar_lds_bytes(*n, 3, nwv);
@@ -1432,17 +1424,17 @@ int sf_nsfar_loss_grad(SfNsfAr* n, const float* flat, const float* theta, const 
     if (part) hipLaunchKernelGGL((k_ar_train<1, true>), grid, block, lds, st, aa, theta, x, idx, B, grad_scale, weights, loss, loss_sum, gdst, gstride, n->d_ustash);
     else hipLaunchKernelGGL((k_ar_train<1, false>), grid, block, lds, st, aa, theta, x, idx, B, grad_scale, weights, loss, loss_sum, gdst, gstride, n->d_ustash);
   }
-  AR_HIP(hipGetLastError());
-  if (ev1) AR_HIP(hipEventRecord(ev1, st));
+  SF_TRY_ERR(hipGetLastError());
+  if (ev1) SF_TRY_ERR(hipEventRecord(ev1, st));
   if (part) {
     hipLaunchKernelGGL(k_ar_gather, dim3((unsigned)((n->n_params + 255) / 256)), dim3(256), 0, st, n->d_gpart, gstride, (int)nwg, n->d_live, grad, (long)n->n_params);
-    AR_HIP(hipGetLastError());
+    SF_TRY_ERR(hipGetLastError());
   }
 #ifdef SF_AR_TRACE
   {
-    AR_HIP(hipStreamSynchronize(st));
+    SF_TRY_ERR(hipStreamSynchronize(st));
     unsigned long long h[256];
-    AR_HIP(hipMemcpy(h, d_tr, sizeof(h), hipMemcpyDeviceToHost));
+    SF_TRY_ERR(hipMemcpy(h, d_tr, sizeof(h), hipMemcpyDeviceToHost));
     static int calls = 0;
     if (++calls % 8 == 0) {
       fprintf(stderr, "[nsfar train trace] B=%ld (units of 100 cycles since stamp 0):", B);

@@ -31,10 +31,10 @@
 // adds the splits in ascending order in fp64.  The split count depends on the shapes only: two calls give the same bits.
 #include <hip/hip_runtime.h>
 
-#include <mutex>
 #include <string>
 
 #include "sf_internal.h"
+#include "sf_scratch.h"
 
 #define SF_OOD_CMAX 64
 #define SF_OOD_KMAX 64
@@ -338,14 +338,7 @@ __global__ __launch_bounds__(256) void k_kde_merge(const double* __restrict__ pa
 
 // ---- host ----------------------------------------------------------------------------------------------------------------
 namespace {
-struct SfOodWs {
-  void* p = nullptr;
-  size_t cap = 0;
-  hipEvent_t ev = nullptr;
-  bool used = false;
-};
-std::mutex g_ood_mu;
-SfOodWs g_ood_ws[16];
+SfScratch g_ood_scratch;   // sf_scratch.h: one for both entry points
 
 struct SfOodPlan { int QT, S, n_qt, gs; long split_len, gl; unsigned magic; size_t lds; };
 
@@ -369,33 +362,6 @@ SfOodPlan sf_ood_plan(int64_t N, int32_t C, int64_t M, int k) {
   const int CP = (C + 3) & ~3;
   pl.lds = (size_t)SF_OOD_CH * CP * 4 + (size_t)k * pl.QT * 8;
   return pl;
-}
-
-// scratch of the device for this call; the call waits for the previous one that used it
-int sf_ood_scratch(const char* who, hipStream_t st, size_t need, SfOodWs** out) {
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess || dev < 0 || dev >= 16) {
-    sf_set_error(std::string(who) + ": no usable device: " + hipGetErrorString(e));
-    return SF_ERR_NO_DEVICE;
-  }
-  SfOodWs& ws = g_ood_ws[dev];
-  auto fail = [&](const char* what, hipError_t err) {
-    sf_set_error(std::string(who) + ": " + what + ": " + hipGetErrorString(err));
-    return SF_ERR_HIP;
-  };
-  if (!ws.ev && (e = hipEventCreateWithFlags(&ws.ev, hipEventDisableTiming)) != hipSuccess) return fail("event", e);
-  if (ws.cap < need) {
-    if (ws.p && (e = hipFree(ws.p)) != hipSuccess) return fail("hipFree", e);   // waits for the work that uses it
-    ws.p = nullptr;
-    ws.cap = 0;
-    if ((e = hipMalloc(&ws.p, need)) != hipSuccess) return fail("hipMalloc", e);
-    ws.cap = need;
-  }
-  if (ws.used && (e = hipStreamWaitEvent(st, ws.ev, 0)) != hipSuccess) return fail("hipStreamWaitEvent", e);
-  ws.used = true;
-  *out = &ws;
-  return SF_OK;
 }
 
 template <template <int> class L, class... A>
@@ -459,15 +425,15 @@ extern "C" int sf_knn(const float* base, int64_t N, int32_t C, const float* quer
   if (M == 0) return SF_OK;
   hipStream_t st = (hipStream_t)stream;
   const SfOodPlan pl = sf_ood_plan(N, C, M, k);
-  std::lock_guard<std::mutex> lock(g_ood_mu);
-  SfOodWs* ws = nullptr;
   const int G = pl.S * pl.gs;   // <= 256 + 4 * 64 - 1
-  const size_t b_part = pl.S > 1 ? (((size_t)M * pl.S * k * 8 + 255) & ~(size_t)255) : 256;
-  const size_t b_gmin = ((size_t)M * G * 4 + 255) & ~(size_t)255, b_b0 = ((size_t)M * 4 + 255) & ~(size_t)255;
-  if (int rc = sf_ood_scratch("sf_knn", st, b_part + (G ? b_gmin + b_b0 : 0), &ws)) return rc;
-  unsigned long long* part = (unsigned long long*)ws->p;
-  float* gmin = (float*)((char*)ws->p + b_part);
-  float* b0 = G ? (float*)((char*)ws->p + b_part + b_gmin) : nullptr;
+  SfScratchCall ws(g_ood_scratch, "sf_knn", st);
+  const int sub_part = ws.add(pl.S > 1 ? (size_t)M * pl.S * k * 8 : 256);
+  const int sub_gmin = G ? ws.add((size_t)M * G * 4) : -1, sub_b0 = G ? ws.add((size_t)M * 4) : -1;
+  if (int rc = ws.reserve()) return rc;
+  unsigned long long* part = ws.get<unsigned long long>(sub_part);
+  float* gmin = G ? ws.get<float>(sub_gmin) : nullptr;
+  float* b0 = G ? ws.get<float>(sub_b0) : nullptr;
+  if (int rc = ws.check()) return rc;
   const int CP = (C + 3) & ~3;
   const dim3 grid((unsigned)pl.n_qt, (unsigned)pl.S);
   if (G) {
@@ -479,13 +445,9 @@ extern "C" int sf_knn(const float* base, int64_t N, int32_t C, const float* quer
                                (int)exclude_self, (long)self_offset, pl.split_len, pl.S, (const float*)b0, part, d2, idx);
   if (pl.S > 1)
     hipLaunchKernelGGL(k_knn_merge, dim3((unsigned)M), dim3(256), 0, st, (const unsigned long long*)part, pl.S, (int)k, d2, idx);
-  hipError_t e = hipGetLastError();
-  (void)hipEventRecord(ws->ev, st);
-  if (e != hipSuccess) {
-    sf_set_error(std::string("sf_knn: launch: ") + hipGetErrorString(e));
-    return SF_ERR_HIP;
-  }
-  return SF_OK;
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return ws.fail("launch", e);
+  return ws.finish();
 }
 
 extern "C" int sf_kde_logsumexp(const float* base_w, int64_t N, int32_t C, const float* query_w, int64_t M, double* out,
@@ -502,17 +464,15 @@ extern "C" int sf_kde_logsumexp(const float* base_w, int64_t N, int32_t C, const
   hipStream_t st = (hipStream_t)stream;
   SfOodPlan pl = sf_ood_plan(N, C, M, 1);
   pl.lds = (size_t)SF_OOD_CH * ((C + 3) & ~3) * 4;
-  std::lock_guard<std::mutex> lock(g_ood_mu);
-  SfOodWs* ws = nullptr;
-  if (int rc = sf_ood_scratch("sf_kde_logsumexp", st, (size_t)M * pl.S * 16, &ws)) return rc;
+  SfScratchCall ws(g_ood_scratch, "sf_kde_logsumexp", st);
+  const int sub_part = ws.add((size_t)M * pl.S * 16);
+  if (int rc = ws.reserve()) return rc;
+  double* part = ws.get<double>(sub_part);
+  if (int rc = ws.check()) return rc;
   sf_ood_dispatch<SfKdeLaunch>((C + 3) & ~3, dim3((unsigned)pl.n_qt, (unsigned)pl.S), pl.QT, pl.lds, st, base_w, (long)N, (int)C,
-                               pl.magic, query_w, (long)M, pl.split_len, pl.S, (double*)ws->p);
-  hipLaunchKernelGGL(k_kde_merge, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, (const double*)ws->p, (long)M, pl.S, out);
-  hipError_t e = hipGetLastError();
-  (void)hipEventRecord(ws->ev, st);
-  if (e != hipSuccess) {
-    sf_set_error(std::string("sf_kde_logsumexp: launch: ") + hipGetErrorString(e));
-    return SF_ERR_HIP;
-  }
-  return SF_OK;
+                               pl.magic, query_w, (long)M, pl.split_len, pl.S, part);
+  hipLaunchKernelGGL(k_kde_merge, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, (const double*)part, (long)M, pl.S, out);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return ws.fail("launch", e);
+  return ws.finish();
 }

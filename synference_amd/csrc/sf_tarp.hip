@@ -13,11 +13,12 @@
 // occurrence owns its cell (plain stores), and the curve is built from integer prefix sums: two calls give the same bits.
 #include <hip/hip_runtime.h>
 
-#include <mutex>
 #include <string>
 
+#include "sf_block.h"
 #include "sf_internal.h"
 #include "sf_rng.h"
+#include "sf_scratch.h"
 
 #define SF_TARP_DMAX 16
 #define SF_TARP_SMAX 8192
@@ -42,30 +43,7 @@ __global__ void k_tarp_resample(int N, long cells, int boot, uint32_t k0, uint32
   }
 }
 
-// ---- 2. exclusive scan of the row counts (one workgroup; the total is B * N < 2^31) --------------------------------
-__global__ __launch_bounds__(1024) void k_tarp_scan(const int32_t* __restrict__ cnt, int N, int32_t* __restrict__ offs) {
-  __shared__ int part[1024];
-  const int tid = threadIdx.x;
-  const int chunk = (N + 1023) / 1024;
-  const long lo = (long)tid * chunk;
-  const long hi = lo + chunk < N ? lo + chunk : N;
-  int s = 0;
-  for (long i = lo; i < hi; ++i) s += cnt[i];
-  part[tid] = s;
-  __syncthreads();
-  for (int o = 1; o < 1024; o <<= 1) {
-    const int v = tid >= o ? part[tid - o] : 0;
-    __syncthreads();
-    part[tid] += v;
-    __syncthreads();
-  }
-  int run = part[tid] - s;
-  for (long i = lo; i < hi; ++i) {
-    offs[i] = run;
-    run += cnt[i];
-  }
-  if (tid == 1023) offs[N] = part[1023];
-}
+// ---- 2. exclusive scan of the row counts: sf_launch_exclusive_scan_i32 (the total is B * N < 2^31) ----------------------
 
 // ---- 3. occurrence list grouped by row (rowcnt counts down to 0; the order inside a row does not matter) -----------
 __global__ void k_tarp_scatter(long cells, const int32_t* __restrict__ idx, const int32_t* __restrict__ offs,
@@ -234,15 +212,8 @@ __global__ __launch_bounds__(256) void k_tarp_curve(const int32_t* __restrict__ 
   const int lo = tid * chunk, hi = lo + chunk < S + 2 ? lo + chunk : S + 2;
   int s = 0;
   for (int k = lo; k < hi; ++k) s += h[k];
-  part[tid] = s;
-  __syncthreads();
-  for (int o = 1; o < 256; o <<= 1) {
-    const int v = tid >= o ? part[tid - o] : 0;
-    __syncthreads();
-    part[tid] += v;
-    __syncthreads();
-  }
-  int run = part[tid] - s;
+  int tot;
+  int run = sf_block_exscan<256>(s, part, &tot);
   for (int k = lo; k < hi; ++k) {
     const int c = h[k];
     h[k] = run;
@@ -272,18 +243,9 @@ __global__ __launch_bounds__(256) void k_tarp_curve(const int32_t* __restrict__ 
   }
 }
 
-// ---- scratch: one growing buffer per device; a call on another stream waits for the previous call's last kernel ----
+// ---- scratch: sf_scratch.h ------------------------------------------------------------------------------------------
 namespace {
-struct SfTarpWs {
-  void* p = nullptr;
-  size_t cap = 0;
-  hipEvent_t ev = nullptr;
-  bool used = false;
-};
-std::mutex g_tarp_mu;
-SfTarpWs g_tarp_ws[16];
-
-inline size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
+SfScratch g_tarp_scratch;
 
 template <int METRIC>
 hipError_t launch_count(int D, dim3 grid, size_t lds, hipStream_t st, const float* samples, const float* theta,
@@ -326,55 +288,33 @@ extern "C" int sf_tarp_coverage(const float* samples, const float* theta, int64_
   const int boot = num_bootstrap > 0 ? 1 : 0;
   const size_t cells = (size_t)(B * N);
   hipStream_t st = (hipStream_t)stream;
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess || dev < 0 || dev >= 16) {
-    sf_set_error(std::string("sf_tarp_coverage: no usable device: ") + hipGetErrorString(e));
-    return SF_ERR_NO_DEVICE;
-  }
   // scratch: [idx] [counts] rowcnt offs occ lowinv
   const bool own_idx = !(boot && boot_idx), own_counts = !counts;
-  const size_t b_cells = up256(cells * 4), b_rows = up256(((size_t)N + 1) * 4);
-  const size_t b_norm = norm_axis == 0 ? up256((size_t)B * D * 2 * 4) : 0;
-  const size_t need = (own_idx ? b_cells : 0) + (own_counts ? b_cells : 0) + 2 * b_rows + b_cells + b_norm;
-
-  std::lock_guard<std::mutex> lock(g_tarp_mu);
-  SfTarpWs& ws = g_tarp_ws[dev];
-  auto fail = [&](const char* what, hipError_t err) {
-    sf_set_error(std::string("sf_tarp_coverage: ") + what + ": " + hipGetErrorString(err));
-    return SF_ERR_HIP;
-  };
-  if (!ws.ev && (e = hipEventCreateWithFlags(&ws.ev, hipEventDisableTiming)) != hipSuccess) return fail("event", e);
-  if (ws.cap < need) {
-    if (ws.p && (e = hipFree(ws.p)) != hipSuccess) return fail("hipFree", e);  // waits for the work that uses it
-    ws.p = nullptr;
-    ws.cap = 0;
-    ws.used = false;
-    if ((e = hipMalloc(&ws.p, need)) != hipSuccess) return fail("hipMalloc", e);
-    ws.cap = need;
-  }
-  if (ws.used && (e = hipStreamWaitEvent(st, ws.ev, 0)) != hipSuccess) return fail("hipStreamWaitEvent", e);
-  char* p = (char*)ws.p;
-  auto take = [&](size_t bytes) { char* q = p; p += bytes; return q; };
-  int32_t* idx = own_idx ? (int32_t*)take(b_cells) : boot_idx;
-  int32_t* cnt = own_counts ? (int32_t*)take(b_cells) : counts;
-  int32_t* rowcnt = (int32_t*)take(b_rows);
-  int32_t* offs = (int32_t*)take(b_rows);
-  int32_t* occ = (int32_t*)take(b_cells);
-  float* lowinv = norm_axis == 0 ? (float*)take(b_norm) : nullptr;
+  SfScratchCall ws(g_tarp_scratch, "sf_tarp_coverage", st);
+  const int sub_idx = own_idx ? ws.add(cells * 4) : -1, sub_cnt = own_counts ? ws.add(cells * 4) : -1;
+  const int sub_rowcnt = ws.add(((size_t)N + 1) * 4), sub_offs = ws.add(((size_t)N + 1) * 4), sub_occ = ws.add(cells * 4);
+  const int sub_norm = norm_axis == 0 ? ws.add((size_t)B * D * 2 * 4) : -1;
+  if (int rc = ws.reserve()) return rc;
+  int32_t* idx = own_idx ? ws.get<int32_t>(sub_idx) : boot_idx;
+  int32_t* cnt = own_counts ? ws.get<int32_t>(sub_cnt) : counts;
+  int32_t* rowcnt = ws.get<int32_t>(sub_rowcnt);
+  int32_t* offs = ws.get<int32_t>(sub_offs);
+  int32_t* occ = ws.get<int32_t>(sub_occ);
+  float* lowinv = norm_axis == 0 ? ws.get<float>(sub_norm) : nullptr;
+  if (int rc = ws.check()) return rc;
+  hipError_t e;
 
   const uint32_t s_lo = (uint32_t)seed, s_hi = (uint32_t)(seed >> 32);
-  if ((e = hipMemsetAsync(rowcnt, 0, ((size_t)N + 1) * 4, st)) != hipSuccess) return fail("hipMemsetAsync", e);
-  ws.used = true;
+  if ((e = hipMemsetAsync(rowcnt, 0, ((size_t)N + 1) * 4, st)) != hipSuccess) return ws.fail("hipMemsetAsync", e);
   size_t blocks = (cells + 255) / 256;
   blocks = blocks > 4096 ? 4096 : blocks;
   hipLaunchKernelGGL(k_tarp_resample, dim3((unsigned)blocks), dim3(256), 0, st, (int)N, (long)cells, boot, s_lo, s_hi ^ 3u, idx,
                      rowcnt);
-  hipLaunchKernelGGL(k_tarp_scan, dim3(1), dim3(1024), 0, st, rowcnt, (int)N, offs);
+  if ((e = sf_launch_exclusive_scan_i32(rowcnt, (int)N, offs, offs + N, st)) != hipSuccess) return ws.fail("launch", e);
   hipLaunchKernelGGL(k_tarp_scatter, dim3((unsigned)blocks), dim3(256), 0, st, (long)cells, idx, offs, rowcnt, occ);
   if (norm_axis == 0)
     hipLaunchKernelGGL(k_tarp_minmax, dim3((unsigned)B), dim3(256), 0, st, theta, idx, (int)N, (int)D, lowinv);
-  if ((e = hipGetLastError()) != hipSuccess) { (void)hipEventRecord(ws.ev, st); return fail("launch", e); }
+  if ((e = hipGetLastError()) != hipSuccess) return ws.fail("launch", e);
   int TS = (SF_TARP_TILE_FLOATS / D) / 64 * 64;                  // draws per tile, whole groups of 64
   const int S64 = (int)((S + 63) / 64 * 64);
   TS = TS > S64 ? S64 : TS;
@@ -383,12 +323,9 @@ extern "C" int sf_tarp_coverage(const float* samples, const float* theta, int64_
                                     TS, offs, occ, s_lo, s_hi ^ 4u, cnt)
                   : launch_count<1>(D, dim3((unsigned)N), lds, st, samples, theta, references, lowinv, norm_axis, (int)N, (int)S,
                                     TS, offs, occ, s_lo, s_hi ^ 4u, cnt);
-  if (e != hipSuccess) { (void)hipEventRecord(ws.ev, st); return fail("k_tarp_count", e); }
+  if (e != hipSuccess) return ws.fail("k_tarp_count", e);
   hipLaunchKernelGGL(k_tarp_curve, dim3((unsigned)B), dim3(256), ((size_t)S + 2) * sizeof(int), st, cnt, (int)N, (int)S,
                      (int)num_alpha_bins, (int)B, ecp, alpha);
-  e = hipGetLastError();
-  hipError_t e2 = hipEventRecord(ws.ev, st);
-  if (e != hipSuccess) return fail("k_tarp_curve", e);
-  if (e2 != hipSuccess) return fail("hipEventRecord", e2);
-  return SF_OK;
+  if ((e = hipGetLastError()) != hipSuccess) return ws.fail("k_tarp_curve", e);
+  return ws.finish();
 }

@@ -265,14 +265,6 @@ __global__ void k_train_prep(const float* __restrict__ flat, const int32_t* __re
   hipError_t sf_launch_nsf_train_h##H(const SfDev&, const SfTrainArgs&, hipStream_t);
 SF_TDECL(1) SF_TDECL(2) SF_TDECL(3) SF_TDECL(4)
 
-#define SF_TRY(call)                                                         \
-  do {                                                                       \
-    hipError_t e_ = (call);                                                  \
-    if (e_ != hipSuccess) {                                                  \
-      err = std::string(#call) + ": " + hipGetErrorString(e_);               \
-      return SF_ERR_HIP;                                                     \
-    }                                                                        \
-  } while (0)
 
 // The epoch loop (sf_flow_train_epoch) asks the gather for the per-block shares of |grad|^2: returns the buffer (grown on demand)
 // and notes how many shares the gradient of THIS call comes with; null when nobody asked or the buffer cannot be had.
@@ -304,7 +296,7 @@ int sf_train_loss_grad(sf_flow* f, const float* flat, const float* theta, const 
     if (dctx) { err = "the autoregressive NSF has no context-gradient path"; return SF_ERR_INVALID; }
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (f->profiling) {
-      if (!f->ev_train[0]) { SF_TRY(hipEventCreate(&f->ev_train[0])); SF_TRY(hipEventCreate(&f->ev_train[1])); }
+      if (!f->ev_train[0]) { SF_TRY_ERR(hipEventCreate(&f->ev_train[0])); SF_TRY_ERR(hipEventCreate(&f->ev_train[1])); }
       e0 = f->ev_train[0]; e1 = f->ev_train[1];
     }
     const int rc = sf_nsfar_loss_grad(f->nsfar, flat, theta, x, idx, B, grad_scale, weights, loss, loss_sum, grad, st, err, e0, e1);
@@ -372,15 +364,15 @@ int sf_train_loss_grad(sf_flow* f, const float* flat, const float* theta, const 
     bool use_fix = coop_nsf ? nsf_mode != 0 : sf_trainc_fix(grid, (long)L.n_gradC);
     if (!f->d_gsrcC) use_fix = false;
     if (use_fix && !f->d_gfixC) {
-      SF_TRY(hipMalloc(&f->d_gfixC, (size_t)SF_FIX_REPLICAS * (size_t)L.n_gradC * sizeof(long long)));
+      SF_TRY_ERR(hipMalloc(&f->d_gfixC, (size_t)SF_FIX_REPLICAS * (size_t)L.n_gradC * sizeof(long long)));
     }
-    if (use_fix) SF_TRY(hipMemsetAsync(f->d_gfixC, 0, (size_t)SF_FIX_REPLICAS * (size_t)L.n_gradC * sizeof(long long), st));
+    if (use_fix) SF_TRY_ERR(hipMemsetAsync(f->d_gfixC, 0, (size_t)SF_FIX_REPLICAS * (size_t)L.n_gradC * sizeof(long long), st));
     const int n_part = use_fix ? 1 : grid;   // (fix: d_gpartC is only the base the job descriptors count from)
     const size_t need = (size_t)n_part * (size_t)L.n_gradC;
     if (need > f->gpartC_cap) {
-      if (f->d_gpartC) SF_TRY(hipFree(f->d_gpartC));
+      if (f->d_gpartC) SF_TRY_ERR(hipFree(f->d_gpartC));
       f->d_gpartC = nullptr; f->gpartC_cap = 0;
-      SF_TRY(hipMalloc(&f->d_gpartC, need * sizeof(float)));
+      SF_TRY_ERR(hipMalloc(&f->d_gpartC, need * sizeof(float)));
       f->gpartC_cap = need;
     }
     {
@@ -397,19 +389,19 @@ int sf_train_loss_grad(sf_flow* f, const float* flat, const float* theta, const 
                          n1, (const int32_t*)nullptr, (const int32_t*)nullptr, (float*)nullptr, 0L, (float*)nullptr, 0,
                          dctx, n4, f->d_s16a, f->d_s16b, f->d_packed16, n5, f->d_s16B, f->d_packed16B, n6, f->d_sC1, f->d_sC2,
                          f->d_imgC, n7);
-      SF_TRY(hipGetLastError());
+      SF_TRY_ERR(hipGetLastError());
       f->packed16_stale = lite;
       f->packed_stale = lite;
       f->wp_stale = true;
     }
-    if (L.n_packedB > 0) SF_TRY(sf_launch_pack_bf16(flat, f->d_bsrc, f->d_packedB, (long)L.n_packedB, st));
+    if (L.n_packedB > 0) SF_TRY_ERR(sf_launch_pack_bf16(flat, f->d_bsrc, f->d_packedB, (long)L.n_packedB, st));
     if (coop_nsf) {
       const long n_chunks = (B + 31) / 32;
       const size_t ust_need = (size_t)n_chunks * 32 * (size_t)L.dev.T * 16;
       if (ust_need > f->ustash_cap) {
-        if (f->d_ustash) SF_TRY(hipFree(f->d_ustash));
+        if (f->d_ustash) SF_TRY_ERR(hipFree(f->d_ustash));
         f->d_ustash = nullptr; f->ustash_cap = 0;
-        SF_TRY(hipMalloc(&f->d_ustash, ust_need * sizeof(float)));
+        SF_TRY_ERR(hipMalloc(&f->d_ustash, ust_need * sizeof(float)));
         f->ustash_cap = ust_need;
       }
       const SfDev& v = L.dev;
@@ -429,19 +421,19 @@ int sf_train_loss_grad(sf_flow* f, const float* flat, const float* theta, const 
       a.trace = nullptr;
 #endif
       if (f->profiling) {
-        if (!f->ev_train[0]) { SF_TRY(hipEventCreate(&f->ev_train[0])); SF_TRY(hipEventCreate(&f->ev_train[1])); }
-        SF_TRY(hipEventRecord(f->ev_train[0], st));
+        if (!f->ev_train[0]) { SF_TRY_ERR(hipEventCreate(&f->ev_train[0])); SF_TRY_ERR(hipEventCreate(&f->ev_train[1])); }
+        SF_TRY_ERR(hipEventRecord(f->ev_train[0], st));
       }
-      SF_TRY(sf_launch_nsf_trainc(a, grid, st));
+      SF_TRY_ERR(sf_launch_nsf_trainc(a, grid, st));
       if (f->profiling) {
-        SF_TRY(hipEventRecord(f->ev_train[1], st));
+        SF_TRY_ERR(hipEventRecord(f->ev_train[1], st));
         f->ev_train_valid = true;
       }
       if (use_fix && nsf_mode == 2)   // float replicas: the partial gather over SF_FIX_REPLICAS images
-        SF_TRY(sf_launch_gather_c2(reinterpret_cast<const float*>(f->d_gfixC), (long)L.n_gradC, SF_FIX_REPLICAS, f->d_gsrcC, f->d_gzeroC, f->n_gzeroC, grad, st, sq_for(f, L)));
-      else if (use_fix) SF_TRY(sf_launch_gather_fix(f->d_gfixC, (long)L.n_gradC, SF_FIX_REPLICAS, f->d_gsrcC, f->d_gzeroC, f->n_gzeroC, grad, st));
-      else if (f->d_gsrcC) SF_TRY(sf_launch_gather_c2(f->d_gpartC, (long)L.n_gradC, n_part, f->d_gsrcC, f->d_gzeroC, f->n_gzeroC, grad, st, sq_for(f, L)));
-      else SF_TRY(sf_launch_gather_c(f->d_gpartC, (long)L.n_gradC, n_part, f->d_gdstC, grad, (long)L.n_params, st));
+        SF_TRY_ERR(sf_launch_gather_c2(reinterpret_cast<const float*>(f->d_gfixC), (long)L.n_gradC, SF_FIX_REPLICAS, f->d_gsrcC, f->d_gzeroC, f->n_gzeroC, grad, st, sq_for(f, L)));
+      else if (use_fix) SF_TRY_ERR(sf_launch_gather_fix(f->d_gfixC, (long)L.n_gradC, SF_FIX_REPLICAS, f->d_gsrcC, f->d_gzeroC, f->n_gzeroC, grad, st));
+      else if (f->d_gsrcC) SF_TRY_ERR(sf_launch_gather_c2(f->d_gpartC, (long)L.n_gradC, n_part, f->d_gsrcC, f->d_gzeroC, f->n_gzeroC, grad, st, sq_for(f, L)));
+      else SF_TRY_ERR(sf_launch_gather_c(f->d_gpartC, (long)L.n_gradC, n_part, f->d_gdstC, grad, (long)L.n_params, st));
       return SF_OK;
     }
     SfTrcArgs a;
@@ -455,17 +447,17 @@ int sf_train_loss_grad(sf_flow* f, const float* flat, const float* theta, const 
     if (loss_sum && f->d_losspart) { a.loss_sum = f->d_losspart; a.loss_mask = SF_LOSS_PARTS - 1; f->losspart_used = true; }
     a.gpart = f->d_gpartC; a.gpart_stride = (long)L.n_gradC; a.fix = use_fix ? f->d_gfixC : nullptr;
     if (f->profiling) {
-      if (!f->ev_train[0]) { SF_TRY(hipEventCreate(&f->ev_train[0])); SF_TRY(hipEventCreate(&f->ev_train[1])); }
-      SF_TRY(hipEventRecord(f->ev_train[0], st));
+      if (!f->ev_train[0]) { SF_TRY_ERR(hipEventCreate(&f->ev_train[0])); SF_TRY_ERR(hipEventCreate(&f->ev_train[1])); }
+      SF_TRY_ERR(hipEventRecord(f->ev_train[0], st));
     }
-    SF_TRY(sf_launch_maf_trainc(a, grid, st));
+    SF_TRY_ERR(sf_launch_maf_trainc(a, grid, st));
     if (f->profiling) {
-      SF_TRY(hipEventRecord(f->ev_train[1], st));
+      SF_TRY_ERR(hipEventRecord(f->ev_train[1], st));
       f->ev_train_valid = true;
     }
-    if (use_fix) SF_TRY(sf_launch_gather_fix(f->d_gfixC, (long)L.n_gradC, SF_FIX_REPLICAS, f->d_gsrcC, f->d_gzeroC, f->n_gzeroC, grad, st));
-    else if (f->d_gsrcC) SF_TRY(sf_launch_gather_c2(f->d_gpartC, (long)L.n_gradC, grid, f->d_gsrcC, f->d_gzeroC, f->n_gzeroC, grad, st, sq_for(f, L)));
-    else SF_TRY(sf_launch_gather_c(f->d_gpartC, (long)L.n_gradC, grid, f->d_gdstC, grad, (long)L.n_params, st));
+    if (use_fix) SF_TRY_ERR(sf_launch_gather_fix(f->d_gfixC, (long)L.n_gradC, SF_FIX_REPLICAS, f->d_gsrcC, f->d_gzeroC, f->n_gzeroC, grad, st));
+    else if (f->d_gsrcC) SF_TRY_ERR(sf_launch_gather_c2(f->d_gpartC, (long)L.n_gradC, grid, f->d_gsrcC, f->d_gzeroC, f->n_gzeroC, grad, st, sq_for(f, L)));
+    else SF_TRY_ERR(sf_launch_gather_c(f->d_gpartC, (long)L.n_gradC, grid, f->d_gdstC, grad, (long)L.n_params, st));
     return SF_OK;
   }
   // ---- lazily built training state
@@ -503,10 +495,10 @@ int sf_train_loss_grad(sf_flow* f, const float* flat, const float* theta, const 
   const long act_per_wave = tiles_per_wave * 4 * 64;  // float4
   const size_t need = (size_t)waves * act_per_wave * 4;
   if (need > f->act_cap) {
-    if (f->d_act) SF_TRY(hipFree(f->d_act));
+    if (f->d_act) SF_TRY_ERR(hipFree(f->d_act));
     f->d_act = nullptr;
     f->act_cap = 0;
-    SF_TRY(hipMalloc(&f->d_act, need * sizeof(float)));
+    SF_TRY_ERR(hipMalloc(&f->d_act, need * sizeof(float)));
     f->act_cap = need;
   }
   // gradient accumulation: one replica per tile + plain stores (bitwise reproducible, and cheaper than atomics) up to
@@ -517,9 +509,9 @@ int sf_train_loss_grad(sf_flow* f, const float* flat, const float* theta, const 
   const bool det = waves > 0 && (waves <= 16 || (force_det == 1 && (size_t)waves * L.n_packed * sizeof(float) <= ((size_t)2 << 30)));
   const int copies = det ? (int)waves : SF_GCOPIES;
   if ((size_t)copies * L.n_packed > f->gpacked_cap) {
-    SF_TRY(hipFree(f->d_gpacked));
+    SF_TRY_ERR(hipFree(f->d_gpacked));
     f->d_gpacked = nullptr; f->gpacked_cap = 0;
-    SF_TRY(hipMalloc(&f->d_gpacked, (size_t)copies * L.n_packed * sizeof(float)));
+    SF_TRY_ERR(hipMalloc(&f->d_gpacked, (size_t)copies * L.n_packed * sizeof(float)));
     f->gpacked_cap = (size_t)copies * L.n_packed;
   }
   {
@@ -531,11 +523,11 @@ int sf_train_loss_grad(sf_flow* f, const float* flat, const float* theta, const 
                        (long)L.n_packed, f->d_t1, f->d_t2, f->d_packedT, (long)L.n_packedT, f->d_gpacked, copies, dctx, n4,
                        f->d_s16a, f->d_s16b, f->d_packed16, n5, f->d_s16B, f->d_packed16B, n6, (const int32_t*)nullptr,
                        (const int32_t*)nullptr, (float*)nullptr, 0L);
-    SF_TRY(hipGetLastError());
+    SF_TRY_ERR(hipGetLastError());
   }
   f->packed16_stale = false;
   f->wp_stale = true;
-  if (L.n_packedB > 0) SF_TRY(sf_launch_pack_bf16(flat, f->d_bsrc, f->d_packedB, (long)L.n_packedB, st));
+  if (L.n_packedB > 0) SF_TRY_ERR(sf_launch_pack_bf16(flat, f->d_bsrc, f->d_packedB, (long)L.n_packedB, st));
   if (B > 0) {
     SfTrainArgs a;
     a.theta = theta; a.x = x; a.idx = idx; a.loss_sum = loss_sum; a.B = B; a.w = grad_scale; a.wts = weights; a.loss = loss; a.dctx = dctx; a.gimg = f->d_gpacked; a.gimg_stride = (long)L.n_packed; a.det = det ? 1 : 0;
@@ -543,23 +535,23 @@ int sf_train_loss_grad(sf_flow* f, const float* flat, const float* theta, const 
     const SfDev m = f->dev();
     const bool maf = m.kind == SF_MAF;
     if (f->profiling) {
-      if (!f->ev_train[0]) { SF_TRY(hipEventCreate(&f->ev_train[0])); SF_TRY(hipEventCreate(&f->ev_train[1])); }
-      SF_TRY(hipEventRecord(f->ev_train[0], st));
+      if (!f->ev_train[0]) { SF_TRY_ERR(hipEventCreate(&f->ev_train[0])); SF_TRY_ERR(hipEventCreate(&f->ev_train[1])); }
+      SF_TRY_ERR(hipEventRecord(f->ev_train[0], st));
     }
     switch (m.HT) {
-      case 1: SF_TRY(maf ? sf_launch_maf_train_h1(m, a, st) : sf_launch_nsf_train_h1(m, a, st)); break;
-      case 2: SF_TRY(maf ? sf_launch_maf_train_h2(m, a, st) : sf_launch_nsf_train_h2(m, a, st)); break;
-      case 3: SF_TRY(maf ? sf_launch_maf_train_h3(m, a, st) : sf_launch_nsf_train_h3(m, a, st)); break;
-      case 4: SF_TRY(maf ? sf_launch_maf_train_h4(m, a, st) : sf_launch_nsf_train_h4(m, a, st)); break;
+      case 1: SF_TRY_ERR(maf ? sf_launch_maf_train_h1(m, a, st) : sf_launch_nsf_train_h1(m, a, st)); break;
+      case 2: SF_TRY_ERR(maf ? sf_launch_maf_train_h2(m, a, st) : sf_launch_nsf_train_h2(m, a, st)); break;
+      case 3: SF_TRY_ERR(maf ? sf_launch_maf_train_h3(m, a, st) : sf_launch_nsf_train_h3(m, a, st)); break;
+      case 4: SF_TRY_ERR(maf ? sf_launch_maf_train_h4(m, a, st) : sf_launch_nsf_train_h4(m, a, st)); break;
       default: err = "bad HT"; return SF_ERR_INVALID;
     }
     if (f->profiling) {
-      SF_TRY(hipEventRecord(f->ev_train[1], st));
+      SF_TRY_ERR(hipEventRecord(f->ev_train[1], st));
       f->ev_train_valid = true;
     }
   }
   hipLaunchKernelGGL(k_grad_gather, dim3((unsigned)((L.n_params + 255) / 256)), dim3(256), 0, st,
                      f->d_gpacked, (long)L.n_packed, copies, f->d_gdst, grad, (long)L.n_params);
-  SF_TRY(hipGetLastError());
+  SF_TRY_ERR(hipGetLastError());
   return SF_OK;
 }

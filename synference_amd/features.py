@@ -17,6 +17,7 @@ from typing import Optional
 import torch
 
 from . import _lib
+from ._lib import ptr as _p, stream_ptr as _stream
 
 
 def flux_to_abmag(flux_njy: torch.Tensor, err_njy: Optional[torch.Tensor] = None, norm_mag_limit: float = 50.0):
@@ -30,18 +31,9 @@ def flux_to_abmag(flux_njy: torch.Tensor, err_njy: Optional[torch.Tensor] = None
     e = None if err_njy is None else _aligned(err_njy)
     mag = torch.empty_like(f)
     mag_err = None if e is None else torch.empty_like(f)
-    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-    st = C.c_void_p(torch.cuda.current_stream(f.device).cuda_stream)
-    _lib.check(_lib.load().sf_flux_to_abmag(p(f), p(e), f.numel(), C.c_float(norm_mag_limit), p(mag), p(mag_err), st))
+    _lib.check(_lib.load().sf_flux_to_abmag(_p(f), _p(e), f.numel(), C.c_float(norm_mag_limit), _p(mag), _p(mag_err),
+                                            _stream(f.device)))
     return mag if e is None else (mag, mag_err)
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def flux_to_asinh(flux_njy: torch.Tensor, f_b_njy, err_njy: Optional[torch.Tensor] = None):

@@ -53,10 +53,10 @@ def _stable_top(key: torch.Tensor, k: int) -> torch.Tensor:
 
 def map_step(theta, lp, g, phi, m, v, lo, hi, best_theta, best_lp, learning_rate: float, step: int, save_best: bool):
     """One fused ascent step (sf_map_step) on contiguous float32 device tensors; ``g`` None: score only."""
-    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    p = _lib.ptr
     B, D = theta.shape
     with torch.cuda.device(theta.device):
-        st = C.c_void_p(torch.cuda.current_stream(theta.device).cuda_stream)
+        st = _lib.stream_ptr(theta.device)
         _lib.check(_lib.load().sf_map_step(B, D, p(phi), p(m), p(v), p(theta), p(lp), p(g), p(lo), p(hi), p(best_theta),
                                            p(best_lp), C.c_float(float(learning_rate)), int(step), 1 if save_best else 0, st))
 

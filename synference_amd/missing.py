@@ -34,16 +34,13 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import ptr as _ptr
 
 logger = logging.getLogger("synference_amd")
 
 _DEFAULTS = {"ini_chi2": 5.0, "max_chi2": 50.0, "nmc": 100, "nposterior": 1000, "tmax_all": 10, "verbose": False}
 # (not in the reference's dictionary, where they are literals: sbi_runner.py:7753-7760, 7778)
 _EXTRA = {"chi2_step": 5.0, "min_neighbours": 30, "fallback_k": 100, "bw": 0.2}
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 class MissingPhotometryHandler:
@@ -154,7 +151,7 @@ class MissingPhotometryHandler:
             out["draw_idx"] = torch.empty((M, nmc, B), dtype=torch.int32, device=dev)
         bc = (C.c_int32 * B)(*[int(c) for c in self.band_columns])
         ec = None if self.error_columns is None else (C.c_int32 * B)(*[int(c) for c in self.error_columns])
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        st = _lib.stream_ptr(dev)
         with torch.cuda.device(dev):
             _lib.check(_lib.load().sf_impute_missing(
                 _ptr(self._train_dev), self.y_train.shape[0], F, bc, ec, B, _ptr(rows), _ptr(sig), _ptr(miss), M, int(row_offset),

@@ -20,7 +20,6 @@ whitening matrices -- so that a second catalogue against the same library pays o
 """
 from __future__ import annotations
 
-import ctypes as C
 import logging
 import math
 from typing import Any, Dict, Optional
@@ -29,6 +28,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import ptr as _ptr
 
 logger = logging.getLogger("synference_amd")
 
@@ -37,10 +37,6 @@ NOT_BUILT = ("robust_mahalanobis", "isolation_forest", "one_class_svm")
 PYOD_METHODS = ("knn", "lof", "kde")
 COMBINATIONS = ("majority", "any", "all", "none")
 KMAX, CMAX = 64, 64
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 # ---- the two kernels ------------------------------------------------------------------------------------------------------
@@ -54,7 +50,7 @@ def knn(base: torch.Tensor, query: torch.Tensor, k: int, exclude_self: bool = Fa
     d2 = torch.empty((M, k), dtype=torch.float32, device=base.device)
     idx = torch.empty((M, k), dtype=torch.int32, device=base.device)
     with torch.cuda.device(base.device):
-        st = C.c_void_p(torch.cuda.current_stream(base.device).cuda_stream)
+        st = _lib.stream_ptr(base.device)
         _lib.check(_lib.load().sf_knn(_ptr(base), base.shape[0], base.shape[1], _ptr(query), M, int(k), int(bool(exclude_self)),
                                       int(self_offset), _ptr(d2), _ptr(idx), st))
     return d2, idx
@@ -67,7 +63,7 @@ def kde_logsumexp(base_w: torch.Tensor, query_w: torch.Tensor) -> torch.Tensor:
     base_w, query_w = base_w.contiguous(), query_w.contiguous()
     out = torch.empty((query_w.shape[0],), dtype=torch.float64, device=base_w.device)
     with torch.cuda.device(base_w.device):
-        st = C.c_void_p(torch.cuda.current_stream(base_w.device).cuda_stream)
+        st = _lib.stream_ptr(base_w.device)
         _lib.check(_lib.load().sf_kde_logsumexp(_ptr(base_w), base_w.shape[0], base_w.shape[1], _ptr(query_w),
                                                 query_w.shape[0], _ptr(out), st))
     return out

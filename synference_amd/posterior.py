@@ -385,7 +385,6 @@ class EnsemblePosterior:
 def device_quantiles(samples: torch.Tensor, quantiles) -> torch.Tensor:
     """(N,S,D) float32 device draws -> (N,D,Q) quantiles on the device (sf_quantiles; numpy 'linear' rule,
     NaN draws ignored).  Counterpart of the host pass at ref: sbi_runner.py:3270-3282."""
-    import ctypes as C
     from . import _lib
     if samples.device.type != "cuda":
         raise RuntimeError("device_quantiles needs the draws on the GPU")
@@ -393,9 +392,8 @@ def device_quantiles(samples: torch.Tensor, quantiles) -> torch.Tensor:
     N, S, D = samples.shape
     q = torch.as_tensor(np.asarray(quantiles, dtype=np.float32), device=samples.device)
     out = torch.empty((N, D, q.numel()), dtype=torch.float32, device=samples.device)
-    st = C.c_void_p(torch.cuda.current_stream(samples.device).cuda_stream)
-    _lib.check(_lib.load().sf_quantiles(C.c_void_p(samples.data_ptr()), N, S, D, C.c_void_p(q.data_ptr()), q.numel(),
-                                        C.c_void_p(out.data_ptr()), st))
+    st = _lib.stream_ptr(samples.device)
+    _lib.check(_lib.load().sf_quantiles(_lib.ptr(samples), N, S, D, _lib.ptr(q), q.numel(), _lib.ptr(out), st))
     return out
 
 
@@ -403,7 +401,6 @@ def device_quantiles_large(samples: torch.Tensor, quantiles) -> torch.Tensor:
     """``device_quantiles`` for long rows, 1 <= S <= 2^24 (sf_quantiles_large: an exact radix select instead of a sort in
     LDS, the position (n - 1) q in float64) -- the pooled nmc x nposterior draws of the missing-band path
     (ref: sbi_runner.py:3292-3297)."""
-    import ctypes as C
     from . import _lib
     if samples.device.type != "cuda":
         raise RuntimeError("device_quantiles_large needs the draws on the GPU")
@@ -411,10 +408,9 @@ def device_quantiles_large(samples: torch.Tensor, quantiles) -> torch.Tensor:
     N, S, D = samples.shape
     q = torch.as_tensor(np.asarray(quantiles, dtype=np.float32), device=samples.device)
     out = torch.empty((N, D, q.numel()), dtype=torch.float32, device=samples.device)
-    st = C.c_void_p(torch.cuda.current_stream(samples.device).cuda_stream)
+    st = _lib.stream_ptr(samples.device)
     with torch.cuda.device(samples.device):
-        _lib.check(_lib.load().sf_quantiles_large(C.c_void_p(samples.data_ptr()), N, S, D, C.c_void_p(q.data_ptr()), q.numel(),
-                                                  C.c_void_p(out.data_ptr()), st))
+        _lib.check(_lib.load().sf_quantiles_large(_lib.ptr(samples), N, S, D, _lib.ptr(q), q.numel(), _lib.ptr(out), st))
     return out
 
 

@@ -221,6 +221,26 @@ def test_compute_calls_fail_loudly_without_a_gpu():
     assert rc == -3 and b"no CPU fallback" in lib.sf_last_error()
 
 
+@pytest.mark.skipif(torch.cuda.is_available(), reason="checks the no-GPU failure mode")
+def test_catalogue_tools_fail_loudly_without_a_gpu():
+    """The device step of the tools' scratch (csrc/sf_scratch.h): SF_ERR_NO_DEVICE and '<entry point>: no usable device: ...'
+    after the argument checks, before anything is read through the (dummy) pointers."""
+    from synference_amd import _lib
+    lib = _lib.load()
+    d = C.c_void_p(4096)                                    # never dereferenced on the host
+    cols = (C.c_int32 * 2)(0, 1)
+    calls = {
+        "sf_tarp_coverage": lambda: lib.sf_tarp_coverage(d, d, 10, 8, 2, None, 0, 0, 2, 1, 7, d, None, None, None, None),
+        "sf_knn": lambda: lib.sf_knn(d, 100, 3, d, 5, 2, 0, 0, d, d, None),
+        "sf_kde_logsumexp": lambda: lib.sf_kde_logsumexp(d, 100, 3, d, 5, d, None),
+        "sf_impute_missing": lambda: lib.sf_impute_missing(d, 100, 2, cols, None, 2, d, d, d, 3, 0, 5.0, 5.0, 50.0, 30, 100, 0.2, 4,
+                                                           7, d, d, d, None, None, None, 0, None, None),
+    }
+    for name, call in calls.items():
+        assert call() == -3, name
+        assert lib.sf_last_error().startswith(name.encode() + b": no usable device: "), lib.sf_last_error()
+
+
 def test_product_never_imports_the_oracle():
     for p in (ROOT / "synference_amd").rglob("*.py"):
         txt = p.read_text()

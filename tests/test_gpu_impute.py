@@ -68,11 +68,9 @@ def _run(shape):
     return _device(shape)
 
 
-@pytest.mark.parametrize("shape", IM.SHAPES, ids=IDS)
-def test_selection_is_the_models(shape):
+def _check_selection(shape, d):
     NT, F, B, M, nmc, with_err = shape
     cs, mods = IM.case_and_model(shape)
-    d = _run(shape)
     for m, mod in enumerate(mods):
         print(f"object {m} {cs['kinds'][m]}: n_used {d['n_used'][m]} (model {mod['n_used']}) thr {d['thr'][m]} (model {mod['thr']})")
         assert d["n_used"][m] == mod["n_used"] and d["thr"][m] == mod["thr"]
@@ -93,11 +91,9 @@ def test_a_short_neighbour_buffer_is_respected():
     assert np.array_equal(d["imputed"], _run(shape)["imputed"], equal_nan=True)
 
 
-@pytest.mark.parametrize("shape", IM.SHAPES, ids=IDS)
-def test_moments_on_the_returned_list(shape):
+def _check_moments(shape, d):
     NT, F, B, M, nmc, with_err = shape
     cs, mods = IM.case_and_model(shape)
-    d = _run(shape)
     worst = 0.0
     for m in range(M):
         n = int(d["n_used"][m])
@@ -113,11 +109,9 @@ def test_moments_on_the_returned_list(shape):
     print(f"kde_var: worst relative difference {worst:.2e}")
 
 
-@pytest.mark.parametrize("shape", IM.SHAPES, ids=IDS)
-def test_draws_are_the_models(shape):
+def _check_draws(shape, d):
     NT, F, B, M, nmc, with_err = shape
     cs, mods = IM.case_and_model(shape)
-    d = _run(shape)
     bc, ec = cs["band_col"], cs["err_col"]
     worst = 0.0
     for m, mod in enumerate(mods):
@@ -142,6 +136,34 @@ def test_draws_are_the_models(shape):
             assert abs(d["recon"][m, b] - mean) <= 1e-6 * abs(mean)
         assert np.isnan(d["recon"][m][~miss]).all()
     print(f"imputed values: worst |difference| / tolerance {worst:.3f}")
+
+
+@pytest.mark.parametrize("shape", IM.SHAPES, ids=IDS)
+def test_selection_is_the_models(shape):
+    _check_selection(shape, _run(shape))
+
+
+@pytest.mark.parametrize("shape", IM.SHAPES, ids=IDS)
+def test_moments_on_the_returned_list(shape):
+    _check_moments(shape, _run(shape))
+
+
+@pytest.mark.parametrize("shape", IM.SHAPES, ids=IDS)
+def test_draws_are_the_models(shape):
+    _check_draws(shape, _run(shape))
+
+
+def test_scratch_reuse_across_sizes():
+    """Small, large, small again: both scratch regions grow, serve a smaller layout from the larger buffers, then one of equal
+    size."""
+    small, large = IM.SHAPES[3], IM.SHAPES[0]
+    first, second, third = _device(small), _device(large), _device(small)
+    for k in first:
+        assert first[k].tobytes() == third[k].tobytes(), k
+    for shape, d in ((small, first), (large, second)):
+        _check_selection(shape, d)
+        _check_moments(shape, d)
+        _check_draws(shape, d)
 
 
 def test_reproducible_and_independent_of_the_grouping():

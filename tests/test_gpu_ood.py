@@ -101,6 +101,43 @@ def test_knn_pairs_are_consistent_without_the_selection_model(case):
         assert not (idx == 500).any()
 
 
+def test_knn_scratch_reuse_across_sizes():
+    """Small, large, small again: the scratch grows, serves a smaller layout from the larger buffer, then one of equal size."""
+    small, large = KNN_CASES[2], KNN_CASES[0]
+    first, second, third = (_knn_raw(*_case(*c), c[3])[1:] for c in (small, large, small))
+    for u, v in zip(first, third):
+        assert u.tobytes() == v.tobytes()
+    for case, (d2, idx) in ((small, first), (large, second)):
+        md2, midx = _knn_pair(case)[1]
+        assert np.array_equal(idx, midx) and np.array_equal(d2.view(np.uint32), md2.view(np.uint32))
+
+
+def test_knn_two_calls_on_two_streams():
+    """Two sf_knn calls queued back to back on two streams, with no host synchronisation in between; different data and
+    shapes, so that the second call carves the shared scratch differently.  Each result must equal that call's result when it
+    runs alone.  This walks the wait-and-record path of the scratch (the second call's stream waits for the event the first
+    call recorded).  It is not a detector: a lost ordering would not fail reliably, and the test must never be looped to
+    make it fail."""
+    from synference_amd import _lib
+    lib = _lib.load()
+    cases = [KNN_CASES[0], KNN_CASES[5]]
+    alone = [_knn_pair(c)[0] for c in cases]
+    bufs = []
+    for c in cases:
+        base, query = _case(*c)
+        bufs.append((torch.tensor(base).cuda(), torch.tensor(query).cuda(), torch.full((c[2], c[3]), SENT_F, device="cuda"),
+                     torch.full((c[2], c[3]), SENT_I, dtype=torch.int32, device="cuda")))
+    streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+    torch.cuda.synchronize()
+    for c, (b, q, d2, idx), st in zip(cases, bufs, streams):
+        with torch.cuda.stream(st):
+            _lib.check(lib.sf_knn(_p(b), c[0], c[1], _p(q), c[2], c[3], 0, 0, _p(d2), _p(idx), C.c_void_p(st.cuda_stream)))
+    for st in streams:
+        st.synchronize()
+    for (b, q, d2, idx), (ad2, aidx) in zip(bufs, alone):
+        assert np.array_equal(idx.cpu().numpy(), aidx) and d2.cpu().numpy().tobytes() == ad2.tobytes()
+
+
 def test_knn_does_not_depend_on_the_split_over_queries():
     case = KNN_CASES[0]
     base, query = _case(*case)

@@ -39,25 +39,41 @@ def _model(shape, metric, norm_axis):
                             num_alpha_bins=max(1, N // 10), seed=SEED, norm_axis=max(norm_axis, 0), band=True)
 
 
-def _device(x, theta, metric="euclidean", norm_axis=0, B=0, n=None, seed=SEED, references=None, lib=None):
-    """Straight through the C ABI with counts and boot_idx returned."""
-    from synference_amd import _lib
-    lib = lib or _lib.load()
+def _buffers(x, theta, B=0, n=None, references=None):
+    """Device copies of the inputs and sentinel-filled outputs of one call."""
     N, S, D = x.shape
     n = n if n is not None else max(1, N // 10)
-    xd, td = torch.tensor(x).cuda(), torch.tensor(theta).cuda()      # (copies: the cached inputs are read-only)
-    rd = None if references is None else torch.tensor(np.asarray(references, dtype=np.float32)).cuda()
     rows = max(B, 1)
-    ecp = torch.full((rows, n + 1), -7.0, dtype=torch.float64, device="cuda")
-    alpha = torch.full((n + 1,), -7.0, dtype=torch.float64, device="cuda")
-    counts = torch.full((rows, N), -7, dtype=torch.int32, device="cuda")
-    bidx = torch.full((max(B, 1), N), -7, dtype=torch.int32, device="cuda")
+    return dict(x=torch.tensor(x).cuda(), theta=torch.tensor(theta).cuda(),     # (copies: the cached inputs are read-only)
+                refs=None if references is None else torch.tensor(np.asarray(references, dtype=np.float32)).cuda(),
+                ecp=torch.full((rows, n + 1), -7.0, dtype=torch.float64, device="cuda"),
+                alpha=torch.full((n + 1,), -7.0, dtype=torch.float64, device="cuda"),
+                counts=torch.full((rows, N), -7, dtype=torch.int32, device="cuda"),
+                bidx=torch.full((rows, N), -7, dtype=torch.int32, device="cuda"), B=B, n=n)
+
+
+def _queue(buf, metric="euclidean", norm_axis=0, seed=SEED, lib=None):
+    """The call on torch's current stream, straight through the C ABI; nothing waits for it."""
+    from synference_amd import _lib
+    lib = lib or _lib.load()
+    N, S, D = buf["x"].shape
     p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-    _lib.check(lib.sf_tarp_coverage(p(xd), p(td), N, S, D, p(rd), METRICS.index(metric), norm_axis, B, n, C.c_uint64(seed),
-                                    p(ecp), p(alpha), p(counts), p(bidx) if B else None,
-                                    C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    _lib.check(lib.sf_tarp_coverage(p(buf["x"]), p(buf["theta"]), N, S, D, p(buf["refs"]), METRICS.index(metric), norm_axis,
+                                    buf["B"], buf["n"], C.c_uint64(seed), p(buf["ecp"]), p(buf["alpha"]), p(buf["counts"]),
+                                    p(buf["bidx"]) if buf["B"] else None, C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+
+
+def _host(buf):
+    return (buf["ecp"].cpu().numpy(), buf["alpha"].cpu().numpy(), buf["counts"].cpu().numpy().astype(np.int64),
+            buf["bidx"].cpu().numpy().astype(np.int64))
+
+
+def _device(x, theta, metric="euclidean", norm_axis=0, B=0, n=None, seed=SEED, references=None, lib=None):
+    """Straight through the C ABI with counts and boot_idx returned."""
+    buf = _buffers(x, theta, B, n, references)
+    _queue(buf, metric, norm_axis, seed, lib)
     torch.cuda.synchronize()
-    return ecp.cpu().numpy(), alpha.cpu().numpy(), counts.cpu().numpy().astype(np.int64), bidx.cpu().numpy().astype(np.int64)
+    return _host(buf)
 
 
 def _check_against_model(ecp, alpha, counts, m, S, n):
@@ -94,6 +110,59 @@ def test_counts_and_curves_match_the_model(shape, metric, norm_axis):
     assert counts.min() >= 0 and counts.max() <= S
     same = _check_against_model(ecp, alpha, counts, m, S, n)
     print(f"passes with the model's counts: {same} of {B}")
+
+
+# N = 1, and N around and beyond the 1024 threads of the row-count scan: a thread owns one count, then several
+SCAN_SHAPES = [(N, 8, 1, 2) for N in (1, 1023, 1024, 1025, 2500)]
+
+
+@pytest.mark.parametrize("shape", SCAN_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_row_scan_beyond_one_count_per_thread(shape):
+    N, S, D, B = shape
+    x, theta = _data(shape)
+    m = _model(shape, "euclidean", 0)
+    n = max(1, N // 10)
+    ecp, alpha, counts, bidx = _device(x, theta, "euclidean", 0, B)
+    assert np.array_equal(bidx, m["idx"])                             # the row resample: exactly
+    assert counts.min() >= 0 and counts.max() <= S
+    _check_against_model(ecp, alpha, counts, m, S, n)
+
+
+def test_scratch_reuse_across_sizes():
+    """Small, large, small again: the scratch grows, serves a smaller layout from the larger buffer, then one of equal size."""
+    small, large = (37, 257, 1, 4), (300, 1000, 3, 8)
+    first = _device(*_data(small), "euclidean", 0, small[3])
+    ecp, alpha, counts, bidx = _device(*_data(large), "euclidean", 0, large[3])
+    third = _device(*_data(small), "euclidean", 0, small[3])
+    for u, v in zip(first, third):
+        assert u.tobytes() == v.tobytes()
+    m = _model(large, "euclidean", 0)
+    assert np.array_equal(bidx, m["idx"]) and counts.min() >= 0 and counts.max() <= large[1]
+    _check_against_model(ecp, alpha, counts, m, large[1], max(1, large[0] // 10))
+    m = _model(small, "euclidean", 0)
+    assert np.array_equal(first[3], m["idx"])
+    _check_against_model(*first[:3], m, small[1], max(1, small[0] // 10))
+
+
+def test_two_calls_on_two_streams():
+    """Two calls queued back to back on two streams, with no host synchronisation in between; different data and a different
+    N, so that the second call carves the shared scratch differently.  Each result must equal that call's result when it
+    runs alone.  This walks the wait-and-record path of the scratch (the second call's stream waits for the event the first
+    call recorded).  It is not a detector: a lost ordering would not fail reliably, and the test must never be looped to
+    make it fail."""
+    cases = [((64, 100, 5, 8), "euclidean"), ((37, 257, 1, 4), "manhattan")]
+    alone = [_device(*_data(shape), metric, 0, shape[3]) for shape, metric in cases]
+    bufs = [_buffers(*_data(shape), shape[3]) for shape, _ in cases]
+    streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+    torch.cuda.synchronize()
+    for buf, st, (_, metric) in zip(bufs, streams, cases):
+        with torch.cuda.stream(st):
+            _queue(buf, metric, 0)
+    for st in streams:
+        st.synchronize()
+    for buf, want in zip(bufs, alone):
+        for u, v in zip(_host(buf), want):
+            assert u.tobytes() == v.tobytes()
 
 
 def test_explicit_references_and_the_non_bootstrap_call():
