@@ -24,55 +24,60 @@ int hip_fail(hipError_t e, const char* what) {
 }
 }  // namespace
 
+// all or nothing: the buffers are built in a local group and moved into the handle at the end, so a failure part-way leaves
+// the handle as it was and the next call starts over
 static int ensure_device(sf_flow* f) {
-  if (f->nsf1 || f->nsfar) {
-    if (f->dev_ready) return SF_OK;
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || nd == 0) return sf_fail(SF_ERR_NO_DEVICE, "no HIP device visible");
-    hipError_t e = hipMalloc(&f->d_flat, (size_t)f->L.n_params * sizeof(float));
-    if (e != hipSuccess) return hip_fail(e, "hipMalloc(d_flat)");
-    f->dev_ready = true;
-    return SF_OK;
-  }
   if (f->dev_ready) return SF_OK;
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
     return sf_fail(SF_ERR_NO_DEVICE, "no HIP device visible: the gfx950 flow engine has no CPU fallback");
+  SfFlowDev d;
+  if (f->nsf1 || f->nsfar) {   // (their images live in the sub-handle)
+    SF_TRY_SET(d.d_flat.alloc((size_t)f->L.n_params));
+    static_cast<SfFlowDev&>(*f) = std::move(d);
+    f->dev_ready = true;
+    return SF_OK;
+  }
   const size_t np = (size_t)f->L.n_packed;
-  SF_TRY_SET(hipMalloc(&f->d_packed, np * sizeof(float)));
-  SF_TRY_SET(hipMemset(f->d_packed, 0, np * sizeof(float)));
-  SF_TRY_SET(hipMalloc(&f->d_cst, f->L.cst.size() * sizeof(float)));
-  SF_TRY_SET(hipMemcpy(f->d_cst, f->L.cst.data(), f->L.cst.size() * sizeof(float), hipMemcpyHostToDevice));
-  SF_TRY_SET(hipMalloc(&f->d_s1, np * sizeof(int32_t)));
-  SF_TRY_SET(hipMalloc(&f->d_s2, np * sizeof(int32_t)));
-  SF_TRY_SET(hipMemcpy(f->d_s1, f->L.src1.data(), np * sizeof(int32_t), hipMemcpyHostToDevice));
-  SF_TRY_SET(hipMemcpy(f->d_s2, f->L.src2.data(), np * sizeof(int32_t), hipMemcpyHostToDevice));
+  SF_TRY_SET(d.d_packed.alloc(np));
+  SF_TRY_SET(hipMemset(d.d_packed, 0, np * sizeof(float)));
+  SF_TRY_SET(d.d_cst.upload(f->L.cst));
+  SF_TRY_SET(d.d_s1.alloc(np));
+  SF_TRY_SET(d.d_s2.alloc(np));
+  SF_TRY_SET(hipMemcpy(d.d_s1, f->L.src1.data(), np * sizeof(int32_t), hipMemcpyHostToDevice));
+  SF_TRY_SET(hipMemcpy(d.d_s2, f->L.src2.data(), np * sizeof(int32_t), hipMemcpyHostToDevice));
   if ((f->L.dev.m16_ok || f->L.nsfS.ok) && f->L.n_packed16 > 0) {
     const size_t n16 = (size_t)f->L.n_packed16;
-    SF_TRY_SET(hipMalloc(&f->d_packed16, n16 * sizeof(float)));
-    SF_TRY_SET(hipMalloc(&f->d_s16a, n16 * sizeof(int32_t)));
-    SF_TRY_SET(hipMalloc(&f->d_s16b, n16 * sizeof(int32_t)));
-    SF_TRY_SET(hipMemcpy(f->d_s16a, f->L.src16a.data(), n16 * sizeof(int32_t), hipMemcpyHostToDevice));
-    SF_TRY_SET(hipMemcpy(f->d_s16b, f->L.src16b.data(), n16 * sizeof(int32_t), hipMemcpyHostToDevice));
+    SF_TRY_SET(d.d_packed16.alloc(n16));
+    SF_TRY_SET(d.d_s16a.alloc(n16));
+    SF_TRY_SET(d.d_s16b.alloc(n16));
+    SF_TRY_SET(hipMemcpy(d.d_s16a, f->L.src16a.data(), n16 * sizeof(int32_t), hipMemcpyHostToDevice));
+    SF_TRY_SET(hipMemcpy(d.d_s16b, f->L.src16b.data(), n16 * sizeof(int32_t), hipMemcpyHostToDevice));
   }
   if ((f->L.dev.m16_ok || f->L.nsfS.ok) && f->L.n_packed16B > 0) {
     const size_t nB = (size_t)f->L.n_packed16B;
-    SF_TRY_SET(hipMalloc(&f->d_packed16B, nB * sizeof(unsigned short)));
-    SF_TRY_SET(hipMalloc(&f->d_s16B, nB * sizeof(int32_t)));
-    SF_TRY_SET(hipMemcpy(f->d_s16B, f->L.src16B.data(), nB * sizeof(int32_t), hipMemcpyHostToDevice));
+    SF_TRY_SET(d.d_packed16B.alloc(nB));
+    SF_TRY_SET(d.d_s16B.alloc(nB));
+    SF_TRY_SET(hipMemcpy(d.d_s16B, f->L.src16B.data(), nB * sizeof(int32_t), hipMemcpyHostToDevice));
   }
   if (f->L.n_packedB > 0) {
-    SF_TRY_SET(hipMalloc(&f->d_packedB, (size_t)f->L.n_packedB * sizeof(unsigned short)));
-    SF_TRY_SET(hipMalloc(&f->d_bsrc, (size_t)f->L.n_packedB * sizeof(int32_t)));
-    SF_TRY_SET(hipMemcpy(f->d_bsrc, f->L.srcB.data(), (size_t)f->L.n_packedB * sizeof(int32_t), hipMemcpyHostToDevice));
+    SF_TRY_SET(d.d_packedB.alloc((size_t)f->L.n_packedB));
+    SF_TRY_SET(d.d_bsrc.alloc((size_t)f->L.n_packedB));
+    SF_TRY_SET(hipMemcpy(d.d_bsrc, f->L.srcB.data(), (size_t)f->L.n_packedB * sizeof(int32_t), hipMemcpyHostToDevice));
   }
-  SF_TRY_SET(hipMalloc(&f->d_flat, (size_t)f->L.n_params * sizeof(float)));
-  SF_TRY_SET(hipMalloc(&f->d_cnt, SF_MAX_ROUNDS * sizeof(uint32_t)));
-  SF_TRY_SET(hipHostMalloc((void**)&f->h_cnt, SF_MAX_ROUNDS * sizeof(uint32_t), hipHostMallocDefault));
-  SF_TRY_SET(hipEventCreate(&f->ev_dense[0]));
-  SF_TRY_SET(hipEventCreate(&f->ev_dense[1]));
+  SF_TRY_SET(d.d_flat.alloc((size_t)f->L.n_params));
+  SF_TRY_SET(d.d_cnt.alloc(SF_MAX_ROUNDS));
+  SF_TRY_SET(d.h_cnt.alloc(SF_MAX_ROUNDS));
+  SF_TRY_SET(d.ev_dense[0].create());
+  SF_TRY_SET(d.ev_dense[1].create());
+  static_cast<SfFlowDev&>(*f) = std::move(d);
   f->dev_ready = true;
   return SF_OK;
+}
+
+sf_flow::~sf_flow() {
+  sf_nsf1_destroy(nsf1);
+  sf_nsfar_destroy(nsfar);
 }
 
 extern "C" {
@@ -127,33 +132,7 @@ int sf_flow_create(const sf_flow_desc* desc, sf_flow** out) {
   return SF_OK;
 }
 
-void sf_flow_destroy(sf_flow* f) {
-  if (!f) return;
-  if (f->nsf1 || f->nsfar) {
-    sf_nsf1_destroy(f->nsf1);
-    sf_nsfar_destroy(f->nsfar);
-    if (f->dev_ready) (void)hipFree(f->d_flat);
-    (void)hipFree(f->d_losspart_mem);   // (sf_flow_train_epoch allocates it for every kind)
-    if (f->ev_train[0]) (void)hipEventDestroy(f->ev_train[0]);
-    if (f->ev_train[1]) (void)hipEventDestroy(f->ev_train[1]);
-    if (f->ev_dense[0]) (void)hipEventDestroy(f->ev_dense[0]);
-    if (f->ev_dense[1]) (void)hipEventDestroy(f->ev_dense[1]);
-    delete f;
-    return;
-  }
-  if (f->dev_ready) {
-    (void)hipFree(f->d_packed); (void)hipFree(f->d_packedT); (void)hipFree(f->d_cst); (void)hipFree(f->d_packedB); (void)hipFree(f->d_bsrc);
-    (void)hipHostFree(f->h_cnt); if (f->ev_train[0]) (void)hipEventDestroy(f->ev_train[0]); if (f->ev_train[1]) (void)hipEventDestroy(f->ev_train[1]); if (f->ev_dense[0]) (void)hipEventDestroy(f->ev_dense[0]); if (f->ev_dense[1]) (void)hipEventDestroy(f->ev_dense[1]);
-    (void)hipFree(f->d_ctab); (void)hipFree(f->d_packed16B); (void)hipFree(f->d_s16B); (void)hipFree(f->d_packed16); (void)hipFree(f->d_s16a); (void)hipFree(f->d_s16b);
-    (void)hipFree(f->d_s1); (void)hipFree(f->d_s2); (void)hipFree(f->d_t1); (void)hipFree(f->d_t2);
-    (void)hipFree(f->d_flat); (void)hipFree(f->d_gpacked); (void)hipFree(f->d_gdst);
-    (void)hipFree(f->d_imgC); (void)hipFree(f->d_sC1); (void)hipFree(f->d_sC2); (void)hipFree(f->d_gdstC); (void)hipFree(f->d_gsrcC); (void)hipFree(f->d_gzeroC); (void)hipFree(f->d_gpartC); (void)hipFree(f->d_gfixC); (void)hipFree(f->d_ustash);
-    (void)hipFree(f->d_queue); (void)hipFree(f->d_ring); (void)hipFree(f->d_galacc); (void)hipFree(f->d_sqpart); (void)hipFree(f->d_losspart_mem); (void)hipFree(f->d_best); (void)hipHostFree(f->h_queue);
-    (void)hipFree(f->d_gtT); (void)hipFree(f->d_gt1); (void)hipFree(f->d_gt2);
-    (void)hipFree(f->d_act); (void)hipFree(f->d_rej[0]); (void)hipFree(f->d_rej[1]); (void)hipFree(f->d_cnt);
-  }
-  delete f;
-}
+void sf_flow_destroy(sf_flow* f) { delete f; }
 
 int64_t sf_flow_num_params(const sf_flow* f) { return f ? f->L.n_params : 0; }
 int64_t sf_flow_packed_size(const sf_flow* f) { return !f ? 0 : (f->nsfar ? (int64_t)f->nsfar->src.size() : f->L.n_packed); }
@@ -460,13 +439,7 @@ int sf_flow_prepare_context(sf_flow* f, const float* x, int64_t M, void* stream)
   sf_ctab_shape(m, R, NV);
   const size_t need = (size_t)M * m.T * NV * R;
   if (need == 0 || need * sizeof(float) > ctab_limit_bytes()) return SF_OK;  // no table: kernels evaluate the context per draw
-  if (f->ctab_cap < need) {
-    (void)hipFree(f->d_ctab);
-    f->d_ctab = nullptr;
-    f->ctab_cap = 0;
-    SF_TRY_SET(hipMalloc(&f->d_ctab, need * sizeof(float)));
-    f->ctab_cap = need;
-  }
+  SF_TRY_SET(f->d_ctab.grow(need));
   m.ctab_R = R; m.ctab_NV = NV;
   if (f->wp_stale && m.kind == SF_MAF && m.m16_ok && m.packed16 && m.o16_wp >= 0) {   // the fused first layer follows the parameters
     SF_TRY_SET(sf_launch_maf_fuse16(m, (hipStream_t)stream));
@@ -553,33 +526,26 @@ int sf_flow_sample_round(sf_flow* f, const float* x, int64_t S, const uint32_t* 
 // 1 / (window x open slots) and its open slots become NaN rows, which is what the reference's timeout / error path
 // produces (ref: sbi_runner.py:6443-6460); [UPSTREAM] accept_reject_sample itself would loop forever on such a galaxy.
 static int ensure_queue(sf_flow* f, int64_t n_slots, int64_t M) {
-  if (!f->d_queue) SF_TRY_SET(hipMalloc(&f->d_queue, sizeof(SfQueue)));
-  if (!f->h_queue) SF_TRY_SET(hipHostMalloc((void**)&f->h_queue, sizeof(SfQueue), hipHostMallocDefault));
+  if (!f->d_queue) SF_TRY_SET(f->d_queue.alloc(1));
+  if (!f->h_queue) SF_TRY_SET(f->h_queue.alloc(1));
   // ring positions are tickets of idle workgroups: at most (resident workgroups x items per iteration) are in flight at a
   // time (<= 2048 x 256), whatever the size of the catalogue -- 2^20 entries (8 MiB) never alias
   uint64_t cap = 1u << 16;
   while (cap < (uint64_t)n_slots && cap < (1ull << 20)) cap <<= 1;
-  if (f->ring_cap < cap) {
-    (void)hipFree(f->d_ring);
-    f->d_ring = nullptr; f->ring_cap = 0;
-    SF_TRY_SET(hipMalloc(&f->d_ring, cap * sizeof(unsigned long long)));
-    SF_TRY_SET(hipMemset(f->d_ring, 0, cap * sizeof(unsigned long long)));  // consumers clear what they take: stays zero
-    f->ring_cap = cap;
+  if (f->d_ring.cap() < cap) {
+    SF_TRY_SET(f->d_ring.grow(cap));
+    hipError_t e = hipMemset(f->d_ring, 0, cap * sizeof(unsigned long long));  // consumers clear what they take: stays zero
+    if (e != hipSuccess) { (void)f->d_ring.reset(); return hip_fail(e, "hipMemset(retry ring)"); }   // (never a ring of unknown content)
     f->ring_dirty = false;
   }
-  if (f->rej_cap < (size_t)n_slots) {
-    (void)hipFree(f->d_rej[0]); (void)hipFree(f->d_rej[1]);
-    f->d_rej[0] = f->d_rej[1] = nullptr; f->rej_cap = 0;
-    SF_TRY_SET(hipMalloc(&f->d_rej[0], (size_t)n_slots * sizeof(uint32_t)));
-    SF_TRY_SET(hipMalloc(&f->d_rej[1], (size_t)n_slots * sizeof(uint32_t)));
-    f->rej_cap = (size_t)n_slots;
+  if (f->d_rej[0].cap() < (size_t)n_slots) {   // both lists or neither: release, build, move in
+    static_cast<SfFlowRej&>(*f) = SfFlowRej();
+    SfFlowRej r;
+    SF_TRY_SET(r.d_rej[0].alloc((size_t)n_slots));
+    SF_TRY_SET(r.d_rej[1].alloc((size_t)n_slots));
+    static_cast<SfFlowRej&>(*f) = std::move(r);
   }
-  if (f->galacc_cap < (size_t)M) {
-    (void)hipFree(f->d_galacc);
-    f->d_galacc = nullptr; f->galacc_cap = 0;
-    SF_TRY_SET(hipMalloc(&f->d_galacc, (size_t)M * sizeof(int32_t)));
-    f->galacc_cap = (size_t)M;
-  }
+  SF_TRY_SET(f->d_galacc.grow((size_t)M));
   return SF_OK;
 }
 
@@ -603,7 +569,7 @@ static int sample_persistent(sf_flow* f, const float* x, int64_t M, int64_t S, c
   a.x = x; a.S = (long)S; seed_keys(seed, 0, a.k0, a.k1);
   a.rng_slot_offset = (unsigned long long)f->sample_row_offset * (unsigned long long)S;
   a.lo = lo; a.hi = hi; a.out = out; a.n_drawn = n_drawn; a.out_f64 = f->sample_out_f64 ? 1 : 0;
-  a.q = f->d_queue; a.ring = f->d_ring; a.ring_mask = (uint32_t)(f->ring_cap - 1);
+  a.q = f->d_queue; a.ring = f->d_ring; a.ring_mask = (uint32_t)(f->d_ring.cap() - 1);
   a.out_slots = (uint32_t)(M * S);
   const uint32_t* cur = slots;
   int64_t pending = n_slots;
@@ -651,7 +617,7 @@ static int sample_persistent(sf_flow* f, const float* x, int64_t M, int64_t S, c
   for (;;) {
     // The retry ring stays all-zero only while every launch ends cleanly (consumers clear what they take).  A launch that
     // ended on a queue error, or never completed, may have left donated entries behind: clear the ring before it is reused.
-    if (f->ring_dirty) SF_TRY_SET(hipMemsetAsync(f->d_ring, 0, f->ring_cap * sizeof(unsigned long long), st));
+    if (f->ring_dirty) SF_TRY_SET(hipMemsetAsync(f->d_ring, 0, f->d_ring.cap() * sizeof(unsigned long long), st));
     f->ring_dirty = true;
     SF_TRY_SET(hipMemsetAsync(f->d_queue, 0, sizeof(SfQueue), st));
 #ifdef SF_Q_STATS
@@ -752,12 +718,7 @@ static int sample_persistent(sf_flow* f, const float* x, int64_t M, int64_t S, c
   // best[i] with an atomic min), a RESOLVE launch re-evaluates exactly attempt best[i] and writes the draw -- the
   // slot still keeps its LOWEST accepted attempt, so the result does not depend on A or on the schedule.
   if (pending > 0 && attempt < ceiling) {
-    if (f->best_cap < (size_t)pending) {
-      (void)hipFree(f->d_best);
-      f->d_best = nullptr; f->best_cap = 0;
-      SF_TRY_SET(hipMalloc(&f->d_best, (size_t)pending * sizeof(uint32_t)));
-      f->best_cap = (size_t)pending;
-    }
+    SF_TRY_SET(f->d_best.grow((size_t)pending));
     SfSampleArgsHost p = a;  // plain launches
     p.q = nullptr; p.ring = nullptr; p.gal_acc = nullptr; p.n_drawn = nullptr;
     uint32_t window_end = attempt < 1024u ? 1024u : ((attempt > ceiling / 16u) ? ceiling : attempt * 16u);
@@ -837,7 +798,7 @@ int sf_flow_sample(sf_flow* f, const float* x, int64_t M, int64_t S, const float
     uint32_t k0, k1;
     seed_keys(seed, 0u, k0, k1);
     std::string err;
-    if (!f->ev_dense[0]) { SF_TRY_SET(hipEventCreate(&f->ev_dense[0])); SF_TRY_SET(hipEventCreate(&f->ev_dense[1])); }
+    SF_TRY_SET(f->ev_dense[0].create()); SF_TRY_SET(f->ev_dense[1].create());
     int64_t unf = 0;
     int rc = sf_nsfar_sample(f->nsfar, x, (long)M, (long)S, nullptr, (long)(M * S), lo, hi, k0, k1,
                              (unsigned long long)f->sample_row_offset * (unsigned long long)S, max_attempts, out, n_drawn, nullptr, &unf, st, err,
@@ -1001,9 +962,9 @@ int sf_flow_train_epoch_dp(sf_flow* f, float* flat, const float* theta, const fl
   struct WantSq { sf_flow* f; WantSq(sf_flow* f_, bool on) : f(f_) { f->want_sq = on; } ~WantSq() { f->want_sq = false; f->n_sqpart = 0; } } want_sq(f, comm == nullptr);
   // ... and the kernels add their loss sums to one of SF_LOSS_PARTS scalars instead of all to the caller's (folded in below)
   if (loss_sum && !f->d_losspart_mem) {
-    if (hipMalloc(&f->d_losspart_mem, SF_LOSS_PARTS * sizeof(double)) == hipSuccess)
+    if (f->d_losspart_mem.alloc(SF_LOSS_PARTS) == hipSuccess)
       (void)hipMemsetAsync(f->d_losspart_mem, 0, SF_LOSS_PARTS * sizeof(double), (hipStream_t)stream);
-    else { f->d_losspart_mem = nullptr; (void)hipGetLastError(); }
+    else (void)hipGetLastError();
   }
   struct Spread {
     sf_flow* f; double* out; hipStream_t st;
@@ -1092,9 +1053,8 @@ extern "C" {
 struct sf_opt {
   int64_t n = 0;
   sf_adam_desc d{};
-  float* m = nullptr;
-  float* v = nullptr;
-  float* norm = nullptr;  // device scalar: sum of squares
+  SfBuf<float> m, v;
+  SfBuf<float> norm;  // device scalar: sum of squares
   int64_t step = 0;
 };
 
@@ -1106,9 +1066,9 @@ int sf_opt_create(int64_t n, const sf_adam_desc* d, sf_opt** out) {
   sf_opt* o = new sf_opt();
   o->n = n;
   o->d = *d;
-  hipError_t e = hipMalloc(&o->m, (size_t)n * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&o->v, (size_t)n * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&o->norm, sizeof(float));
+  hipError_t e = o->m.alloc((size_t)n);
+  if (e == hipSuccess) e = o->v.alloc((size_t)n);
+  if (e == hipSuccess) e = o->norm.alloc(1);
   if (e == hipSuccess) e = hipMemset(o->m, 0, (size_t)n * sizeof(float));
   if (e == hipSuccess) e = hipMemset(o->v, 0, (size_t)n * sizeof(float));
   if (e != hipSuccess) {
@@ -1118,11 +1078,7 @@ int sf_opt_create(int64_t n, const sf_adam_desc* d, sf_opt** out) {
   *out = o;
   return SF_OK;
 }
-void sf_opt_destroy(sf_opt* o) {
-  if (!o) return;
-  (void)hipFree(o->m); (void)hipFree(o->v); (void)hipFree(o->norm);
-  delete o;
-}
+void sf_opt_destroy(sf_opt* o) { delete o; }
 int sf_adam_step(sf_opt* o, float* params, const float* grad, float max_norm, float* grad_norm_out, void* stream) {
   if (!o || !params || !grad) return sf_fail(SF_ERR_INVALID, "null argument");
   o->step += 1;

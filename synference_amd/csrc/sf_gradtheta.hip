@@ -149,20 +149,14 @@ int sf_flow_log_prob_grad(sf_flow* f, const float* theta, const float* x, int64_
   if (dtheta && !f->gt_image_valid) {
     const size_t n = (size_t)L.n_packedT;
     if (!f->d_gtT) {
-      auto undo = [&]() {
-        (void)hipFree(f->d_gtT); (void)hipFree(f->d_gt1); (void)hipFree(f->d_gt2);
-        f->d_gtT = nullptr; f->d_gt1 = f->d_gt2 = nullptr;
-      };
-      hipError_t e = hipMalloc(&f->d_gtT, n * sizeof(float));
-      if (e == hipSuccess) e = hipMalloc(&f->d_gt1, n * sizeof(int32_t));
-      if (e == hipSuccess) e = hipMalloc(&f->d_gt2, n * sizeof(int32_t));
       // (blocking copies, once per handle: the tables are in place before the gather below is queued on any stream)
-      if (e == hipSuccess) e = hipMemcpy(f->d_gt1, L.srcT1.data(), n * sizeof(int32_t), hipMemcpyHostToDevice);
-      if (e == hipSuccess) e = hipMemcpy(f->d_gt2, L.srcT2.data(), n * sizeof(int32_t), hipMemcpyHostToDevice);
-      if (e != hipSuccess) {
-        undo();
-        return sf_fail(SF_ERR_HIP, std::string("transposed inference image: ") + hipGetErrorString(e));
-      }
+      SfFlowGt g;   // all or nothing
+      SF_TRY_SET(g.d_gtT.alloc(n));
+      SF_TRY_SET(g.d_gt1.alloc(n));
+      SF_TRY_SET(g.d_gt2.alloc(n));
+      SF_TRY_SET(hipMemcpy(g.d_gt1, L.srcT1.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
+      SF_TRY_SET(hipMemcpy(g.d_gt2, L.srcT2.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
+      static_cast<SfFlowGt&>(*f) = std::move(g);
     }
     SF_TRY_SET(sf_launch_pack(f->d_flat, f->d_gt1, f->d_gt2, f->d_gtT, (long)n, st));
     f->gt_image_valid = true;
@@ -185,14 +179,8 @@ int sf_flow_log_prob_grad(sf_flow* f, const float* theta, const float* x, int64_
       if (per_launch > cap_tiles) per_launch = cap_tiles;
     }
     const size_t need = (size_t)per_launch * per_tile;
-    if (need > f->act_cap) {  // (the stash is scratch shared with the training kernels)
-      if (f->d_act) SF_TRY_SET(hipFree(f->d_act));
-      f->d_act = nullptr;
-      f->act_cap = 0;
-      SF_TRY_SET(hipMalloc(&f->d_act, need * sizeof(float)));
-      f->act_cap = need;
-    }
-    a.act = reinterpret_cast<float4*>(f->d_act);
+    SF_TRY_SET(f->d_act.grow(need));  // (the stash is scratch shared with the training kernels)
+    a.act = reinterpret_cast<float4*>(f->d_act.get());
   }
   const bool maf = m.kind == SF_MAF;
   for (long t0 = 0; t0 < tiles; t0 += per_launch) {

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sf_buf.h"
 #include "sf_layout.h"
 #include "sf_queue.h"
 
@@ -136,105 +137,114 @@ void sf_set_error(const std::string& msg);          // thread-local message behi
 int sf_fail(int code, const std::string& msg);      // sf_set_error(msg), then `code` for the caller to return
 // a HIP call that must succeed: on failure the message "<call>: <hip error>" and return SF_ERR_HIP.  _ERR writes the message
 // to the enclosing function's `std::string err` (helpers whose caller reports it), _SET makes it the thread's last error.
+// (An operation of an owner, sf_buf.h -- x.alloc(n), x.grow(n), x.upload(v), x.create() -- also names the runtime function that failed.)
+inline std::string sf_hip_message(const char* call, hipError_t e) {
+  std::string s = std::string(call) + ": ";
+  for (const char* op : {".alloc(", ".grow(", ".upload(", ".create("})
+    if (s.find(op) != std::string::npos) { s += std::string(sf_buf_last_call()) + ": "; break; }
+  return s + hipGetErrorString(e);
+}
 #define SF_TRY_ERR(call)                                                     \
   do {                                                                       \
     hipError_t e_ = (call);                                                  \
     if (e_ != hipSuccess) {                                                  \
-      err = std::string(#call) + ": " + hipGetErrorString(e_);               \
+      err = sf_hip_message(#call, e_);                                       \
       return SF_ERR_HIP;                                                     \
     }                                                                        \
   } while (0)
 #define SF_TRY_SET(call)                                                                                   \
   do {                                                                                                     \
     hipError_t e_ = (call);                                                                                \
-    if (e_ != hipSuccess) return sf_fail(SF_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));   \
+    if (e_ != hipSuccess) return sf_fail(SF_ERR_HIP, sf_hip_message(#call, e_));                          \
   } while (0)
 struct sf_comm;
 int sf_comm_all_reduce_impl(sf_comm* c, float* buf, long n, hipStream_t st);  // sf_comm.hip: ncclAllReduce(SUM, fp32) in place
 
-// ---- the handle (shared by sf_api.hip and sf_train.hip) -------------------------------------
+// ---- the handle (shared by sf_api.hip, sf_train.hip and sf_gradtheta.hip) ----------------------
+// Every d_* / h_* / ev_* member owns what it points to (sf_buf.h): sf_flow_destroy is `delete`.  Buffers that are built together,
+// all or nothing, form a struct that the handle inherits (so that their names read as before): the builder fills a local one and
+// moves it in, and a group that has to grow is first assigned an empty one (free before malloc).
 #define SF_LOSS_PARTS 64
 #define SF_MAX_ROUNDS 80
 struct SfNsf1;
-struct sf_flow {
+struct SfFlowDev {   // ensure_device (sf_api.hip)
+  SfBuf<float> d_packed;        // forward operand image
+  SfBuf<float> d_cst;
+  SfBuf<int32_t> d_s1, d_s2;
+  SfBuf<float> d_packed16;      // 16-row image of the incremental MAF inverse (sf_maf16.hip)
+  SfBuf<int32_t> d_s16a, d_s16b;
+  SfBuf<unsigned short> d_packed16B;  // split-bf16 hidden blocks of the 16-row sampler (sf_layout.h)
+  SfBuf<int32_t> d_s16B;
+  SfBuf<unsigned short> d_packedB;    // bf16 hidden operand image (hidden_bf16)
+  SfBuf<int32_t> d_bsrc;
+  SfBuf<float> d_flat;          // staging for host-sourced parameters
+  SfBuf<uint32_t> d_cnt;        // SF_MAX_ROUNDS rejected-slot counters (one per round of a sf_flow_sample call)
+  SfPinned<uint32_t> h_cnt;     // pinned host mirror for the per-round read-back
+  SfEvent ev_dense[2];          // brackets round 0 of the last sf_flow_sample call
+};
+struct SfFlowTrain {   // the `train_ready` group (sf_train.hip)
+  SfBuf<float> d_packedT;       // transposed operand image (training, lazily built)
+  SfBuf<int32_t> d_t1, d_t2;
+  SfBuf<float> d_gpacked;       // gradient image replicas (accumulation target)
+  SfBuf<int32_t> d_gdst;        // logical parameter -> gradient image index
+};
+struct SfFlowTrainC {  // the `trainc_ready` group: cooperative 16-row training path (sf_trainc.hip), operand image and gather tables
+  SfBuf<float> d_imgC;
+  SfBuf<int32_t> d_sC1, d_sC2, d_gdstC;
+  SfBuf<int32_t> d_gsrcC;       // inverse of gdstC: [n_gradC][2] parameters fed by a position of the gradient partial (-1: none); null: not invertible
+  SfBuf<int32_t> d_gzeroC;      // parameters without a position (their gradient is 0)
+  long n_gzeroC = 0;
+};
+// transposed INFERENCE image of sf_flow_log_prob_grad (sf_gradtheta.hip): built from d_flat on the first gradient call after
+// sf_flow_set_params, valid until the next one; buffers of its own, training's d_packedT is rebuilt per call from the caller's vector
+struct SfFlowGt {
+  SfBuf<float> d_gtT;
+  SfBuf<int32_t> d_gt1, d_gt2;
+};
+struct SfFlowRej { SfBuf<uint32_t> d_rej[2]; };   // rejected-slot lists of the persistent sampler, one capacity
+struct sf_flow : SfFlowDev, SfFlowTrain, SfFlowTrainC, SfFlowGt, SfFlowRej {
   SfLayout L;
   struct SfNsfAr* nsfar = nullptr;   // != null: the autoregressive NSF (sf_nsfar.hip); L carries the shape and n_params only
   SfNsf1* nsf1 = nullptr;       // != null: the one-parameter NSF (sf_nsf1.hip); L then only carries the shape and n_params
+  ~sf_flow();                   // sf_api.hip: the two sub-handles
   bool dev_ready = false;
   bool params_set = false;
   bool train_ready = false;     // every lazily built training buffer exists (sf_train.hip)
   bool flat_valid = false;      // d_flat holds the vector last given to sf_flow_set_params
-  float* d_packed = nullptr;    // forward operand image
-  float* d_packedT = nullptr;   // transposed operand image (training, lazily built)
-  // transposed INFERENCE image of sf_flow_log_prob_grad (sf_gradtheta.hip): built from d_flat on the first gradient call after
-  // sf_flow_set_params, valid until the next one; buffers of its own, training's d_packedT is rebuilt per call from the caller's vector
-  float* d_gtT = nullptr;
-  int32_t *d_gt1 = nullptr, *d_gt2 = nullptr;
   bool gt_image_valid = false;
   long gt_simds = 0;            // SIMDs of the handle's device (4 per CU), asked once: the width a stash-bounded launch keeps
-  float* d_cst = nullptr;
-  unsigned short* d_packedB = nullptr;  // bf16 hidden operand image (hidden_bf16)
-  int32_t* d_bsrc = nullptr;
-  float* d_packed16 = nullptr;          // 16-row image of the incremental MAF inverse (sf_maf16.hip)
   bool packed16_stale = false;          // loss_grad refreshed only the forward image
-  unsigned short* d_packed16B = nullptr;  // split-bf16 hidden blocks of the 16-row sampler (sf_layout.h)
-  int32_t* d_s16B = nullptr;
-  int32_t *d_s16a = nullptr, *d_s16b = nullptr;
-  int32_t *d_s1 = nullptr, *d_s2 = nullptr, *d_t1 = nullptr, *d_t2 = nullptr;
-  float* d_flat = nullptr;      // staging for host-sourced parameters
-  float* d_gpacked = nullptr;   // gradient image replicas (accumulation target)
-  size_t gpacked_cap = 0;       // floats
-  int32_t* d_gdst = nullptr;    // logical parameter -> gradient image index
-  // cooperative 16-row training path (sf_trainc.hip): operand image, its gather table, gradient partials
-  float* d_imgC = nullptr;
-  int32_t *d_sC1 = nullptr, *d_sC2 = nullptr, *d_gdstC = nullptr;
-  int32_t* d_gsrcC = nullptr;  // inverse of gdstC: [n_gradC][2] parameters fed by a position of the gradient partial (-1: none); nullptr: not invertible
-  int32_t* d_gzeroC = nullptr; // parameters without a position (their gradient is 0)
-  long n_gzeroC = 0;
-  float* d_gpartC = nullptr;
-  long long* d_gfixC = nullptr; // SF_FIX_REPLICAS int64 gradient images (fixed-point accumulation, sf_fixacc.h)
-  size_t gpartC_cap = 0;        // floats
+  SfBuf<float> d_gpartC;        // cooperative training: gradient partials
+  SfBuf<long long> d_gfixC;     // SF_FIX_REPLICAS int64 gradient images (fixed-point accumulation, sf_fixacc.h)
   bool trainc_ready = false;
-  float* d_ustash = nullptr;    // cooperative NSF training (sf_nsfc.hip): u / u' of every transform, [rows][T][16]
-  size_t ustash_cap = 0;        // floats
-  float* d_act = nullptr;       // activation stash (training)
-  size_t act_cap = 0;           // floats
-  uint32_t* d_rej[2] = {nullptr, nullptr};
-  size_t rej_cap = 0;
-  SfQueue* d_queue = nullptr;    // work-queue words of the persistent sampler (sf_queue.h)
-  SfQueue* h_queue = nullptr;    // pinned host mirror, read once per stage
-  unsigned long long* d_ring = nullptr;  // retry ring
-  uint64_t ring_cap = 0;         // entries (power of two)
+  SfBuf<float> d_ustash;        // cooperative NSF training (sf_nsfc.hip): u / u' of every transform, [rows][T][16]
+  SfBuf<float> d_act;           // activation stash (training)
+  SfBuf<SfQueue> d_queue;       // work-queue words of the persistent sampler (sf_queue.h)
+  SfPinned<SfQueue> h_queue;    // pinned host mirror, read once per stage
+  SfBuf<unsigned long long> d_ring;  // retry ring (a power of two of entries)
   bool ring_dirty = false;       // a persistent launch did not end cleanly: clear the ring before the next one
-  int32_t* d_galacc = nullptr;   // per-galaxy accepted-slot counter of a stage (progress rule)
-  uint32_t* d_best = nullptr;    // deep-tail windows: lowest accepted attempt per survivor (find launch -> resolve launch)
-  size_t best_cap = 0;
-  size_t galacc_cap = 0;
+  SfBuf<int32_t> d_galacc;       // per-galaxy accepted-slot counter of a stage (progress rule)
+  SfBuf<uint32_t> d_best;        // deep-tail windows: lowest accepted attempt per survivor (find launch -> resolve launch)
   // per-block shares of |grad|^2 from the gather of the last loss_grad (epoch loop only: want_sq); n_sqpart = 0: none
-  float* d_sqpart = nullptr;
-  size_t sqpart_cap = 0;
+  SfBuf<float> d_sqpart;
   int n_sqpart = 0;
   bool want_sq = false;
   bool prep_lite = false;     // epoch call, not its last step: only the cooperative training image is re-tiled per step
   bool packed_stale = false;  // the density / sampler images lag behind the training image (cleared by the next full re-tiling)
   // loss sums of an epoch call spread over SF_LOSS_PARTS device scalars (non-null only inside sf_flow_train_epoch), folded into
   // the caller's scalar at its end
-  double* d_losspart = nullptr;
-  double* d_losspart_mem = nullptr;
+  double* d_losspart = nullptr;      // (a view of d_losspart_mem, not an owner)
+  SfBuf<double> d_losspart_mem;
   bool losspart_used = false;
-  uint32_t* d_cnt = nullptr;     // SF_MAX_ROUNDS rejected-slot counters (one per round of a sf_flow_sample call)
-  uint32_t* h_cnt = nullptr;     // pinned host mirror for the per-round read-back
   bool wp_stale = true;              // the fused first-layer blocks (o16_wp) lag behind packed16: recomputed before the next context table
   bool sample_out_f64 = false;       // sf_flow_set_sample_output_f64: `out` of sf_flow_sample / _slots is a double array
   long long sample_row_offset = 0;   // sf_flow_set_sample_row_offset: first row of the next sampling calls in its catalogue
   double sample_time_limit_s = 0.0;  // > 0: sf_flow_sample* stop opening new attempt windows after this much wall time
   bool profiling = false;         // sf_flow_set_profiling: bracket the training flow kernel with HIP events
-  hipEvent_t ev_train[2] = {nullptr, nullptr};
+  SfEvent ev_train[2];
   bool ev_train_valid = false;
-  hipEvent_t ev_dense[2] = {nullptr, nullptr};  // brackets round 0 of the last sf_flow_sample call
   float last_stats[4] = {0.f, 0.f, 0.f, 0.f};   // dense-round ms, rounds, rejected after round 0, items evaluated
-  float* d_ctab = nullptr;       // per-galaxy context table (sf_flow_prepare_context)
-  size_t ctab_cap = 0;           // floats
+  SfBuf<float> d_ctab;           // per-galaxy context table (sf_flow_prepare_context)
   const float* ctab_x = nullptr; // context rows the table was built from (NULL = no valid table)
   int64_t ctab_M = 0;
   SfDev dev() const {
@@ -243,8 +253,8 @@ struct sf_flow {
     v.packedT = d_packedT;
     v.cst = d_cst;
     v.packedB = d_packedB;
-    v.packed16 = packed16_stale ? nullptr : d_packed16;
-    v.packed16B = reinterpret_cast<const uint32_t*>(d_packed16B);
+    v.packed16 = packed16_stale ? nullptr : d_packed16.get();
+    v.packed16B = reinterpret_cast<const uint32_t*>(d_packed16B.get());
     v.ctab = nullptr;  // set per launch by the sampler entry points
     return v;
   }

@@ -156,12 +156,14 @@ __global__ __launch_bounds__(256) void k_mlp_bwd(SfMlpDev m, SfMlpArgs a) {
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-struct sf_mlp {
+struct SfMlpBufs {   // built once, all or nothing (mlp_ensure)
+  SfBuf<float> d_packed, d_packedT, d_cst, d_gimg;
+  SfBuf<int32_t> d_s1, d_s2, d_t1, d_t2, d_gdst;
+};
+struct sf_mlp : SfMlpBufs {
   SfMlpLayout L;
   bool dev_ready = false;
-  float *d_packed = nullptr, *d_packedT = nullptr, *d_cst = nullptr, *d_gimg = nullptr, *d_act = nullptr;
-  int32_t *d_s1 = nullptr, *d_s2 = nullptr, *d_t1 = nullptr, *d_t2 = nullptr, *d_gdst = nullptr;
-  size_t act_cap = 0;
+  SfBuf<float> d_act;
   SfMlpDev dev() const {
     SfMlpDev v = L.dev;
     v.packed = d_packed; v.packedT = d_packedT; v.cst = d_cst;
@@ -185,19 +187,15 @@ int mlp_ensure(sf_mlp* m) {
     return SF_ERR_NO_DEVICE;
   }
   const SfMlpLayout& L = m->L;
-  auto up = [&](const std::vector<int32_t>& v, int32_t** d) -> hipError_t {
-    hipError_t e = hipMalloc(d, std::max<size_t>(v.size(), 1) * sizeof(int32_t));
-    if (e != hipSuccess) return e;
-    return hipMemcpy(*d, v.data(), v.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-  };
-  SF_TRY_SET(hipMalloc(&m->d_packed, (size_t)L.n_packed * sizeof(float)));
-  SF_TRY_SET(hipMalloc(&m->d_packedT, std::max<size_t>((size_t)L.n_packedT, 64) * sizeof(float)));
-  SF_TRY_SET(hipMalloc(&m->d_gimg, (size_t)L.n_packed * sizeof(float)));
-  SF_TRY_SET(hipMalloc(&m->d_cst, L.cst.size() * sizeof(float)));
-  SF_TRY_SET(hipMemcpy(m->d_cst, L.cst.data(), L.cst.size() * sizeof(float), hipMemcpyHostToDevice));
-  SF_TRY_SET(up(L.src1, &m->d_s1)); SF_TRY_SET(up(L.src2, &m->d_s2));
-  SF_TRY_SET(up(L.srcT1, &m->d_t1)); SF_TRY_SET(up(L.srcT2, &m->d_t2));
-  SF_TRY_SET(up(L.gdst, &m->d_gdst));
+  SfMlpBufs b;
+  SF_TRY_SET(b.d_packed.alloc((size_t)L.n_packed));
+  SF_TRY_SET(b.d_packedT.alloc(std::max<size_t>((size_t)L.n_packedT, 64)));
+  SF_TRY_SET(b.d_gimg.alloc((size_t)L.n_packed));
+  SF_TRY_SET(b.d_cst.upload(L.cst));
+  SF_TRY_SET(b.d_s1.upload(L.src1)); SF_TRY_SET(b.d_s2.upload(L.src2));
+  SF_TRY_SET(b.d_t1.upload(L.srcT1)); SF_TRY_SET(b.d_t2.upload(L.srcT2));
+  SF_TRY_SET(b.d_gdst.upload(L.gdst));
+  static_cast<SfMlpBufs&>(*m) = std::move(b);
   m->dev_ready = true;
   return SF_OK;
 }
@@ -236,15 +234,7 @@ int sf_mlp_create(const sf_mlp_desc* d, sf_mlp** out) {
   *out = m;
   return SF_OK;
 }
-void sf_mlp_destroy(sf_mlp* m) {
-  if (!m) return;
-  if (m->dev_ready) {
-    (void)hipFree(m->d_packed); (void)hipFree(m->d_packedT); (void)hipFree(m->d_cst); (void)hipFree(m->d_gimg);
-    (void)hipFree(m->d_act); (void)hipFree(m->d_s1); (void)hipFree(m->d_s2); (void)hipFree(m->d_t1);
-    (void)hipFree(m->d_t2); (void)hipFree(m->d_gdst);
-  }
-  delete m;
-}
+void sf_mlp_destroy(sf_mlp* m) { delete m; }
 int64_t sf_mlp_num_params(const sf_mlp* m) { return m ? m->L.n_params : 0; }
 
 int sf_mlp_forward(sf_mlp* m, const float* flat, const float* x, int64_t B, float* out, void* stream) {
@@ -278,19 +268,14 @@ int sf_mlp_backward(sf_mlp* m, const float* flat, const float* x, const float* d
   const long waves = (B + 31) / 32;
   const long act_per_wave = (long)std::max(1, (L.dev.L - 1) * L.dev.HT) * 4 * 64;
   const size_t need = (size_t)std::max<long>(waves, 1) * act_per_wave * 4;
-  if (need > m->act_cap) {
-    if (m->d_act) SF_TRY_SET(hipFree(m->d_act));
-    m->d_act = nullptr; m->act_cap = 0;
-    SF_TRY_SET(hipMalloc(&m->d_act, need * sizeof(float)));
-    m->act_cap = need;
-  }
+  SF_TRY_SET(m->d_act.grow(need));
   SF_TRY_SET(sf_launch_pack(flat, m->d_s1, m->d_s2, m->d_packed, (long)L.n_packed, st));
   if (L.n_packedT > 0) SF_TRY_SET(sf_launch_pack(flat, m->d_t1, m->d_t2, m->d_packedT, (long)L.n_packedT, st));
   SF_TRY_SET(hipMemsetAsync(m->d_gimg, 0, (size_t)L.n_packed * sizeof(float), st));
   if (B > 0) {
     SfMlpArgs a{};
     a.x = x; a.dout = dout; a.B = B; a.gimg = m->d_gimg;
-    a.act = reinterpret_cast<float4*>(m->d_act); a.act_per_wave = act_per_wave;
+    a.act = reinterpret_cast<float4*>(m->d_act.get()); a.act_per_wave = act_per_wave;
     const SfMlpDev d = m->dev();
     switch (d.HT) {
       case 1: SF_TRY_SET(launch_bwd<1>(d, a, st)); break;

@@ -6,6 +6,7 @@
 #include <string>
 
 #include "../../include/synference_hip.h"
+#include "sf_buf.h"
 
 #define SF_NSF1_TMAX 16   // transforms (the spline chain of the training kernel is unrolled over them)
 
@@ -15,15 +16,11 @@ struct SfNsf1 {
   int T = 0, C = 0, H = 0, K = 0, NP = 0;
   float tail_bound = 3.f, min_w = 1e-3f, min_h = 1e-3f, min_d = 1e-3f, inv_sqrt_h = 1.f, deriv_const = 0.f;
   float th_mean = 0.f, th_std = 1.f;
-  float* d_q = nullptr;     // [T][rows][3K - 1] raw spline parameters
-  size_t q_cap = 0;
-  float* d_dq = nullptr;    // their gradients
-  size_t dq_cap = 0;
-  float* d_xg = nullptr;    // gathered mini-batch rows (sf_flow_loss_grad_rows)
-  size_t xg_cap = 0;
-  float* d_thg = nullptr;
-  size_t thg_cap = 0;
-  unsigned int* d_cnt = nullptr;
+  ~SfNsf1();                // sf_nsf1.hip: the MLP handle
+  SfBuf<float> d_q;         // [T][rows][3K - 1] raw spline parameters
+  SfBuf<float> d_dq;        // their gradients
+  SfBuf<float> d_xg, d_thg; // gathered mini-batch rows (sf_flow_loss_grad_rows)
+  SfBuf<unsigned int> d_cnt;
 };
 
 int sf_nsf1_create(const sf_flow_desc& d, SfNsf1** out, std::string& err);

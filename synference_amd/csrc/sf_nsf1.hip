@@ -214,16 +214,6 @@ Nsf1C consts_of(const SfNsf1& n) {
     }                                                                       \
   } while (0)
 
-int grow(float*& p, size_t& cap, size_t need, std::string& err) {
-  if (need <= cap) return SF_OK;
-  if (p) SF_TRY_ERR(hipFree(p));
-  p = nullptr;
-  cap = 0;
-  SF_TRY_ERR(hipMalloc(&p, need * sizeof(float)));
-  cap = need;
-  return SF_OK;
-}
-
 // q[t][row][:] = MLP_t(x[row]) for every transform, with the parameters in `flat` (device)
 int conditioner(SfNsf1& n, const float* flat, const float* x, long rows, float* q, hipStream_t st, std::string& err) {
   for (int t = 0; t < n.T; ++t)
@@ -255,18 +245,13 @@ int sf_nsf1_create(const sf_flow_desc& d, SfNsf1** out, std::string& err) {
   return SF_OK;
 }
 
-void sf_nsf1_destroy(SfNsf1* n) {
-  if (!n) return;
-  sf_mlp_destroy(n->mlp);
-  (void)hipFree(n->d_q); (void)hipFree(n->d_dq); (void)hipFree(n->d_xg); (void)hipFree(n->d_thg); (void)hipFree(n->d_cnt);
-  delete n;
-}
+SfNsf1::~SfNsf1() { sf_mlp_destroy(mlp); }
+void sf_nsf1_destroy(SfNsf1* n) { delete n; }
 
 int sf_nsf1_log_prob(SfNsf1* n, const float* flat, const float* theta, const float* x, long B, float* out, hipStream_t st,
                      std::string& err) {
-  int rc = grow(n->d_q, n->q_cap, (size_t)n->T * B * n->NP, err);
-  if (rc) return rc;
-  rc = conditioner(*n, flat, x, B, n->d_q, st, err);
+  SF_TRY_ERR(n->d_q.grow((size_t)n->T * B * n->NP));
+  int rc = conditioner(*n, flat, x, B, n->d_q, st, err);
   if (rc) return rc;
   hipLaunchKernelGGL(k_nsf1_logprob, dim3((unsigned)((B + 127) / 128)), dim3(128), 0, st, n->d_q, theta, B, consts_of(*n), out);
   SF_TRY_ERR(hipGetLastError());
@@ -275,9 +260,8 @@ int sf_nsf1_log_prob(SfNsf1* n, const float* flat, const float* theta, const flo
 
 int sf_nsf1_inverse(SfNsf1* n, const float* flat, const float* z, const float* x, long B, float* theta, float* logdet,
                     hipStream_t st, std::string& err) {
-  int rc = grow(n->d_q, n->q_cap, (size_t)n->T * B * n->NP, err);
-  if (rc) return rc;
-  rc = conditioner(*n, flat, x, B, n->d_q, st, err);
+  SF_TRY_ERR(n->d_q.grow((size_t)n->T * B * n->NP));
+  int rc = conditioner(*n, flat, x, B, n->d_q, st, err);
   if (rc) return rc;
   hipLaunchKernelGGL(k_nsf1_inverse, dim3((unsigned)((B + 127) / 128)), dim3(128), 0, st, n->d_q, z, B, consts_of(*n), theta, logdet);
   SF_TRY_ERR(hipGetLastError());
@@ -293,14 +277,14 @@ int sf_nsf1_loss_grad(SfNsf1* n, const float* flat, const float* theta, const fl
   }
   int rc;
   if (idx) {  // the mini-batch gather (the MLP engine reads contiguous rows)
-    if ((rc = grow(n->d_xg, n->xg_cap, (size_t)B * n->C, err)) || (rc = grow(n->d_thg, n->thg_cap, (size_t)B, err))) return rc;
+    SF_TRY_ERR(n->d_xg.grow((size_t)B * n->C)); SF_TRY_ERR(n->d_thg.grow((size_t)B));
     const long tot = B * (n->C + 1);
     hipLaunchKernelGGL(k_nsf1_gather, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, theta, x, idx, B, n->C, n->d_thg, n->d_xg);
     SF_TRY_ERR(hipGetLastError());
     theta = n->d_thg;
     x = n->d_xg;
   }
-  if ((rc = grow(n->d_q, n->q_cap, (size_t)n->T * B * n->NP, err)) || (rc = grow(n->d_dq, n->dq_cap, (size_t)n->T * B * n->NP, err))) return rc;
+  SF_TRY_ERR(n->d_q.grow((size_t)n->T * B * n->NP)); SF_TRY_ERR(n->d_dq.grow((size_t)n->T * B * n->NP));
   rc = conditioner(*n, flat, x, B, n->d_q, st, err);
   if (rc) return rc;
   hipLaunchKernelGGL(k_nsf1_train, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, n->d_q, theta, B, consts_of(*n), grad_scale, weights,
@@ -314,11 +298,10 @@ int sf_nsf1_loss_grad(SfNsf1* n, const float* flat, const float* theta, const fl
 int sf_nsf1_sample(SfNsf1* n, const float* flat, const float* x, long M, long S, const uint32_t* slots, long n_slots,
                    const float* lo, const float* hi, uint32_t k0, uint32_t k1, unsigned long long slot_offset, int max_attempts,
                    float* out, int32_t* n_drawn, int64_t* n_unfilled, hipStream_t st, std::string& err) {
-  int rc = grow(n->d_q, n->q_cap, (size_t)n->T * M * n->NP, err);
+  SF_TRY_ERR(n->d_q.grow((size_t)n->T * M * n->NP));
+  int rc = conditioner(*n, flat, x, M, n->d_q, st, err);
   if (rc) return rc;
-  rc = conditioner(*n, flat, x, M, n->d_q, st, err);
-  if (rc) return rc;
-  if (!n->d_cnt) SF_TRY_ERR(hipMalloc(&n->d_cnt, sizeof(unsigned int)));
+  if (!n->d_cnt) SF_TRY_ERR(n->d_cnt.alloc(1));
   SF_TRY_ERR(hipMemsetAsync(n->d_cnt, 0, sizeof(unsigned int), st));
   // no ceiling asked for: 2^22 attempts per slot (the engine's other samplers give a galaxy up once 1e5 attempts of its open
   // slots brought no draw; a scalar slot that failed four million attempts is in the same state)
@@ -335,9 +318,8 @@ int sf_nsf1_sample(SfNsf1* n, const float* flat, const float* x, long M, long S,
 
 int sf_nsf1_acceptance(SfNsf1* n, const float* flat, const float* x, long M, long cnt, const float* lo, const float* hi, uint32_t k0,
                        uint32_t k1, unsigned long long slot_offset, int32_t* count, hipStream_t st, std::string& err) {
-  int rc = grow(n->d_q, n->q_cap, (size_t)n->T * M * n->NP, err);
-  if (rc) return rc;
-  rc = conditioner(*n, flat, x, M, n->d_q, st, err);
+  SF_TRY_ERR(n->d_q.grow((size_t)n->T * M * n->NP));
+  int rc = conditioner(*n, flat, x, M, n->d_q, st, err);
   if (rc) return rc;
   const long tot = M * cnt;
   hipLaunchKernelGGL(k_nsf1_accept, dim3((unsigned)((tot + 127) / 128)), dim3(128), 0, st, n->d_q, M, cnt, consts_of(*n), lo, hi, k0, k1,

@@ -8,8 +8,19 @@
 #include <vector>
 
 #include "../../include/synference_hip.h"
+#include "sf_buf.h"
 
-struct SfNsfAr {
+// device state built once, all or nothing (ar_ensure): a local one is filled and moved into the handle
+struct SfNsfArDev {
+  SfBuf<float> d_img;
+  SfBuf<int32_t> d_src, d_none, d_perm, d_ptype, d_tend, d_ord, d_dimof, d_dwave;
+  SfBuf<float> d_xmean, d_xstd;
+  SfBuf<unsigned char> d_live;           // [n_params] 1 = the parameter has a gradient (unmasked weight or bias)
+  SfPinned<unsigned long long> h_ctr;    // pinned host copy of d_ctr (read back after the persistent launch and after every round)
+  SfBuf<unsigned long long> d_ctr;       // [0] work cursor of the sampler, [1] slots written off, [2] evaluations, [3] first attempts rejected
+};
+struct SfNsfArSurv { SfBuf<uint32_t> d_surv[2], d_best; };   // survivor lists of the find / resolve rounds, lowest accepted attempt: one capacity
+struct SfNsfAr : SfNsfArDev, SfNsfArSurv {
   int D = 0, C = 0, H = 0, Hp = 0, T = 0, K = 0, NP = 0;
   float bound = 5.f, cw = 0.f, cd = 0.f, logdet0 = 0.f;
   float th_scale[16], th_shift[16];
@@ -27,21 +38,10 @@ struct SfNsfAr {
   // its tile), biases in that order
   int s16_nt = 0, s16_ni = 0, s16_ks = 4, s16_tpt = 1, o_F0 = 0, o_fb0 = 0, o_F1 = 0, o_fb1 = 0, o_F2 = 0;
   bool dev_ready = false;
-  float* d_img = nullptr;
-  int32_t *d_src = nullptr, *d_none = nullptr, *d_perm = nullptr, *d_ptype = nullptr, *d_tend = nullptr, *d_ord = nullptr, *d_dimof = nullptr, *d_dwave = nullptr;
-  float *d_xmean = nullptr, *d_xstd = nullptr;
   int affine = 0;               // SF_MAF_AR (zuko MAF): MonotonicAffineTransform instead of the spline
-  float* d_ustash = nullptr;
-  size_t ustash_cap = 0;
-  unsigned char* d_live = nullptr;   // [n_params] 1 = the parameter has a gradient (unmasked weight or bias)
-  float* d_gpart = nullptr;          // per-workgroup gradient partials of the training kernel (small batches)
-  size_t gpart_cap = 0;
-  int32_t* d_gal = nullptr;              // [2][M]: attempts / accepted draws per row (progress rule of the uncapped sampler)
-  size_t gal_cap = 0;
-  unsigned long long* h_ctr = nullptr;   // pinned host copy of d_ctr (read back after the persistent launch and after every round)
-  unsigned long long* d_ctr = nullptr;   // [0] work cursor of the sampler, [1] slots written off, [2] evaluations, [3] first attempts rejected
-  uint32_t *d_surv[2] = {nullptr, nullptr}, *d_best = nullptr;   // survivor lists of the find / resolve rounds, lowest accepted attempt
-  size_t surv_cap = 0;
+  SfBuf<float> d_ustash;
+  SfBuf<float> d_gpart;              // per-workgroup gradient partials of the training kernel (small batches)
+  SfBuf<int32_t> d_gal;              // [2][M]: attempts / accepted draws per row (progress rule of the uncapped sampler)
   double last_evals = 0.0, last_rej0 = 0.0;   // of the last sampling call that read the counters back
 };
 

@@ -1146,42 +1146,32 @@ int sf_nsfar_create(const sf_flow_desc& d, SfNsfAr** out, std::string& err) {
   return SF_OK;
 }
 
-void sf_nsfar_destroy(SfNsfAr* n) {
-  if (!n) return;
-  (void)hipFree(n->d_img); (void)hipFree(n->d_src); (void)hipFree(n->d_none); (void)hipFree(n->d_perm); (void)hipFree(n->d_ptype); (void)hipFree(n->d_tend);
-  (void)hipFree(n->d_ord); (void)hipFree(n->d_dimof); (void)hipFree(n->d_dwave); (void)hipFree(n->d_xmean); (void)hipFree(n->d_xstd); (void)hipFree(n->d_ustash);
-  (void)hipFree(n->d_ctr); (void)hipHostFree(n->h_ctr); (void)hipFree(n->d_live); (void)hipFree(n->d_gpart); (void)hipFree(n->d_gal); (void)hipFree(n->d_surv[0]); (void)hipFree(n->d_surv[1]); (void)hipFree(n->d_best);
-  delete n;
-}
+void sf_nsfar_destroy(SfNsfAr* n) { delete n; }
 
 static int ar_ensure(SfNsfAr* n, std::string& err) {
   if (n->dev_ready) return SF_OK;
-  auto up = [&](auto*& dst, const auto& v) -> hipError_t {
-    using T = typename std::remove_reference<decltype(v[0])>::type;
-    hipError_t e = hipMalloc(&dst, v.size() * sizeof(T));
-    if (e != hipSuccess) return e;
-    return hipMemcpy(dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-  };
-  SF_TRY_ERR(hipMalloc(&n->d_img, n->src.size() * sizeof(float)));
-  SF_TRY_ERR(up(n->d_src, n->src)); SF_TRY_ERR(up(n->d_perm, n->perm)); SF_TRY_ERR(up(n->d_ptype, n->ptype)); SF_TRY_ERR(up(n->d_tend, n->tend));
-  SF_TRY_ERR(up(n->d_ord, n->ord)); SF_TRY_ERR(up(n->d_dimof, n->dimof)); SF_TRY_ERR(up(n->d_dwave, n->dwave)); SF_TRY_ERR(up(n->d_xmean, n->h_xmean)); SF_TRY_ERR(up(n->d_xstd, n->h_xstd));
+  SfNsfArDev d;   // all or nothing
+  SF_TRY_ERR(d.d_img.alloc(n->src.size()));
+  SF_TRY_ERR(d.d_src.upload(n->src)); SF_TRY_ERR(d.d_perm.upload(n->perm)); SF_TRY_ERR(d.d_ptype.upload(n->ptype)); SF_TRY_ERR(d.d_tend.upload(n->tend));
+  SF_TRY_ERR(d.d_ord.upload(n->ord)); SF_TRY_ERR(d.d_dimof.upload(n->dimof)); SF_TRY_ERR(d.d_dwave.upload(n->dwave)); SF_TRY_ERR(d.d_xmean.upload(n->h_xmean)); SF_TRY_ERR(d.d_xstd.upload(n->h_xstd));
   {   // live[i] = 1 where logical parameter i appears in an image (an unmasked weight or a bias): the entries a training workgroup writes
     std::vector<unsigned char> live((size_t)n->n_params, 0);
     for (int32_t v : n->src)
       if (v >= 0) live[(size_t)v] = 1;
-    SF_TRY_ERR(up(n->d_live, live));
+    SF_TRY_ERR(d.d_live.upload(live));
   }
-  SF_TRY_ERR(hipMalloc(&n->d_ctr, 8 * sizeof(unsigned long long)));
-  SF_TRY_ERR(hipHostMalloc((void**)&n->h_ctr, 8 * sizeof(unsigned long long), hipHostMallocDefault));   // [0] cursor [1] unfilled [2] evaluations [3] rejected first attempts [4], [5] survivor counts
+  SF_TRY_ERR(d.d_ctr.alloc(8));
+  SF_TRY_ERR(d.h_ctr.alloc(8));   // [0] cursor [1] unfilled [2] evaluations [3] rejected first attempts [4], [5] survivor counts
   {
     const std::vector<int32_t> none(n->src.size(), -1);
-    SF_TRY_ERR(up(n->d_none, none));
+    SF_TRY_ERR(d.d_none.upload(none));
   }
   const size_t lds = (size_t)160 * 1024 - 1024;   // (k_ar_sample also has 768 static bytes)
   SF_TRY_ERR(set_lds(k_ar_logprob<1>, lds)); SF_TRY_ERR(set_lds(k_ar_logprob<4>, lds)); SF_TRY_ERR(set_lds(k_ar_inverse, lds)); SF_TRY_ERR(set_lds(k_ar_sample, lds));
   SF_TRY_ERR(set_lds(k_ar_train<1, false>, lds)); SF_TRY_ERR(set_lds(k_ar_train<4, false>, lds));
   SF_TRY_ERR(set_lds(k_ar_train<1, true>, lds)); SF_TRY_ERR(set_lds(k_ar_train<4, true>, lds));
   SF_TRY_ERR(set_lds(k_ar_find, lds)); SF_TRY_ERR(set_lds(k_ar_resolve, lds));
+  static_cast<SfNsfArDev&>(*n) = std::move(d);
   n->dev_ready = true;
   return SF_OK;
 }
@@ -1263,12 +1253,7 @@ int sf_nsfar_sample(SfNsfAr* n, const float* x, long M, long S, const uint32_t* 
   const uint32_t cap = count ? 1u : (max_attempts > 0 ? (uint32_t)max_attempts : (1u << 20));
   int32_t* g_try = nullptr;
   if (!count && max_attempts <= 0 && lo) {
-    if ((size_t)(2 * M) > n->gal_cap) {
-      if (n->d_gal) SF_TRY_ERR(hipFree(n->d_gal));
-      n->d_gal = nullptr; n->gal_cap = 0;
-      SF_TRY_ERR(hipMalloc(&n->d_gal, (size_t)(2 * M) * sizeof(int32_t)));
-      n->gal_cap = (size_t)(2 * M);
-    }
+    SF_TRY_ERR(n->d_gal.grow((size_t)(2 * M)));
     SF_TRY_ERR(hipMemsetAsync(n->d_gal, 0, (size_t)(2 * M) * sizeof(int32_t), st));
     g_try = n->d_gal;
   }
@@ -1288,13 +1273,13 @@ int sf_nsfar_sample(SfNsfAr* n, const float* x, long M, long S, const uint32_t* 
     // (16-sample waves: an open entry costs a whole 16-candidate round of ONE wave per 16 attempts once the list has run dry, so the
     //  hand-over comes early -- measured on the bench flow: window 256 / 64 / 32 / 16 -> 8.35 / 7.84 / 6.93 / 7.29 ms per catalogue)
     window = sf_nsfar16_eligible(*n) ? 32u : 256u;
-    if ((size_t)n_slots > n->surv_cap) {
-      (void)hipFree(n->d_surv[0]); (void)hipFree(n->d_surv[1]); (void)hipFree(n->d_best);
-      n->d_surv[0] = n->d_surv[1] = n->d_best = nullptr; n->surv_cap = 0;
-      SF_TRY_ERR(hipMalloc(&n->d_surv[0], (size_t)n_slots * sizeof(uint32_t)));
-      SF_TRY_ERR(hipMalloc(&n->d_surv[1], (size_t)n_slots * sizeof(uint32_t)));
-      SF_TRY_ERR(hipMalloc(&n->d_best, (size_t)n_slots * sizeof(uint32_t)));
-      n->surv_cap = (size_t)n_slots;
+    if ((size_t)n_slots > n->d_best.cap()) {   // all three or none: release, build, move in
+      static_cast<SfNsfArSurv&>(*n) = SfNsfArSurv();
+      SfNsfArSurv v;
+      SF_TRY_ERR(v.d_surv[0].alloc((size_t)n_slots));
+      SF_TRY_ERR(v.d_surv[1].alloc((size_t)n_slots));
+      SF_TRY_ERR(v.d_best.alloc((size_t)n_slots));
+      static_cast<SfNsfArSurv&>(*n) = std::move(v);
     }
   }
   unsigned int* d_ns = reinterpret_cast<unsigned int*>(n->d_ctr + 4);   // [0], [1]: survivor counts of the two lists
@@ -1377,12 +1362,7 @@ int sf_nsfar_loss_grad(SfNsfAr* n, const float* flat, const float* theta, const 
     return SF_OK;
   }
   const size_t need = (size_t)B * n->T * n->D;
-  if (need > n->ustash_cap) {
-    if (n->d_ustash) SF_TRY_ERR(hipFree(n->d_ustash));
-    n->d_ustash = nullptr; n->ustash_cap = 0;
-    SF_TRY_ERR(hipMalloc(&n->d_ustash, need * sizeof(float)));
-    n->ustash_cap = need;
-  }
+  SF_TRY_ERR(n->d_ustash.grow(need));
   // Gradient accumulation: one partial per 64-row chunk + k_ar_gather (plain stores, summed in chunk order) while the partials fit
   // 512 MiB -- cfg1 shape: up to 2 300 chunks = 147 000 rows; 16 384 rows: 0.57 -> 0.36 ms, 131 072 rows: 3.0 -> 1.6 ms -- else f32
   // atomics into the one gradient (SF_AR_GRAD=atomic forces them).  Measured and dropped: 2 x CUs persistent workgroups that own a
@@ -1395,12 +1375,7 @@ int sf_nsfar_loss_grad(SfNsfAr* n, const float* flat, const float* theta, const 
   const bool part = force != 1 && part_bytes <= ((size_t)512 << 20);
   const long nwg = n_chunks;
   if (part) {
-    if (part_bytes > n->gpart_cap) {
-      if (n->d_gpart) SF_TRY_ERR(hipFree(n->d_gpart));
-      n->d_gpart = nullptr; n->gpart_cap = 0;
-      SF_TRY_ERR(hipMalloc(&n->d_gpart, part_bytes));
-      n->gpart_cap = part_bytes;
-    }
+    SF_TRY_ERR(n->d_gpart.grow(part_bytes / sizeof(float)));
   } else {
     SF_TRY_ERR(hipMemsetAsync(grad, 0, (size_t)n->n_params * sizeof(float), st));
   }

@@ -272,12 +272,7 @@ static float* sq_for(sf_flow* f, const SfLayout& L) {
   f->n_sqpart = 0;
   if (!f->want_sq) return nullptr;
   const long nb = sf_gather_c2_blocks((long)L.n_gradC, f->n_gzeroC);
-  if ((size_t)nb > f->sqpart_cap) {
-    (void)hipFree(f->d_sqpart);
-    f->d_sqpart = nullptr; f->sqpart_cap = 0;
-    if (hipMalloc(&f->d_sqpart, (size_t)nb * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    f->sqpart_cap = (size_t)nb;
-  }
+  if (f->d_sqpart.grow((size_t)nb) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
   f->n_sqpart = (int)nb;
   return f->d_sqpart;
 }
@@ -296,7 +291,7 @@ int sf_train_loss_grad(sf_flow* f, const float* flat, const float* theta, const 
     if (dctx) { err = "the autoregressive NSF has no context-gradient path"; return SF_ERR_INVALID; }
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (f->profiling) {
-      if (!f->ev_train[0]) { SF_TRY_ERR(hipEventCreate(&f->ev_train[0])); SF_TRY_ERR(hipEventCreate(&f->ev_train[1])); }
+      SF_TRY_ERR(f->ev_train[0].create()); SF_TRY_ERR(f->ev_train[1].create());
       e0 = f->ev_train[0]; e1 = f->ev_train[1];
     }
     const int rc = sf_nsfar_loss_grad(f->nsfar, flat, theta, x, idx, B, grad_scale, weights, loss, loss_sum, grad, st, err, e0, e1);
@@ -309,27 +304,14 @@ int sf_train_loss_grad(sf_flow* f, const float* flat, const float* theta, const 
   const bool coop_nsf = B > 0 && !coop_maf && sf_nsfc_eligible(L, dctx != nullptr);
   if (coop_maf || coop_nsf) {
     if (!f->trainc_ready) {
-      auto undo = [&]() {
-        (void)hipFree(f->d_imgC); (void)hipFree(f->d_sC1); (void)hipFree(f->d_sC2); (void)hipFree(f->d_gdstC);
-        (void)hipFree(f->d_gsrcC); (void)hipFree(f->d_gzeroC);
-        f->d_imgC = nullptr; f->d_sC1 = f->d_sC2 = f->d_gdstC = f->d_gsrcC = f->d_gzeroC = nullptr; f->n_gzeroC = 0;
-      };
-#define SF_TRY_C(call)                                                       \
-  do {                                                                       \
-    hipError_t e_ = (call);                                                  \
-    if (e_ != hipSuccess) {                                                  \
-      err = std::string(#call) + ": " + hipGetErrorString(e_);               \
-      undo();                                                                \
-      return SF_ERR_HIP;                                                     \
-    }                                                                        \
-  } while (0)
-      SF_TRY_C(hipMalloc(&f->d_imgC, (size_t)L.n_imgC * sizeof(float)));
-      SF_TRY_C(hipMalloc(&f->d_sC1, (size_t)L.n_imgC * sizeof(int32_t)));
-      SF_TRY_C(hipMalloc(&f->d_sC2, (size_t)L.n_imgC * sizeof(int32_t)));
-      SF_TRY_C(hipMemcpy(f->d_sC1, L.srcC1.data(), (size_t)L.n_imgC * sizeof(int32_t), hipMemcpyHostToDevice));
-      SF_TRY_C(hipMemcpy(f->d_sC2, L.srcC2.data(), (size_t)L.n_imgC * sizeof(int32_t), hipMemcpyHostToDevice));
-      SF_TRY_C(hipMalloc(&f->d_gdstC, (size_t)L.n_params * sizeof(int32_t)));
-      SF_TRY_C(hipMemcpy(f->d_gdstC, L.gdstC.data(), (size_t)L.n_params * sizeof(int32_t), hipMemcpyHostToDevice));
+      SfFlowTrainC c;   // all or nothing: moved into the handle once it is complete
+      SF_TRY_ERR(c.d_imgC.alloc((size_t)L.n_imgC));
+      SF_TRY_ERR(c.d_sC1.alloc((size_t)L.n_imgC));
+      SF_TRY_ERR(c.d_sC2.alloc((size_t)L.n_imgC));
+      SF_TRY_ERR(hipMemcpy(c.d_sC1, L.srcC1.data(), (size_t)L.n_imgC * sizeof(int32_t), hipMemcpyHostToDevice));
+      SF_TRY_ERR(hipMemcpy(c.d_sC2, L.srcC2.data(), (size_t)L.n_imgC * sizeof(int32_t), hipMemcpyHostToDevice));
+      SF_TRY_ERR(c.d_gdstC.alloc((size_t)L.n_params));
+      SF_TRY_ERR(hipMemcpy(c.d_gdstC, L.gdstC.data(), (size_t)L.n_params * sizeof(int32_t), hipMemcpyHostToDevice));
       {
         // position -> parameter(s), for the gather that walks the partials in THEIR order (coalesced reads): a position
         // feeds at most two parameters (b0 and bc share one); if the packer ever maps more, the parameter-order gather stays
@@ -344,16 +326,12 @@ int sf_train_loss_grad(sf_flow* f, const float* flat, const float* theta, const 
           else ok = false;
         }
         if (ok) {
-          SF_TRY_C(hipMalloc(&f->d_gsrcC, inv.size() * sizeof(int32_t)));
-          SF_TRY_C(hipMemcpy(f->d_gsrcC, inv.data(), inv.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-          f->n_gzeroC = (long)zero.size();
-          if (!zero.empty()) {
-            SF_TRY_C(hipMalloc(&f->d_gzeroC, zero.size() * sizeof(int32_t)));
-            SF_TRY_C(hipMemcpy(f->d_gzeroC, zero.data(), zero.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-          }
+          SF_TRY_ERR(c.d_gsrcC.upload(inv));
+          c.n_gzeroC = (long)zero.size();
+          if (!zero.empty()) SF_TRY_ERR(c.d_gzeroC.upload(zero));
         }
       }
-#undef SF_TRY_C
+      static_cast<SfFlowTrainC&>(*f) = std::move(c);
       f->trainc_ready = true;
     }
     const int grid = coop_maf ? sf_trainc_grid(B, &L.trc, L.dev.T) : sf_nsfc_grid(B, L.nsc.NT);
@@ -363,18 +341,11 @@ int sf_train_loss_grad(sf_flow* f, const float* flat, const float* theta, const 
     const int nsf_mode = coop_nsf ? sf_nsfc_acc_mode(B, grid, (long)L.n_gradC) : 0;
     bool use_fix = coop_nsf ? nsf_mode != 0 : sf_trainc_fix(grid, (long)L.n_gradC);
     if (!f->d_gsrcC) use_fix = false;
-    if (use_fix && !f->d_gfixC) {
-      SF_TRY_ERR(hipMalloc(&f->d_gfixC, (size_t)SF_FIX_REPLICAS * (size_t)L.n_gradC * sizeof(long long)));
-    }
+    if (use_fix && !f->d_gfixC) SF_TRY_ERR(f->d_gfixC.alloc((size_t)SF_FIX_REPLICAS * (size_t)L.n_gradC));
     if (use_fix) SF_TRY_ERR(hipMemsetAsync(f->d_gfixC, 0, (size_t)SF_FIX_REPLICAS * (size_t)L.n_gradC * sizeof(long long), st));
     const int n_part = use_fix ? 1 : grid;   // (fix: d_gpartC is only the base the job descriptors count from)
     const size_t need = (size_t)n_part * (size_t)L.n_gradC;
-    if (need > f->gpartC_cap) {
-      if (f->d_gpartC) SF_TRY_ERR(hipFree(f->d_gpartC));
-      f->d_gpartC = nullptr; f->gpartC_cap = 0;
-      SF_TRY_ERR(hipMalloc(&f->d_gpartC, need * sizeof(float)));
-      f->gpartC_cap = need;
-    }
+    SF_TRY_ERR(f->d_gpartC.grow(need));
     {
       // inside an epoch call (sf_flow_train_epoch, all steps but its last) only the cooperative image is re-tiled: the density
       // and sampler images are not read by the training kernels, and nobody can look at them before the call returns
@@ -398,12 +369,7 @@ int sf_train_loss_grad(sf_flow* f, const float* flat, const float* theta, const 
     if (coop_nsf) {
       const long n_chunks = (B + 31) / 32;
       const size_t ust_need = (size_t)n_chunks * 32 * (size_t)L.dev.T * 16;
-      if (ust_need > f->ustash_cap) {
-        if (f->d_ustash) SF_TRY_ERR(hipFree(f->d_ustash));
-        f->d_ustash = nullptr; f->ustash_cap = 0;
-        SF_TRY_ERR(hipMalloc(&f->d_ustash, ust_need * sizeof(float)));
-        f->ustash_cap = ust_need;
-      }
+      SF_TRY_ERR(f->d_ustash.grow(ust_need));
       const SfDev& v = L.dev;
       SfNscArgs a;
       a.c = L.nsc;
@@ -421,7 +387,7 @@ int sf_train_loss_grad(sf_flow* f, const float* flat, const float* theta, const 
       a.trace = nullptr;
 #endif
       if (f->profiling) {
-        if (!f->ev_train[0]) { SF_TRY_ERR(hipEventCreate(&f->ev_train[0])); SF_TRY_ERR(hipEventCreate(&f->ev_train[1])); }
+        SF_TRY_ERR(f->ev_train[0].create()); SF_TRY_ERR(f->ev_train[1].create());
         SF_TRY_ERR(hipEventRecord(f->ev_train[0], st));
       }
       SF_TRY_ERR(sf_launch_nsf_trainc(a, grid, st));
@@ -430,7 +396,7 @@ int sf_train_loss_grad(sf_flow* f, const float* flat, const float* theta, const 
         f->ev_train_valid = true;
       }
       if (use_fix && nsf_mode == 2)   // float replicas: the partial gather over SF_FIX_REPLICAS images
-        SF_TRY_ERR(sf_launch_gather_c2(reinterpret_cast<const float*>(f->d_gfixC), (long)L.n_gradC, SF_FIX_REPLICAS, f->d_gsrcC, f->d_gzeroC, f->n_gzeroC, grad, st, sq_for(f, L)));
+        SF_TRY_ERR(sf_launch_gather_c2(reinterpret_cast<const float*>(f->d_gfixC.get()), (long)L.n_gradC, SF_FIX_REPLICAS, f->d_gsrcC, f->d_gzeroC, f->n_gzeroC, grad, st, sq_for(f, L)));
       else if (use_fix) SF_TRY_ERR(sf_launch_gather_fix(f->d_gfixC, (long)L.n_gradC, SF_FIX_REPLICAS, f->d_gsrcC, f->d_gzeroC, f->n_gzeroC, grad, st));
       else if (f->d_gsrcC) SF_TRY_ERR(sf_launch_gather_c2(f->d_gpartC, (long)L.n_gradC, n_part, f->d_gsrcC, f->d_gzeroC, f->n_gzeroC, grad, st, sq_for(f, L)));
       else SF_TRY_ERR(sf_launch_gather_c(f->d_gpartC, (long)L.n_gradC, n_part, f->d_gdstC, grad, (long)L.n_params, st));
@@ -447,7 +413,7 @@ int sf_train_loss_grad(sf_flow* f, const float* flat, const float* theta, const 
     if (loss_sum && f->d_losspart) { a.loss_sum = f->d_losspart; a.loss_mask = SF_LOSS_PARTS - 1; f->losspart_used = true; }
     a.gpart = f->d_gpartC; a.gpart_stride = (long)L.n_gradC; a.fix = use_fix ? f->d_gfixC : nullptr;
     if (f->profiling) {
-      if (!f->ev_train[0]) { SF_TRY_ERR(hipEventCreate(&f->ev_train[0])); SF_TRY_ERR(hipEventCreate(&f->ev_train[1])); }
+      SF_TRY_ERR(f->ev_train[0].create()); SF_TRY_ERR(f->ev_train[1].create());
       SF_TRY_ERR(hipEventRecord(f->ev_train[0], st));
     }
     SF_TRY_ERR(sf_launch_maf_trainc(a, grid, st));
@@ -462,31 +428,17 @@ int sf_train_loss_grad(sf_flow* f, const float* flat, const float* theta, const 
   }
   // ---- lazily built training state
   if (!f->train_ready) {
-    // all-or-nothing: a failed allocation frees what was already taken, so that the next call starts over instead of
-    // launching kernels on half-built state
-    auto undo = [&]() {
-      (void)hipFree(f->d_packedT); (void)hipFree(f->d_t1); (void)hipFree(f->d_t2); (void)hipFree(f->d_gpacked); (void)hipFree(f->d_gdst);
-      f->d_packedT = nullptr; f->d_t1 = f->d_t2 = nullptr; f->d_gpacked = nullptr; f->d_gdst = nullptr; f->gpacked_cap = 0;
-    };
-#define SF_TRY_U(call)                                                       \
-  do {                                                                       \
-    hipError_t e_ = (call);                                                  \
-    if (e_ != hipSuccess) {                                                  \
-      err = std::string(#call) + ": " + hipGetErrorString(e_);               \
-      undo();                                                                \
-      return SF_ERR_HIP;                                                     \
-    }                                                                        \
-  } while (0)
-    SF_TRY_U(hipMalloc(&f->d_packedT, (size_t)L.n_packedT * sizeof(float)));
-    SF_TRY_U(hipMalloc(&f->d_t1, (size_t)L.n_packedT * sizeof(int32_t)));
-    SF_TRY_U(hipMalloc(&f->d_t2, (size_t)L.n_packedT * sizeof(int32_t)));
-    SF_TRY_U(hipMemcpy(f->d_t1, L.srcT1.data(), (size_t)L.n_packedT * sizeof(int32_t), hipMemcpyHostToDevice));
-    SF_TRY_U(hipMemcpy(f->d_t2, L.srcT2.data(), (size_t)L.n_packedT * sizeof(int32_t), hipMemcpyHostToDevice));
-    SF_TRY_U(hipMalloc(&f->d_gpacked, (size_t)SF_GCOPIES * L.n_packed * sizeof(float)));
-    f->gpacked_cap = (size_t)SF_GCOPIES * L.n_packed;
-    SF_TRY_U(hipMalloc(&f->d_gdst, (size_t)L.n_params * sizeof(int32_t)));
-    SF_TRY_U(hipMemcpy(f->d_gdst, L.gdst.data(), (size_t)L.n_params * sizeof(int32_t), hipMemcpyHostToDevice));
-#undef SF_TRY_U
+    // all-or-nothing: a failed allocation frees what was already taken (the local group), so that the next call starts over
+    // instead of launching kernels on half-built state
+    SfFlowTrain t;
+    SF_TRY_ERR(t.d_packedT.alloc((size_t)L.n_packedT));
+    SF_TRY_ERR(t.d_t1.alloc((size_t)L.n_packedT));
+    SF_TRY_ERR(t.d_t2.alloc((size_t)L.n_packedT));
+    SF_TRY_ERR(hipMemcpy(t.d_t1, L.srcT1.data(), (size_t)L.n_packedT * sizeof(int32_t), hipMemcpyHostToDevice));
+    SF_TRY_ERR(hipMemcpy(t.d_t2, L.srcT2.data(), (size_t)L.n_packedT * sizeof(int32_t), hipMemcpyHostToDevice));
+    SF_TRY_ERR(t.d_gpacked.alloc((size_t)SF_GCOPIES * L.n_packed));
+    SF_TRY_ERR(t.d_gdst.upload(L.gdst));
+    static_cast<SfFlowTrain&>(*f) = std::move(t);
     f->train_ready = true;
   }
   const SfDev& v = L.dev;
@@ -494,13 +446,7 @@ int sf_train_loss_grad(sf_flow* f, const float* flat, const float* theta, const 
   const long tiles_per_wave = (long)v.T * (v.kind == SF_MAF ? ((v.NB + 1) * v.HT + 1) : (2 + (3 * v.NB + 1) * v.HT));
   const long act_per_wave = tiles_per_wave * 4 * 64;  // float4
   const size_t need = (size_t)waves * act_per_wave * 4;
-  if (need > f->act_cap) {
-    if (f->d_act) SF_TRY_ERR(hipFree(f->d_act));
-    f->d_act = nullptr;
-    f->act_cap = 0;
-    SF_TRY_ERR(hipMalloc(&f->d_act, need * sizeof(float)));
-    f->act_cap = need;
-  }
+  SF_TRY_ERR(f->d_act.grow(need));
   // gradient accumulation: one replica per tile + plain stores (bitwise reproducible, and cheaper than atomics) up to
   // 16 tiles (batch 512: the reference's batch sizes), or whenever SF_DETERMINISTIC=1 and the replicas fit 2 GiB
   // (batch 2048: +15 % step time for zeroing and summing 64 replicas); else per-XCD replicas + f32 atomics
@@ -508,12 +454,7 @@ int sf_train_loss_grad(sf_flow* f, const float* flat, const float* theta, const 
   if (force_det < 0) { const char* e = std::getenv("SF_DETERMINISTIC"); force_det = e ? std::atoi(e) : 0; }
   const bool det = waves > 0 && (waves <= 16 || (force_det == 1 && (size_t)waves * L.n_packed * sizeof(float) <= ((size_t)2 << 30)));
   const int copies = det ? (int)waves : SF_GCOPIES;
-  if ((size_t)copies * L.n_packed > f->gpacked_cap) {
-    SF_TRY_ERR(hipFree(f->d_gpacked));
-    f->d_gpacked = nullptr; f->gpacked_cap = 0;
-    SF_TRY_ERR(hipMalloc(&f->d_gpacked, (size_t)copies * L.n_packed * sizeof(float)));
-    f->gpacked_cap = (size_t)copies * L.n_packed;
-  }
+  SF_TRY_ERR(f->d_gpacked.grow((size_t)copies * L.n_packed));
   {
     const long n4 = (dctx && B > 0) ? B * (long)L.dev.C : 0;
     const long n5 = f->d_packed16 ? (long)L.n_packed16 : 0;
@@ -531,11 +472,11 @@ int sf_train_loss_grad(sf_flow* f, const float* flat, const float* theta, const 
   if (B > 0) {
     SfTrainArgs a;
     a.theta = theta; a.x = x; a.idx = idx; a.loss_sum = loss_sum; a.B = B; a.w = grad_scale; a.wts = weights; a.loss = loss; a.dctx = dctx; a.gimg = f->d_gpacked; a.gimg_stride = (long)L.n_packed; a.det = det ? 1 : 0;
-    a.act = reinterpret_cast<float4*>(f->d_act); a.act_per_wave = act_per_wave;
+    a.act = reinterpret_cast<float4*>(f->d_act.get()); a.act_per_wave = act_per_wave;
     const SfDev m = f->dev();
     const bool maf = m.kind == SF_MAF;
     if (f->profiling) {
-      if (!f->ev_train[0]) { SF_TRY_ERR(hipEventCreate(&f->ev_train[0])); SF_TRY_ERR(hipEventCreate(&f->ev_train[1])); }
+      SF_TRY_ERR(f->ev_train[0].create()); SF_TRY_ERR(f->ev_train[1].create());
       SF_TRY_ERR(hipEventRecord(f->ev_train[0], st));
     }
     switch (m.HT) {

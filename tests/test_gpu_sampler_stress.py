@@ -155,3 +155,64 @@ def test_later_persistent_windows_equal_the_find_and_resolve_launches():
         lines.append([ln for ln in r.stdout.splitlines() if ln.startswith("DIGEST")][-1].split())
     assert lines[0][1] == lines[1][1] and lines[0][2] == lines[1][2] == "0", lines
     assert int(lines[0][4]) >= 3 and int(lines[1][4]) == 2, lines     # find / resolve pairs vs a second persistent launch
+
+
+# ---- a handle owns its device memory: created and dropped over and over, nothing stays behind and nothing changes --------------
+# Gradients that are reproducible from one handle to the next (measured on the code before the handles owned their buffers through
+# sf_buf.h, repetition 1 against repetition 2, and unchanged since): see _GRAD_REPRODUCIBLE.  The per-row losses, the draws and
+# log_prob are compared for every flow.
+_LIFETIME_FLOWS = ["maf_small", "nsf_nb1", "nsf_d1", "nsfar_small"]
+# (nsf_d1 at 200 rows: several waves of the MLP backward add their shares with float atomics, in the order they happen to arrive)
+_GRAD_REPRODUCIBLE = {"maf_small": (32, 200), "nsf_nb1": (32, 200), "nsf_d1": (32,), "nsfar_small": (32, 200)}
+
+
+def _free_bytes():
+    torch.cuda.synchronize()
+    return torch.cuda.mem_get_info()[0]
+
+
+def _handle_lifetime(spec, t):
+    """One life of a handle: parameters, two catalogues (the second larger: every sampler buffer grows), a density call and two
+    training batches (the second larger).  Returns the results (on the host: nothing of a repetition stays on the device) and the
+    free device memory just before the handle is dropped."""
+    f = HipFlow(spec, "cuda:0")
+    f.set_params(t["flat"])
+    f.set_sample_time_limit(60.0)
+    res = {}
+    for M, S in ((3, 5), (40, 300)):
+        res["draws_%dx%d" % (M, S)] = f.sample(t["x"][:M], S, t["lo"], t["hi"], seed=5, out=t["out_%d" % M]).cpu()
+    res["log_prob"] = f.log_prob(t["theta"], t["x"]).cpu()
+    for B in (32, 200):
+        loss, grad = f.loss_grad(t["flat"], t["theta"][:B], t["x"][:B], 1.0 / B)
+        res["loss_%d" % B], res["grad_%d" % B] = loss.cpu(), grad.cpu()
+    alive = _free_bytes()
+    del f
+    return res, alive
+
+
+@pytest.mark.parametrize("name", _LIFETIME_FLOWS)
+def test_handles_created_and_dropped_leave_no_memory_and_no_state_behind(name):
+    import gc
+    _, spec, flat, theta, x = make_case(name, B=200)
+    dev = torch.device("cuda:0")
+    mean, std = torch.as_tensor(spec.theta_mean), torch.as_tensor(spec.theta_std)
+    t = dict(flat=torch.as_tensor(flat, device=dev), theta=torch.as_tensor(theta, device=dev), x=torch.as_tensor(x, device=dev),
+             lo=(mean - 3 * std).to(dev), hi=(mean + 3 * std).to(dev),        # a box that most draws fall into
+             out_3=torch.empty((3, 5, spec.D), device=dev), out_40=torch.empty((40, 300, spec.D), device=dev))
+    first, free_1, footprint = None, None, None
+    for rep in range(8):
+        before = _free_bytes()
+        res, alive = _handle_lifetime(spec, t)
+        gc.collect()
+        after = _free_bytes()
+        if rep == 0:
+            first, free_1, footprint = res, after, before - alive
+            continue
+        if rep == 7:
+            for key, ref in first.items():
+                if key.startswith("grad_") and int(key[5:]) not in _GRAD_REPRODUCIBLE[name]:
+                    continue
+                assert torch.equal(res[key].view(torch.int32), ref.view(torch.int32)), (name, key)     # bit for bit (NaN rows too)
+            print(f"{name}: footprint of one handle {footprint} bytes, free after repetition 1 {free_1}, after repetition 8 {after}")
+            # one handle lost per repetition would be 7 footprints
+            assert free_1 - after <= max(footprint, 0), (name, footprint, free_1 - after)
