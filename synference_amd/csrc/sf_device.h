@@ -51,8 +51,16 @@ __device__ __forceinline__ float sf_sigmoid(float x) {
 __device__ __forceinline__ float sf_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
 __device__ __forceinline__ float sf_log(float x) { return __builtin_amdgcn_logf(x) * 0.6931471805599453f; }
 __device__ __forceinline__ float sf_div(float a, float b) { return a * __builtin_amdgcn_rcpf(b); }
-__device__ __forceinline__ float sf_softplus(float x) {  // torch: threshold 20
-  return x > 20.0f ? x : sf_log(1.0f + sf_exp(x));
+__device__ __forceinline__ float sf_softplus(float x) {  // torch's softplus (its threshold of 20 changes nothing in fp32)
+  // max(x, 0) + log1p(t), t = e^-|x|.  u = 1 + t keeps none of t's bits below 2^-24: at t = 1e-3 log(u) is off by 6e-5 relative, and
+  // eps + softplus is a MAF's scale and a spline's knot derivative (a sharp MAF's inverse was 12x further from the fp64 oracle than the
+  // fp32 oracle is: tests/test_gpu_sharp.py).  The rounding error of u is known exactly, d = t - (u - 1), and log(u + d) =
+  // log(u) + d / u; 1 / u = 2 - u to first order on [1, 2] (what is left is below 4e-8 relative).  The correction rides in the
+  // addend of the last multiply-add, beside the logarithm: same depth as log(1 + e^x).
+  const float t = sf_exp(-fabsf(x));
+  const float u = 1.0f + t;
+  const float d = t - (u - 1.0f);
+  return __builtin_fmaf(__builtin_amdgcn_logf(u), 0.6931471805599453f, __builtin_fmaf(d, 2.0f - u, fmaxf(x, 0.0f)));
 }
 // attempts-per-galaxy counters (n_drawn): int32, pinned at INT32_MAX once they would wrap (no attempt ceiling + S slots of
 // a galaxy that accepts one draw in a million: S x attempts passes 2^31).  An add that finds the counter too full to take it

@@ -120,8 +120,11 @@ def test_split_bf16_sampler_matches_oracle_draw_for_draw(name, sampler_mode):
     _draw_for_draw(name)
 
 
-def _draw_for_draw(name):
-    ospec, spec, flat, theta, x = make_case(name, B=6, spread=0.2)
+def _draw_for_draw(name, flat=None, case=make_case):
+    """``case``: a make_case-shaped factory (name, B=, spread=) for other weights on the same shapes; ``flat``: other parameters for
+    the factory's flow."""
+    ospec, spec, flat0, theta, x = case(name, B=6, spread=0.2)
+    flat = flat0 if flat is None else flat
     S, seed = 257, 2025
     # prior box from the 3%..97% quantiles of unbounded draws: ~60-75% acceptance, so the
     # rejection rounds are exercised for real
