@@ -1691,7 +1691,9 @@ hipError_t sf_launch_maf_inv16b_hook(const SfDev& m, const float* z, const float
 }
 
 // Per-galaxy context table of the 16-row path: tab[gal][t][row] = b0 + bc + Wc e(x_gal), rows in tile order.
-// One wave = 16 galaxies; same MFMA sequence as the in-kernel evaluation, so the sampler's draws do not change.
+// One wave = 16 galaxies of ONE transform (blockIdx.y): the T transforms of a galaxy are independent chains of a few MFMAs, and
+// the kernel runs in front of every sampling call -- side by side they take one chain's latency instead of T.  Same MFMA
+// sequence per (galaxy, transform) as the in-kernel evaluation, so the sampler's draws do not change.
 __global__ __launch_bounds__(256) void k_maf_ctab16(SfDev m, const float* __restrict__ x, long M, float* __restrict__ tab) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int s = lane & 15, g4 = lane >> 4;
@@ -1700,7 +1702,8 @@ __global__ __launch_bounds__(256) void k_maf_ctab16(SfDev m, const float* __rest
   const bool valid = gal < M;
   const float* xr = x + (valid ? gal : M - 1) * m.C;
   const int NT = m.nT16;
-  for (int t = 0; t < m.T; ++t) {
+  {
+    const int t = blockIdx.y;
     const float* tp = m.packed16 + (size_t)t * m.t16_stride;
     f32x4 c0[4];
 #pragma unroll
@@ -1778,7 +1781,7 @@ hipError_t sf_launch_maf_fuse16(const SfDev& m, hipStream_t st) {
   return hipGetLastError();
 }
 hipError_t sf_launch_maf_ctab16(const SfDev& m, const float* x, long M, float* tab, hipStream_t st) {
-  hipLaunchKernelGGL(k_maf_ctab16, dim3((unsigned)((M + 63) / 64)), dim3(256), 0, st, m, x, M, tab);
+  hipLaunchKernelGGL(k_maf_ctab16, dim3((unsigned)((M + 63) / 64), (unsigned)m.T), dim3(256), 0, st, m, x, M, tab);
   return hipGetLastError();
 }
 
