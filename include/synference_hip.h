@@ -438,6 +438,79 @@ int sf_scatter_depths(const float* flux /*[N,C]*/, int64_t N, int32_t C, const f
                       int32_t n_scatters, float min_flux_pc_error, uint64_t seed,
                       float* out /*[N*n_scatters,C]*/, float* err_out, void* stream);
 
+/* ---- empirical noise models (csrc/sf_noise.hip; fitted and packed by synference_amd/noise_models.py) ---------------------
+ * One band of a packed model: p(sigma | flux) of one filter as three tables over n_bins ascending centres -- centers[n],
+ * median[n], std[n] at table[table_offset ...] -- and everything that is constant per band, computed on the host.
+ * Spaces: PHYSICAL = a flux density in some unit, AB = AB magnitudes, ASINH = asinh magnitudes with softening b_jy.
+ * A physical unit u enters through its AB zero point zp (m = zp - 2.5 log10(f_u); 8.9 for Jy) and through plain factors.
+ * Field order and types are mirrored by the ctypes Structure of the same name (synference_amd/_lib.py). */
+#define SF_NOISE_KIND_GENERAL 0    /* ref: noise_models.py:638-1099 GeneralEmpiricalUncertaintyModel */
+#define SF_NOISE_KIND_ASINH 1      /* ref: noise_models.py:443-635 AsinhEmpiricalUncertaintyModel */
+#define SF_NOISE_SPACE_PHYSICAL 0
+#define SF_NOISE_SPACE_AB 1
+#define SF_NOISE_SPACE_ASINH 2
+#define SF_NOISE_FLUX_SCATTER 0    /* limit_value + std_at_limit * N(0,1) truncated to +-3 (unscattered in the scalings call) */
+#define SF_NOISE_FLUX_LIMIT 1      /* limit_value */
+#define SF_NOISE_FLUX_NUMBER 2     /* flux_number */
+typedef struct sf_noise_band {
+  int32_t kind;            /* SF_NOISE_KIND_* */
+  int32_t interp_space;    /* space of the tables: General PHYSICAL / AB, Asinh ASINH / PHYSICAL */
+  int32_t in_space;        /* space of the input flux: PHYSICAL / AB */
+  int32_t out_space;       /* General PHYSICAL / AB, Asinh always ASINH */
+  int32_t n_bins;          /* 2 .. 256 */
+  int32_t table_offset;    /* floats into the table: centers[n_bins], median[n_bins], std[n_bins] */
+  int32_t extrapolate;     /* continue the end segments instead of holding the end values */
+  int32_t resample;        /* the returned error is a second sigma draw at the scattered flux */
+  int32_t upper_limits;    /* General: SNR cut before the scatter */
+  int32_t has_limit;       /* General: upper_limit_value exists (SNR cut after the scatter, flux and error rules) */
+  int32_t flux_rule;       /* SF_NOISE_FLUX_* */
+  int32_t replace_err;     /* the error rule is a recognised one: limited elements get err_value */
+  float in_to_unit;        /* physical input -> interpolation unit */
+  float zp_in;             /* AB zero point of the physical input unit */
+  float zp_unit;           /* AB zero point of the interpolation unit */
+  float zp_out;            /* AB zero point of the physical output unit */
+  float unit_to_out;       /* interpolation unit -> physical output unit */
+  float in_to_jy;          /* physical input -> Jy (Asinh) */
+  float unit_per_jy;       /* Jy -> interpolation unit (Asinh, physical tables) */
+  float jy_per_unit;       /* interpolation unit -> Jy (Asinh, physical tables) */
+  float b_jy;              /* Asinh: softening in Jy */
+  float sigma_clip;        /* General: scatter noise truncated to +- this many sigma; negative: not truncated */
+  float snr_threshold;     /* treat_as_upper_limits_below */
+  float limit_value;       /* upper_limit_value, interpolation space */
+  float flux_number;       /* numeric upper_limit_flux_behaviour */
+  float std_at_limit;      /* max(0, std table at limit_value) */
+  float err_value;         /* the replacement error, interpolation space */
+  float min_err;           /* clip of the returned error, output space */
+  float max_err;
+} sf_noise_band;
+
+/* Scatter every library row n_scatters times through its band's model: out / err_out [(i*n_scatters + s), c] = the noisy flux
+ * or magnitude and its error in the band's output space, row order as sf_scatter_depths.  flux [N,C] device in each band's
+ * input space; bands [C] and table [n_table] HOST arrays (copied to the device by the call); err_out may be NULL.
+ * One Philox4x32-10 call per output element: key (seed, stream 6), counter (out_row lo, out_row hi, 0, band), u0..u3 = the four
+ * words as uniforms ((r >> 9) + 0.5) 2^-23.  With x the flux in the band's interpolation space:
+ *   sigma(x, u) = mu + ss t,  mu / ss = the median / max(0, std) table at x (linear; NaN in, NaN out),
+ *                 t = quantile u of N(0,1) truncated to [a, inf), a = min(-mu / (ss > 1e-9 ? ss : 1), 12)
+ *   General: s1 = sigma(x, u0); lim0 = upper_limits and SNR(x, s1) below the threshold or not finite; y = x, and unless lim0
+ *     y += s1 z, z the quantile u1 of N(0,1) (truncated to +-sigma_clip); s = resample ? sigma(y, u2) : s1; with has_limit,
+ *     where lim0 or SNR(y, s) is below: y by flux_rule (u3), s = err_value; then units out and clip to [min_err, max_err].
+ *     SNR in AB space is 2.5 / (ln 10 e) (NaN where the flux is 0 or NaN), in physical space f / e.
+ *   Asinh: tables over asinh magnitudes m: s1 = sigma(m, u0), y = m + s1 z, s = resample ? sigma(y, u2) : s1; tables over a
+ *     physical unit: s1 = sigma(x, u0), y_jy = f_jy + s1_jy z, y = asinh magnitude of y_jy, e = resample ? sigma(y_jy, u2) : s1,
+ *     s = 2.5 log10(e) e_jy / sqrt(y_jy^2 + 4 b^2); then clip.
+ * Packed tables above 64 KiB (or structs and tables together above the 64 KiB staged per workgroup), a band with fewer than
+ * 2 or more than 256 bins, C < 1: SF_ERR_INVALID with a message, nothing launched.  N == 0: SF_OK, nothing launched.
+ * Replaces ref: noise_models.py:818-957 and 507-560 as called from sbi_runner.py:813-903. */
+int sf_scatter_empirical(const float* flux /*[N,C] device*/, int64_t N, int32_t C, const sf_noise_band* bands /*[C] host*/,
+                         const float* table /*[n_table] host*/, int64_t n_table, int32_t n_scatters, uint64_t seed,
+                         float* out /*[N*n_scatters,C] device*/, float* err_out /*device, may be NULL*/, void* stream);
+
+/* The deterministic twin for an observed catalogue (flux, err [N,C] device in each band's input space): units in, SNR cut
+ * with the flux rule unscattered, replacement error, units out, clip.  No random numbers.  Same limits as above.
+ * Replaces ref: noise_models.py:1074-1099 and 562-592 as called from sbi_runner.py:2767-2843. */
+int sf_apply_scalings(const float* flux, const float* err, int64_t N, int32_t C, const sf_noise_band* bands /*[C] host*/,
+                      const float* table /*[n_table] host*/, int64_t n_table, float* out, float* err_out, void* stream);
+
 /* PIT ranks of the truths among the posterior draws: out[g,d] = #{draws < truth} / #{finite draws}.
  * Replaces the host pass at ref: sbi_runner.py:7153-7158. */
 int sf_pit_ranks(const float* samples /*[N,S,D]*/, const float* truth /*[N,D]*/, int64_t N, int64_t S, int32_t D,

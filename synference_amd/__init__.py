@@ -7,7 +7,10 @@ from .priors import CustomIndependentUniform, Interval, prior_from_parameters  #
 from .runner import HIPRunner, NumpyLoader, train_flow  # noqa: F401
 from .fitter import SBI_Fitter  # noqa: F401
 from .missing import MissingPhotometryHandler  # noqa: F401
+from .noise_models import (AsinhEmpiricalUncertaintyModel, EmpiricalUncertaintyModel,  # noqa: F401
+                           GeneralEmpiricalUncertaintyModel, UncertaintyModel)
 
 __all__ = ["FlowSpec", "FCN", "FlowEstimator", "build_flow", "load_nde_hip", "EnsemblePosterior", "FlowPosterior",
            "CustomIndependentUniform", "Interval", "prior_from_parameters", "HIPRunner", "NumpyLoader",
-           "train_flow", "SBI_Fitter", "MissingPhotometryHandler"]
+           "train_flow", "SBI_Fitter", "MissingPhotometryHandler", "UncertaintyModel",
+           "EmpiricalUncertaintyModel", "GeneralEmpiricalUncertaintyModel", "AsinhEmpiricalUncertaintyModel"]

@@ -40,6 +40,15 @@ class sf_adam_desc(C.Structure):
                 ("weight_decay", C.c_float), ("decoupled", C.c_int32)]
 
 
+class sf_noise_band(C.Structure):
+    """One band of a packed empirical noise model (field order of include/synference_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("kind", "interp_space", "in_space", "out_space", "n_bins", "table_offset",
+                                         "extrapolate", "resample", "upper_limits", "has_limit", "flux_rule", "replace_err")] + \
+               [(n, C.c_float) for n in ("in_to_unit", "zp_in", "zp_unit", "zp_out", "unit_to_out", "in_to_jy", "unit_per_jy",
+                                         "jy_per_unit", "b_jy", "sigma_clip", "snr_threshold", "limit_value", "flux_number",
+                                         "std_at_limit", "err_value", "min_err", "max_err")]
+
+
 # name -> (restype, argtypes); mirrors include/synference_hip.h one for one
 PROTOTYPES = {
     "sf_flow_create": (C.c_int, [C.POINTER(sf_flow_desc), C.POINTER(C.c_void_p)]),
@@ -62,6 +71,10 @@ PROTOTYPES = {
     "sf_flux_to_asinh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p]),
     "sf_scatter_depths": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_uint64,
+                                    C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sf_scatter_empirical": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(sf_noise_band), c_f32p, C.c_int64, C.c_int32,
+                                       C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sf_apply_scalings": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(sf_noise_band), c_f32p, C.c_int64,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     "sf_pit_ranks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
     "sf_tarp_coverage": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,

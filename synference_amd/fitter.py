@@ -187,20 +187,34 @@ class SBI_Fitter:
           * ``normed_flux_units="asinh"`` (1591-1627, 1718-1732; utils.py:647-704; ``sf_flux_to_asinh``): softening
             ``asinh_softening_parameters`` per filter in the grid's unit -- an array, a dict by filter name, or
             ``"SNR_<k>"`` = k x depth / 5 when scattering with depths; no magnitude-limit clip there, as in the reference.
-        Outside the accelerated path (``ValueError``): other flux units, extra feature expressions, empirical noise
-        models, simulated missing fluxes, normalisation by a supplementary parameter or of asinh magnitudes.  ``seed``
-        replaces numpy's global generator for the scatter noise and the ``max_rows`` draw."""
+          * ``scatter_fluxes`` + ``empirical_noise_models`` = {filter: model of ``synference_amd.noise_models``}
+            (1679-1693, ``_apply_empirical_noise_models`` 813-903; ``sf_scatter_empirical``): every filter is scattered through
+            its own model from the grid's unit straight to ``normed_flux_units``, errors included; for AB, NaN and inf become
+            ``norm_mag_limit`` (1707-1714); all-Asinh models make ``asinh_softening_parameters`` optional (1592-1600).  Depths
+            win when both are given and ``min_flux_pc_error`` is ignored on this path, as in the reference.  General models with
+            ``normed_flux_units="asinh"``, Asinh models with "AB" and mixed dicts are a ``ValueError``.
+        Outside the accelerated path (``ValueError``): other flux units, extra feature expressions, simulated missing
+        fluxes, normalisation by a supplementary parameter or of asinh magnitudes.  ``seed`` replaces numpy's global
+        generator for the scatter noise and the ``max_rows`` draw."""
         _warn_unknown("create_feature_array_from_raw_photometry", unknown)
         if self.raw_observation_grid is None:
             raise ValueError("no raw observation grid: build the fitter with init_from_hdf5 or pass feature_array")
-        if extra_features or normed_flux_units not in ("AB", "asinh") or empirical_noise_models is not None or simulate_missing_fluxes:
-            raise ValueError("only normed_flux_units='AB' / 'asinh' without extra features, empirical noise models or "
-                             "simulated missing fluxes is on the HIP path")
+        if extra_features or normed_flux_units not in ("AB", "asinh") or simulate_missing_fluxes:
+            raise ValueError("only normed_flux_units='AB' / 'asinh' without extra features or simulated missing fluxes is on "
+                             "the HIP path")
         asinh = normed_flux_units == "asinh"
         if asinh and normalize_method is not None:
             raise ValueError("normalisation of asinh magnitudes is outside the HIP path")
+        # the models scatter only when there are no depths: depths win when both are given (ref: 1636 / 1679)
+        use_models = bool(scatter_fluxes) and depths is None and empirical_noise_models is not None
+        if use_models and not isinstance(empirical_noise_models, dict):
+            raise ValueError("empirical_noise_models must be a dictionary")
         if asinh:
-            assert asinh_softening_parameters is not None, "asinh_softening_parameters must be provided for asinh normalization."
+            from .noise_models import AsinhEmpiricalUncertaintyModel
+            err_is_asinh = isinstance(empirical_noise_models, dict) and all(
+                isinstance(m, AsinhEmpiricalUncertaintyModel) for m in empirical_noise_models.values())   # ref: 1592-1600
+            assert asinh_softening_parameters is not None or (err_is_asinh and use_models), \
+                "asinh_softening_parameters must be provided for asinh normalization."
         if not torch.cuda.is_available():
             raise RuntimeError("create_feature_array_from_raw_photometry runs on the GPU (no CPU fallback)")
         from .features import flux_to_abmag, flux_to_asinh, scatter_depths
@@ -218,14 +232,23 @@ class SBI_Fitter:
         n_sc = int(scatter_fluxes) if scatter_fluxes else 0
         flux = torch.as_tensor(np.ascontiguousarray(grid.T), dtype=torch.float32).cuda()  # (N, C) on the device
         err = None
-        if n_sc:
+        converted = False
+        if n_sc and use_models:
+            flux, err = self._apply_empirical_noise_models(flux, names, empirical_noise_models, n_sc, normed_flux_units, seed)
+            self.empirical_noise_models = empirical_noise_models
+            converted = True                                  # magnitudes and their errors already (ref: 1693-1715)
+        elif n_sc:
             if depths is None:
                 raise ValueError("If scattering fluxes, depths or empirical noise models must be provided.")
             if isinstance(depths, dict):
                 depths = np.asarray([depths[n_] for n_ in names], dtype=np.float32)
             self.phot_depths, self.min_flux_pc_error = depths, min_flux_pc_error
             flux, err = scatter_depths(flux, depths, n_sc, 5.0, min_flux_pc_error, seed=seed, return_errors=True)
-        if asinh:
+        if converted:
+            mag, mag_err = flux, err
+            if not asinh:                                      # NaN and inf (zero and negative fluxes) to the limit (1707-1714)
+                mag = torch.where(torch.isfinite(mag), mag, torch.full_like(mag, norm_mag_limit))
+        elif asinh:
             if isinstance(asinh_softening_parameters, str):
                 assert asinh_softening_parameters.startswith("SNR_"), "If a string, asinh_softening_parameters must start with 'SNR_'."
                 assert n_sc and depths is not None, ("If setting asinh_softening_parameters from noise models, "
@@ -313,11 +336,36 @@ class SBI_Fitter:
                                         remove_nan_inf=remove_nan_inf, parameters_to_remove=parameters_to_remove,
                                         photometry_to_remove=photometry_to_remove, parameters_to_add=parameters_to_add,
                                         drop_dropouts=drop_dropouts, drop_dropout_fraction=drop_dropout_fraction,
-                                        raw_observation_names=names, error_names=error_names, norm_name=norm_name)
+                                        raw_observation_names=names, error_names=error_names, norm_name=norm_name,
+                                        empirical_noise_models=empirical_noise_models if converted else None)
         self.update_parameter_array(parameters_to_remove=list(parameters_to_remove or []), delete_rows=np.sort(delete_rows),
                                     n_scatters=max(n_sc, 1), parameters_to_add=list(parameters_to_add or []),
                                     parameter_transformations=parameter_transformations)
         return self.feature_array, self.feature_names
+
+    def _grid_flux_unit(self) -> str:
+        """The unit of the raw observation grid as one of the noise models' unit strings (the library convention is nJy)."""
+        from .noise_models import PHYSICAL_UNITS
+        u = self.raw_observation_units
+        u = u if isinstance(u, str) or u is None else (str(u[0]) if len(u) else None)
+        return u if u in PHYSICAL_UNITS or u == "AB" else "nJy"
+
+    def _apply_empirical_noise_models(self, flux, phot_names, empirical_noise_models, n_scatters, normed_flux_units, seed):
+        """ref: sbi_runner.py:813-903 -- every filter scattered ``n_scatters`` times through its own model on the device
+        (``sf_scatter_empirical``): (N, C) grid fluxes -> (N * n_scatters, C) values and errors in ``normed_flux_units``."""
+        from .features import scatter_empirical
+        if not isinstance(empirical_noise_models, dict):
+            raise ValueError("empirical_noise_models must be a dictionary")
+        for name in phot_names:
+            if name not in empirical_noise_models:
+                raise ValueError(f"""No empirical noise model found for filter {name}.
+                    Please provide a valid model.""")
+        for name in empirical_noise_models.keys():
+            if name not in phot_names:
+                raise ValueError(f"Filter {name} in empirical_noise_models is not in phot_names:\
+                    {phot_names}. Please provide a valid filter name.")
+        return scatter_empirical(flux, [empirical_noise_models[n_] for n_ in phot_names], self._grid_flux_unit(),
+                                 normed_flux_units, n_scatters=n_scatters, seed=seed)
 
     def update_parameter_array(self, parameters_to_remove: list = [], delete_rows=[], n_scatters: int = 1,
                                parameters_to_add: list = [], parameter_transformations: dict = None) -> None:
@@ -900,12 +948,14 @@ class SBI_Fitter:
         trained on, plus the mask of removed rows, from the transformations recorded by
         ``create_feature_array_from_raw_photometry`` (``self.feature_array_flags``).
 
-        As in the reference the photometry columns must ALREADY be in the training units (``flux_units`` has to equal
-        ``normed_flux_units``, an assertion there too); what happens here is column mapping and validation (every
+        When the flags hold empirical noise models and the error columns are features, each band's flux and error columns
+        first go through its model's ``apply_scalings`` from ``flux_units`` to the training unit (2767-2843, on the device).
+        Otherwise, as in the reference, the photometry columns must ALREADY be in the training units (``flux_units`` has to equal
+        ``normed_flux_units``, an assertion there too); what happens then is column mapping and validation (every
         filter, every ``unc_`` column when errors were features, the ``norm_<filter>_<unit>`` column), the error-NaN
         check, the normalisation step exactly as the reference writes it (2844-2865), removal of rows that carry the
-        missing-data flag, the ``norm_mag_limit`` clip and inf -> NaN.  Empirical noise models, flags and simulated
-        missing fluxes are outside the HIP path."""
+        missing-data flag, the ``norm_mag_limit`` clip and inf -> NaN.  Flags and simulated missing fluxes are outside the
+        HIP path."""
         import pandas as pd
         flags = dict(getattr(self, "feature_array_flags", None) or {})
         if len(flags) == 0:
@@ -927,8 +977,6 @@ class SBI_Fitter:
             raise ValueError(f"Column '{flags['norm_name']}' not found in\n                observations. "
                              "Please provide a mapping for the normalization factor.")
         training_flux_units = flags["normed_flux_units"]
-        assert flux_units == training_flux_units, (f"Flux units '{flux_units}' do not match\n                    "
-                                                   f"training data units '{training_flux_units}'.")
         fnames = list(self.feature_names)
         nrows, ncols = observations.shape[0], np.shape(self.feature_array)[1]
         fa = np.zeros((ncols, nrows), dtype=np.float32)
@@ -951,6 +999,11 @@ class SBI_Fitter:
             if np.sum(bad) > 0:
                 raise ValueError(f"Error column '{col}' contains NaN values where the\n                    corresponding flux "
                                  f"column '{col.replace('unc_', '')}' does not.{np.sum(bad)} NaN values found.")
+        if flags.get("empirical_noise_models") is not None and err_names:
+            flux_units = self._apply_model_scalings(fa, fnames, flags, columns_to_feature_names, feature_names_to_columns,
+                                                    flux_units, missing_data_flag)
+        assert flux_units == training_flux_units, (f"Flux units '{flux_units}' do not match\n                    "
+                                                   f"training data units '{training_flux_units}'.")
         if flags.get("norm_name") is not None:
             ncol = feature_names_to_columns[flags["norm_name"]]
             if ncol not in observations.columns:
@@ -975,6 +1028,48 @@ class SBI_Fitter:
         fa[clip] = flags["norm_mag_limit"]
         fa[~np.isfinite(fa)] = np.nan
         return fa.T, removed
+
+    def _apply_model_scalings(self, fa, fnames, flags, columns_to_feature_names, feature_names_to_columns, flux_units,
+                              missing_data_flag):
+        """ref: sbi_runner.py:2767-2843 -- each band's flux and error rows of ``fa`` through its noise model's
+        ``apply_scalings`` (``sf_apply_scalings``), from ``flux_units`` to the training unit; a band without a matching
+        ``unc_`` column is skipped with a warning.  Entries that carry the missing-data flag keep it.  Returns the unit the
+        photometry is in afterwards."""
+        from .features import apply_scalings
+        from .noise_models import UncertaintyModel
+        if not torch.cuda.is_available():
+            raise RuntimeError("create_features_from_observations with empirical noise models runs on the GPU (no CPU fallback)")
+        rows, models = [], []
+        for model_name, model in flags["empirical_noise_models"].items():
+            if not isinstance(model, UncertaintyModel):
+                raise TypeError(f"Invalid empirical noise model type: {type(model)}. Expected an EmpiricalUncertaintyModel instance.")
+            if model_name in columns_to_feature_names:
+                model_name = columns_to_feature_names[model_name]
+            if model_name not in feature_names_to_columns or model_name not in fnames:
+                logger.warning(f"Empirical noise model '{model_name}' not found in feature names.")
+                continue
+            eindex, tail = None, model_name.split(".")[-1]
+            for ecol in flags["error_names"]:
+                if ecol == f"unc_{model_name}" or (ecol.startswith("unc_") and ecol.endswith(tail)):
+                    eindex = fnames.index(ecol)
+                    break
+            if eindex is None:
+                logger.warning(f"No matching error column for '{model_name}'. Skipping empirical scaling.")
+                continue
+            rows.append((fnames.index(model_name), eindex))
+            models.append(model)
+        if models:
+            fi, ei = [r[0] for r in rows], [r[1] for r in rows]
+            f_in, e_in = fa[fi, :].T, fa[ei, :].T
+            new_f, new_e = apply_scalings(torch.as_tensor(np.ascontiguousarray(f_in)).cuda(),
+                                          torch.as_tensor(np.ascontiguousarray(e_in)).cuda(), models, flux_units,
+                                          flags["normed_flux_units"])
+            new_f, new_e = new_f.cpu().numpy(), new_e.cpu().numpy()
+            if not (isinstance(missing_data_flag, float) and np.isnan(missing_data_flag)):
+                new_f = np.where(f_in == missing_data_flag, f_in, new_f)
+                new_e = np.where(e_in == missing_data_flag, e_in, new_e)
+            fa[fi, :], fa[ei, :] = new_f.T, new_e.T
+        return flags["normed_flux_units"]
 
     def fit_catalogue(self, observations, columns_to_feature_names: dict = None, num_samples: int = 1000,
                       quantiles=(0.16, 0.5, 0.84), sample_method: str = "direct", append_to_input: bool = True,
