@@ -1,5 +1,7 @@
 #!/bin/bash
-# usage: ab_multi.sh n "ENV_A" "ENV_B" ...  -> n rounds of alternating bench runs, prints the sampler launch time of each
+# usage: ab_multi.sh n "ENV_A" "ENV_B" ...  -> n rounds of alternating bench runs, prints the sampler launch time of each.
+# Stops at the first run that exits non-zero (a fault, a time limit, no result line): nothing more is started after it.
+set -o pipefail
 n=$1; shift
 for i in $(seq 1 $n); do
   for v in "$@"; do
@@ -7,5 +9,10 @@ for i in $(seq 1 $n); do
 import sys, json
 d = json.loads(sys.stdin.readline())
 print('$v', 'ms_per_step', round(d['ms_per_step'], 3), 'kernel_ms', round(d['roofline'].get('launch_ms'), 3), 'frac', round(d['roofline']['frac'], 4), 'evals', d['config'].get('evals_per_step', d['roofline'].get('note', '')[:0]))"
+    rc=$?
+    if [ $rc -ne 0 ]; then
+      echo "ab_multi: round $i, '$v': exit status $rc -- stopping" >&2
+      exit $rc
+    fi
   done
 done

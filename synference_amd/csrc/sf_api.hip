@@ -370,19 +370,20 @@ int sf_flow_inverse_from_noise_sampler(sf_flow* f, const float* z, const float* 
     return ms.hidden_bf16 == 2 ? SF_OK : 1;
   }
   const SfDev m = f->dev();
-  if (!sf_maf16b_available(m)) {  // the sampler of this flow is the 32-row fp32 path
+  const SfMaf16Plan pl = sf_maf16_plan(m);
+  if (!pl.sampler16) {  // the sampler of this flow is the 32-row fp32 path
     SfSampleArgsHost a;
     a.x = x; a.z_in = z; a.n_items = (long)B; a.out = theta;
     SF_TRY_SET(sf_launch_inverse(m, a, (hipStream_t)stream));
     return 1;  // (positive: "fp32 path", not an error)
   }
-  if (sf_sampler_fp32_for(SF_MAF)) {
+  if (pl.fp32) {
     // the default sampler of a flow with the unrolled kernels runs the FUSED first layer off the context table: the hook builds
     // the table for these rows and runs the find kernel's pass functions on the given noise
     int rc = sf_flow_prepare_context(f, x, B, stream);
     if (rc) return rc;
     const SfDev mt = sampler_dev(f, x);
-    if (sf_maf16_fused_d(mt) > 0) {
+    if (sf_maf16_plan(mt).fused) {
       SfSampleArgsHost a;
       a.x = x; a.z_in = z; a.n_items = (long)B; a.out = theta; a.S = 1;
       hipError_t e = sf_launch_maf_find16_zin(mt, a, (hipStream_t)stream);
@@ -393,9 +394,27 @@ int sf_flow_inverse_from_noise_sampler(sf_flow* f, const float* z, const float* 
     (void)sf_flow_release_context(f);
   }
   SF_TRY_SET(sf_launch_maf_inv16b_hook(m, z, x, (long)B, theta, (hipStream_t)stream));
-  return sf_sampler_fp32_for(SF_MAF) ? 2 : SF_OK;   // 2: the 16-row sampler's fp32 pass functions
+  return pl.fp32 ? 2 : SF_OK;   // 2: the 16-row sampler's fp32 pass functions
 }
 
+// Arithmetic of the samplers' hidden blocks (process-wide; sf_set_sampler_fp32 / environment SF_SAMPLER_FP32):
+//   1  fp32 everywhere: MAF k_maf_samp16<.., PREC = 1> (v_mfma_f32_16x16x4_f32), NSF the fp32 image
+//   0  split bf16 x3 where the flow has such an image (the opt-in fast mode of round 2-4)
+//  -1  (unset) per flow kind: MAF fp32 -- BASELINE configs[1] says fp32, and the split products move log p(draw) by up to
+//      1.3e-3 against the north-star tolerance of 1e-4 -- NSF split (its draws meet the fp64 oracle as closely as the
+//      all-fp32 kernels do: tests/test_gpu_parity.py::test_sampler_arithmetic_from_given_noise)
+extern "C++" {   // (internal linkage names of sf_internal.h, kept beside the C entry point that sets the switch)
+static int g_sampler_fp32 = -2;
+void sf_sampler_fp32_set(int on) { g_sampler_fp32 = on < 0 ? -1 : (on ? 1 : 0); }
+int sf_sampler_fp32_get() {
+  if (g_sampler_fp32 == -2) { const char* e = std::getenv("SF_SAMPLER_FP32"); g_sampler_fp32 = (e && *e) ? (std::atoi(e) != 0 ? 1 : 0) : -1; }
+  return g_sampler_fp32;
+}
+int sf_sampler_fp32_for(int kind) {
+  const int g = sf_sampler_fp32_get();
+  return g < 0 ? (kind == SF_MAF ? 1 : 0) : g;
+}
+}  // extern "C++"
 int sf_set_sampler_fp32(int on) {
   sf_sampler_fp32_set(on);
   return SF_OK;

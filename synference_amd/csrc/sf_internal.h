@@ -79,7 +79,6 @@ hipError_t sf_launch_logprob(const SfDev& m, const float* theta, const float* x,
 hipError_t sf_launch_inverse(const SfDev& m, const SfSampleArgsHost& a, hipStream_t st);
 bool sf_maf16_enabled(const SfDev& m, const SfSampleArgsHost& a);
 hipError_t sf_launch_maf_inv16(const SfDev& m, const SfSampleArgsHost& a, hipStream_t st);
-bool sf_maf16b_available(const SfDev& m);
 hipError_t sf_launch_maf_inv16b_hook(const SfDev& m, const float* z, const float* x, long n, float* out, hipStream_t st);
 void sf_sampler_fp32_set(int on);
 int sf_sampler_fp32_get();        // 1 fp32, 0 split bf16 x3, -1 unset: per flow kind
@@ -89,7 +88,18 @@ void sf_ctab_shape(const SfDev& m, int& R, int& NV);
 hipError_t sf_launch_ctab(const SfDev& m, const float* x, long M, float* tab, hipStream_t st);
 hipError_t sf_launch_maf_ctab16(const SfDev& m, const float* x, long M, float* tab, hipStream_t st);
 hipError_t sf_launch_maf_fuse16(const SfDev& m, hipStream_t st);
-int sf_maf16_fused_d(const SfDev& m);   // D (3..5) when the fused-first-layer fp32 kernels apply to this view (table with c0' rows), else 0
+// Which 16-row MAF kernels (sf_maf16.hip) a view of a flow runs on, in the process's sampler arithmetic: the one place that decides.
+struct SfMaf16Plan {
+  bool ok16 = false;       // the flow has the 16-row path at all (fp32 image; sf_maf16_enabled adds the launch's own condition)
+  bool sampler16 = false;  // ... and its persistent sampler in this arithmetic; false: the sampler IS the 32-row fp32 path
+  bool fp32 = false;       // hidden blocks in fp32 (sf_sampler_fp32_for(SF_MAF)), else split bf16 x3
+  bool span = false;       // contiguous placement: degree groups straddle tiles
+  bool head_mfma = false;  // head rows on the matrix pipe (aligned placement with the head tile in the image: D <= 8)
+  int dd = 0;              // D (3..5) when the unrolled kernels apply (this view has the context table, degree p alone in tile p - 2,
+                           // the packer's offsets are the hard-wired ones), else 0: the kernels that dispatch per pass
+  bool fused = false;      // ... with the fused first layer (fp32, the table carries the c0' rows)
+};
+SfMaf16Plan sf_maf16_plan(const SfDev& m);
 hipError_t sf_launch_maf_find16_zin(const SfDev& m, const SfSampleArgsHost& a, hipStream_t st);   // W' = (W1 o M)(W0 o M0) into o16_wp of every transform
 hipError_t sf_launch_pack(const float* flat, const int32_t* s1, const int32_t* s2, float* packed, long n,
                           hipStream_t st);
