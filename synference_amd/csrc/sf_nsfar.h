@@ -56,19 +56,24 @@ int sf_nsfar_inverse(SfNsfAr* n, const float* z, const float* x, long B, float* 
 int sf_nsfar_sample(SfNsfAr* n, const float* x, long M, long S, const uint32_t* slots, long n_slots, const float* lo, const float* hi,
                     uint32_t k0, uint32_t k1, unsigned long long slot_offset, int max_attempts, float* out, int32_t* n_drawn,
                     int32_t* count, int64_t* n_unfilled, hipStream_t st, std::string& err, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
-// sf_nsfar16.hip: the persistent first launch of sf_nsfar_sample on 16-sample register tiles (same arguments and hand-over as k_ar_sample)
-struct SfAr16Launch {
+// One sampling call as all six sampler kernels take it (sf_ar_sampler.h: the control flow; sf_nsfar.hip / sf_nsfar16.hip: the candidate routines and kernels).
+// cursor = d_ctr: [0] work cursor, [2] evaluations, [3] first attempts rejected.
+struct SfArLaunch {
   const float* x; long S; const uint32_t* slots; long n_slots; const float* lo; const float* hi; uint32_t k0, k1; unsigned long long slot_offset;
   uint32_t max_attempts; float* out; int32_t* n_drawn; int32_t* count; unsigned long long* cursor; unsigned int* n_unfilled; int32_t* g_try;
   int32_t* g_acc; unsigned long long walk_R, walk_C; uint32_t window_end; uint32_t* surv; unsigned int* n_surv;
 };
+// One chip-wide round: FIND tries attempts [base, att_end) of the n_surv survivors (64 per workgroup, `chunks` workgroups per
+// survivor) and lowers best[]; RESOLVE writes the found draws and appends what stays open to next[] (base == att_end: nothing was
+// tried, the last RESOLVE that writes off what the ceiling left open).
+struct SfArRound {
+  const uint32_t* surv; unsigned int n_surv; uint32_t* best; uint32_t base, chunks, att_end; uint32_t* next; unsigned int* n_next;
+};
+// sf_nsfar16.hip: the three launches on 16-candidate register tiles, for the shapes that take them
 bool sf_nsfar16_eligible(const SfNsfAr& n);
-hipError_t sf_nsfar16_launch(const SfNsfAr& n, const SfAr16Launch& L, int cus, hipStream_t st);
-// the chip-wide rounds on the same candidate routine (arguments of k_ar_find / k_ar_resolve; L carries x, S, the box, the keys and the outputs)
-hipError_t sf_nsfar16_find(const SfNsfAr& n, const SfAr16Launch& L, const uint32_t* surv, unsigned int n_surv, uint32_t base, uint32_t chunks,
-                           uint32_t att_end, uint32_t* best, unsigned long long* ctr, hipStream_t st);
-hipError_t sf_nsfar16_resolve(const SfNsfAr& n, const SfAr16Launch& L, const uint32_t* surv, unsigned int n_surv, const uint32_t* best,
-                              uint32_t tried_end, uint32_t tried_now, uint32_t* next, unsigned int* n_next, hipStream_t st);
+hipError_t sf_nsfar16_launch(const SfNsfAr& n, const SfArLaunch& L, int cus, hipStream_t st);
+hipError_t sf_nsfar16_find(const SfNsfAr& n, const SfArLaunch& L, const SfArRound& R, hipStream_t st);
+hipError_t sf_nsfar16_resolve(const SfNsfAr& n, const SfArLaunch& L, const SfArRound& R, hipStream_t st);
 int sf_nsfar_loss_grad(SfNsfAr* n, const float* flat, const float* theta, const float* x, const long long* idx, long B, float grad_scale,
                        const float* weights, float* loss, double* loss_sum, float* grad, hipStream_t st, std::string& err, hipEvent_t ev0 = nullptr,
                        hipEvent_t ev1 = nullptr);

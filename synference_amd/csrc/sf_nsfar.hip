@@ -19,7 +19,8 @@
 //     soon as the dimensions ordered before r are inverted, so the sweep r = 0 .. D-1 computes the hidden units of type r,
 //     the head of the dimension with order r, inverts that dimension, and goes on (zuko sweeps the whole network D times);
 //   * rejected draws are retried by compaction: a wave keeps taking (slot, attempt) items -- its own rejects first -- until
-//     the catalogue's slot list is exhausted.
+//     the catalogue's slot list is exhausted (the sampler's control flow lives once in sf_ar_sampler.h; here: ar_candidate, its
+//     engine ArLdsEngine and the host driver sf_nsfar_sample).
 // Training: forward with every transform's inputs stashed, then per transform (top down) the hyper-network is recomputed from
 // the stash and back-propagated by hand.
 #include <hip/hip_runtime.h>
@@ -30,6 +31,7 @@
 #include <string>
 #include <vector>
 
+#include "sf_ar_sampler.h"
 #include "sf_device.h"
 #include "sf_internal.h"
 #include "sf_nsfar.h"
@@ -162,13 +164,6 @@ __device__ __forceinline__ int ar_slot_row(const ArArgs& a, int sl) {
 // workgroup barrier of the multi-wave kernels of this file
 __device__ __forceinline__ void ar_barrier() {
   __syncthreads();   // (-DSF_FUZZ_SCHED: the macro of sf_device.h, barrier + delay)
-}
-
-// order the LDS traffic of ONE wave (its LDS operations execute in program order: a read issued after a write of another lane
-// of the same wave sees it; this only keeps the compiler from reordering them)
-__device__ __forceinline__ void ar_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
 }
 
 // NTL x sixteen output rows [p0, p0 + 16 NTL) of a product for the wave's 64 samples:
@@ -462,14 +457,12 @@ __global__ __launch_bounds__(64) void k_ar_inverse(ArArgs a, const float* __rest
 }
 
 // one candidate per lane: noise of (slot, attempt) through the inverse flow, box test; the candidate is left in V rows [0, D)
-__device__ __forceinline__ bool ar_candidate(const ArArgs& a, const ZSplC& sc, const float* __restrict__ x, long g, unsigned long long slot,
-                                             uint32_t att, uint32_t k0, uint32_t k1, unsigned long long slot_offset,
-                                             const float* __restrict__ lo, const float* __restrict__ hi, float* E0, float* V, float* H1, float* H2,
-                                             float* QB, int lane, bool active) {
-  for (int c = 0; c < a.C; ++c) E0[(a.D + c) * RS + lane] = (x[g * a.C + c] - a.xmean[c]) / a.xstd[c];
+__device__ __forceinline__ bool ar_candidate(const ArArgs& a, const ZSplC& sc, const SfArLaunch& L, long g, unsigned long long slot, uint32_t att,
+                                             float* E0, float* V, float* H1, float* H2, float* QB, int lane, bool active) {
+  for (int c = 0; c < a.C; ++c) E0[(a.D + c) * RS + lane] = (L.x[g * a.C + c] - a.xmean[c]) / a.xstd[c];
   for (int d0 = 0; d0 < a.D; d0 += 4) {
     float z4[4];
-    sf_normal4(k0, k1, slot + slot_offset, att, (uint32_t)(d0 >> 2), z4);
+    sf_normal4(L.k0, L.k1, slot + L.slot_offset, att, (uint32_t)(d0 >> 2), z4);
 #pragma unroll
     for (int j = 0; j < 4; ++j)
       if (d0 + j < a.D) V[(d0 + j) * RS + lane] = z4[j];
@@ -482,203 +475,58 @@ __device__ __forceinline__ bool ar_candidate(const ArArgs& a, const ZSplC& sc, c
   for (int d = 0; d < a.D; ++d) {
     const float th = (V[d * RS + lane] - a.th_shift[d]) / a.th_scale[d];
     V[d * RS + lane] = th;
-    ok = ok && (th == th) && fabsf(th) < 3.0e38f && (!lo || (th >= lo[d] && th <= hi[d]));
+    ok = ok && (th == th) && fabsf(th) < 3.0e38f && (!L.lo || (th >= L.lo[d] && th <= L.hi[d]));
   }
   return ok;
 }
 
-// rejection sampler: a wave works (slot, attempt) items until the slot list is exhausted; rejected items come back first
-__global__ __launch_bounds__(64) void k_ar_sample(ArArgs a, const float* __restrict__ x, long S, const uint32_t* __restrict__ slots,
-                                                   long n_slots, const float* __restrict__ lo, const float* __restrict__ hi, uint32_t k0,
-                                                   uint32_t k1, unsigned long long slot_offset, uint32_t max_attempts,
-                                                   float* __restrict__ out, int32_t* __restrict__ n_drawn, int32_t* __restrict__ count,
-                                                   unsigned long long* __restrict__ cursor, unsigned int* __restrict__ n_unfilled,
-                                                   int32_t* __restrict__ g_try, int32_t* __restrict__ g_acc, unsigned long long walk_R,
-                                                   unsigned long long walk_C, uint32_t window_end, uint32_t* __restrict__ surv,
-                                                   unsigned int* __restrict__ n_surv) {
-  // window_end < max_attempts: an entry that has used up attempts [0, window_end) is appended to surv[] -- the find / resolve
-  // launches of sf_nsfar_sample spread its further attempts over the whole chip -- instead of being carried on by this wave
-  // cursor[2]: evaluations (items worked), cursor[3]: first attempts rejected -- statistics for sf_flow_sample_stats
-  extern __shared__ float lds[];
-  float* E0 = lds;
-  float* H1 = E0 + a.NIN16 * RS;
-  float* H2 = H1 + a.Hp * RS;
-  float* QB = H2 + a.Hp * RS;
-  float* V = QB + 32 * RS;
-  __shared__ unsigned long long r_slot[64];
-  __shared__ uint32_t r_att[64];
-  const int lane = threadIdx.x;
-  const ZSplC sc = {a.K, a.B, a.cw, a.cd};
-  for (int r = a.D + a.C; r < a.NIN16; ++r) E0[r * RS + lane] = 0.f;
-  // The slot list is walked ACROSS its rows: item i is entry (i % R) * C + i / R of the list seen as R x C (whole catalogue:
-  // R = rows, C = draws per row, i.e. draw i / M of row i % M; an explicit list, sorted by slot: R = 4096 pieces) -- the 64 items
-  // of a wave then belong to 64 different rows, so a row that accepts one draw in hundreds leaves ONE stubborn entry in many
-  // waves instead of 64 in a few.  Once the list has run dry a wave spends its idle lanes on its open entries: W = 2^k <= 64 /
-  // entries attempts of each side by side, the LOWEST accepted attempt wins (what the one-at-a-time order would have kept).
-  const bool interleave = walk_R > 1;
-  const unsigned long long n_index = interleave ? walk_R * walk_C : (unsigned long long)n_slots;   // (>= n_slots: holes are skipped)
-  int n_retry = 0;
-  bool list_done = false;
-  unsigned int n_ev = 0, n_rej0 = 0;
-  for (;;) {
-    const int take = list_done ? 0 : 64 - n_retry;
-    unsigned long long base = n_index;
-    if (take > 0) {
-      if (lane == 0) base = atomicAdd(cursor, (unsigned long long)take);
-      base = ((unsigned long long)__builtin_amdgcn_readfirstlane((int)(base >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)base);
-    }
-    int n_fresh = 0;
-    if (take > 0) {
-      if (base >= n_index) list_done = true;
-      else {
-        const unsigned long long left = n_index - base;
-        n_fresh = left < (unsigned long long)take ? (int)left : take;
-        if (n_fresh < take) list_done = true;
-      }
-    }
-    const int n_ent = n_retry + n_fresh;
-    if (n_ent == 0) {
-      if (lane == 0) {
-        if (n_ev) atomicAdd(cursor + 2, (unsigned long long)n_ev);
-        if (n_rej0) atomicAdd(cursor + 3, (unsigned long long)n_rej0);
-      }
-      break;
-    }
-    int lw = 0;   // log2 of the speculation width
-    if (list_done && !count)
-      while ((n_ent << (lw + 1)) <= 64) ++lw;
-    const int W = 1 << lw;
-    const int e = lane >> lw, sub = lane & (W - 1);
-    unsigned long long slot = 0;
-    uint32_t att0 = 0;
-    bool exists = e < n_ent;   // (an entry of this round: a carried one, or a fresh item that is not a hole of the cover)
-    if (exists) {
-      if (e < n_retry) { slot = r_slot[e]; att0 = r_att[e]; }
-      else {
-        const unsigned long long idx = base + (unsigned)(e - n_retry);
-        const unsigned long long pos = interleave ? (idx % walk_R) * walk_C + idx / walk_R : idx;
-        if (pos >= (unsigned long long)n_slots) exists = false;   // (a hole of the R x C cover)
-        else slot = slots ? (unsigned long long)slots[pos] : pos;
-      }
-    }
-    const uint32_t att = att0 + (uint32_t)sub;
-    const bool active = exists && att < window_end;
-    ar_barrier();   // (the retry list has been read)
-    const long g = exists ? (long)(slot / (unsigned long long)S) : 0;
-    const bool ok = ar_candidate(a, sc, x, g, slot, att, k0, k1, slot_offset, lo, hi, E0, V, H1, H2, QB, lane, active);
-    const unsigned long long m_ok = __ballot(ok);
-    // (statistics stay in the wave until it leaves: per round they were two more atomics on the cache line of the queue head)
-    n_ev += (unsigned)__popcll(__ballot(active));
-    n_rej0 += (unsigned)__popcll(__ballot(active && !ok && att == 0u));
-    if (count) {   // acceptance counting (leakage correction): one attempt per item, nothing written
-      if (ok) atomicAdd(count + g, 1);
-      n_retry = 0;
-      continue;
-    }
-    // the entry's lanes: [e W, e W + W); its lowest accepted attempt
-    const unsigned long long grp = W == 64 ? m_ok : ((m_ok >> (e * W)) & ((1ull << W) - 1ull));
-    const bool resolved = grp != 0ull;
-    const int win = resolved ? __builtin_ctzll(grp) : 0;
-    const bool leader = exists && sub == 0;
-    const uint32_t tried_now = att0 + (uint32_t)W < window_end ? (uint32_t)W : window_end - att0;   // attempts of this round that count
-    const bool window_out = leader && !resolved && att0 + (uint32_t)W >= window_end;
-    bool give_up = window_out && window_end >= max_attempts;
-    if (g_try && leader) {   // no ceiling asked for: a row whose open slots spent 1e5 attempts without ONE accepted draw is written off
-      const int tried = atomicAdd(g_try + g, (int)(resolved ? win + 1 : (int)tried_now)) + (int)(resolved ? win + 1 : (int)tried_now);
-      if (resolved) atomicAdd(g_acc + g, 1);
-      else if (tried >= 100000 && __hip_atomic_load(g_acc + g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) give_up = true;
-    }
-    if (ok && sub == win) {   // the winner writes the draw
-      for (int d = 0; d < a.D; ++d) out[slot * a.D + d] = V[d * RS + lane];
-      if (n_drawn) sf_sat_add(n_drawn + g, (int32_t)(att + 1u));
-    }
-    if (give_up) {
-      for (int d = 0; d < a.D; ++d) out[slot * a.D + d] = __builtin_nanf("");
-      if (n_drawn) sf_sat_add(n_drawn + g, (int32_t)(att0 + tried_now));
-      atomicAdd(n_unfilled, 1u);
-    }
-    if (window_out && !give_up) surv[atomicAdd(n_surv, 1u)] = (uint32_t)slot;   // (hand-over; a row written off by the progress rule is not)
-    const bool again = leader && !resolved && !give_up && !window_out;
-    const unsigned long long m = __ballot(again);
-    if (again) {
-      const int pos = __popcll(m & ((1ull << lane) - 1ull));
-      r_slot[pos] = slot;
-      r_att[pos] = att0 + (uint32_t)W;
-    }
-    n_retry = __popcll(m);
-    ar_barrier();
+// The engine of sf_ar_sampler.h on the LDS rows: one wave per workgroup, lane l serves entry l and carries its side effects.
+struct ArLdsEngine {
+  static constexpr int NE = 64, DD = 0;
+  const ArArgs& a;
+  const SfArLaunch& L;
+  const ZSplC sc;
+  const int lane;
+  float *E0, *H1, *H2, *QB, *V;
+  __device__ __forceinline__ ArLdsEngine(const ArArgs& a_, const SfArLaunch& L_, float* lds, int lane_)
+      : a(a_), L(L_), sc{a_.K, a_.B, a_.cw, a_.cd}, lane(lane_) {
+    E0 = lds;
+    H1 = E0 + a.NIN16 * RS;
+    H2 = H1 + a.Hp * RS;
+    QB = H2 + a.Hp * RS;
+    V = QB + 32 * RS;
+    for (int r = a.D + a.C; r < a.NIN16; ++r) E0[r * RS + lane] = 0.f;
   }
-}
+  __device__ __forceinline__ int dims() const { return a.D; }
+  __device__ __forceinline__ bool lead() const { return true; }
+  __device__ __forceinline__ int col() const { return lane; }
+  __device__ __forceinline__ float value(int d) const { return V[d * RS + lane]; }
+  __device__ __forceinline__ bool candidate(long g, unsigned long long slot, uint32_t att, bool active) {
+    return ar_candidate(a, sc, L, g, slot, att, E0, V, H1, H2, QB, lane, active);
+  }
+  __device__ __forceinline__ void list_seen_dry() {}
+  __device__ __forceinline__ void wave_leaves() {}
+};
 
-// FIND: attempts [base, base + A) of every survivor side by side -- workgroup (e, j) tries attempts base + 64 j + lane of
-// survivor e; an accepted attempt only lowers best[e].  RESOLVE re-evaluates exactly attempt best[e] and writes the draw: the
-// slot keeps its LOWEST accepted attempt, whatever A and the schedule were.
-__global__ __launch_bounds__(64) void k_ar_find(ArArgs a, const float* __restrict__ x, long S, const uint32_t* __restrict__ surv,
-                                                 unsigned int n_surv, uint32_t base, uint32_t chunks, uint32_t att_end,
-                                                 const float* __restrict__ lo, const float* __restrict__ hi, uint32_t k0, uint32_t k1,
-                                                 unsigned long long slot_offset, uint32_t* __restrict__ best, unsigned long long* __restrict__ ctr) {
+// The three sampler kernels: sf_ar_sampler.h's persistent loop, FIND and RESOLVE on 64 candidates per wave
+__global__ __launch_bounds__(64) void k_ar_sample(ArArgs a, SfArLaunch L) {
   extern __shared__ float lds[];
-  float* E0 = lds;
-  float* H1 = E0 + a.NIN16 * RS;
-  float* H2 = H1 + a.Hp * RS;
-  float* QB = H2 + a.Hp * RS;
-  float* V = QB + 32 * RS;
+  __shared__ unsigned long long r_slot[1][64];
+  __shared__ uint32_t r_att[1][64];
   const int lane = threadIdx.x;
-  const ZSplC sc = {a.K, a.B, a.cw, a.cd};
-  for (int r = a.D + a.C; r < a.NIN16; ++r) E0[r * RS + lane] = 0.f;
-  const unsigned int e = blockIdx.x / chunks, j = blockIdx.x - e * chunks;
-  if (e >= n_surv) return;
-  const unsigned long long slot = surv[e];
-  const uint32_t att = base + 64u * j + (uint32_t)lane;
-  const bool active = att < att_end;
-  const long g = (long)(slot / (unsigned long long)S);
-  const bool ok = ar_candidate(a, sc, x, g, slot, att, k0, k1, slot_offset, lo, hi, E0, V, H1, H2, QB, lane, active);
-  if (ok) atomicMin(best + e, att);
-  const unsigned long long ma = __ballot(active);
-  if (lane == 0) atomicAdd(ctr + 2, (unsigned long long)__popcll(ma));
+  ArLdsEngine eng(a, L, lds, lane);
+  ar_sample_loop(eng, L, lane, r_slot[0], r_att[0]);
 }
-__global__ __launch_bounds__(64) void k_ar_resolve(ArArgs a, const float* __restrict__ x, long S, const uint32_t* __restrict__ surv,
-                                                    unsigned int n_surv, const uint32_t* __restrict__ best, uint32_t tried_end,
-                                                    uint32_t max_attempts, const float* __restrict__ lo, const float* __restrict__ hi,
-                                                    uint32_t k0, uint32_t k1, unsigned long long slot_offset, float* __restrict__ out,
-                                                    int32_t* __restrict__ n_drawn, int32_t* __restrict__ g_try, int32_t* __restrict__ g_acc,
-                                                    uint32_t tried_now, uint32_t* __restrict__ next, unsigned int* __restrict__ n_next,
-                                                    unsigned int* __restrict__ n_unfilled) {
+__global__ __launch_bounds__(64) void k_ar_find(ArArgs a, SfArLaunch L, SfArRound R) {
   extern __shared__ float lds[];
-  float* E0 = lds;
-  float* H1 = E0 + a.NIN16 * RS;
-  float* H2 = H1 + a.Hp * RS;
-  float* QB = H2 + a.Hp * RS;
-  float* V = QB + 32 * RS;
   const int lane = threadIdx.x;
-  const ZSplC sc = {a.K, a.B, a.cw, a.cd};
-  for (int r = a.D + a.C; r < a.NIN16; ++r) E0[r * RS + lane] = 0.f;
-  const unsigned int e = blockIdx.x * 64u + (unsigned)lane;
-  const bool exists = e < n_surv;
-  const unsigned long long slot = exists ? surv[e] : 0ull;
-  const uint32_t b = exists ? best[e] : 0xffffffffu;
-  const bool found = exists && b != 0xffffffffu;
-  const long g = exists ? (long)(slot / (unsigned long long)S) : 0;
-  const bool ok = ar_candidate(a, sc, x, g, slot, found ? b : 0u, k0, k1, slot_offset, lo, hi, E0, V, H1, H2, QB, lane, found);
-  if (found) {   // (ok by construction: the find launch accepted this very attempt)
-    for (int d = 0; d < a.D; ++d) out[slot * a.D + d] = ok ? V[d * RS + lane] : __builtin_nanf("");
-    if (n_drawn) sf_sat_add(n_drawn + g, (int32_t)(b + 1u));
-    if (g_acc) atomicAdd(g_acc + g, 1);
-    if (g_try) atomicAdd(g_try + g, (int)tried_now);
-  } else if (exists) {
-    bool give_up = tried_end >= max_attempts;
-    if (g_try) {   // (uncapped: the progress rule, as in k_ar_sample)
-      const int tried = atomicAdd(g_try + g, (int)tried_now) + (int)tried_now;
-      if (tried >= 100000 && __hip_atomic_load(g_acc + g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) give_up = true;
-    }
-    if (give_up) {
-      for (int d = 0; d < a.D; ++d) out[slot * a.D + d] = __builtin_nanf("");
-      if (n_drawn) sf_sat_add(n_drawn + g, (int32_t)tried_end);
-      atomicAdd(n_unfilled, 1u);
-    } else {
-      next[atomicAdd(n_next, 1u)] = (uint32_t)slot;
-    }
-  }
+  ArLdsEngine eng(a, L, lds, lane);
+  ar_find_round(eng, L, R, lane, 0);
+}
+__global__ __launch_bounds__(64) void k_ar_resolve(ArArgs a, SfArLaunch L, SfArRound R) {
+  extern __shared__ float lds[];
+  ArLdsEngine eng(a, L, lds, threadIdx.x);
+  ar_resolve_round(eng, L, R, 0);
 }
 
 // forward (with the inputs of every transform stashed) + loss, then the backward sweep
@@ -1235,20 +1083,38 @@ int sf_nsfar_inverse(SfNsfAr* n, const float* z, const float* x, long B, float* 
   return SF_OK;
 }
 
-int sf_nsfar_sample(SfNsfAr* n, const float* x, long M, long S, const uint32_t* slots, long n_slots, const float* lo, const float* hi,
-                    uint32_t k0, uint32_t k1, unsigned long long slot_offset, int max_attempts, float* out, int32_t* n_drawn,
-                    int32_t* count, int64_t* n_unfilled, hipStream_t st, std::string& err, hipEvent_t ev0, hipEvent_t ev1) {
-  SF_TRY_ERR(hipMemsetAsync(n->d_ctr, 0, 8 * sizeof(unsigned long long), st));
+// The three launches of a sampling call.  Each picks the engine itself: the 16-candidate register tiles where the shape takes them
+// (sf_nsfar16_eligible), the 64-candidate LDS rows otherwise.
+static hipError_t ar_launch_persistent(const SfNsfAr& n, const SfArLaunch& L, hipStream_t st) {
   static int cus = 0;   // (asked once: the query costs more than a small sampling call)
   if (!cus) {
     int dev = 0;
     hipDeviceProp_t pr;
     cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256;
   }
-  const size_t lds = sf_nsfar_lds_bytes(*n, 2, 1);
+  if (sf_nsfar16_eligible(n)) return sf_nsfar16_launch(n, L, cus, st);
+  const size_t lds = sf_nsfar_lds_bytes(n, 2, 1);
   const long per_cu = (long)((size_t)160 * 1024 / (lds + 1024));
   long grid = (long)cus * (per_cu < 1 ? 1 : (per_cu > 8 ? 8 : per_cu));
-  if (grid > (n_slots + 63) / 64) grid = (n_slots + 63) / 64;
+  if (grid > (L.n_slots + 63) / 64) grid = (L.n_slots + 63) / 64;
+  hipLaunchKernelGGL(k_ar_sample, dim3((unsigned)grid), dim3(64), lds, st, args_of(n), L);
+  return hipGetLastError();
+}
+static hipError_t ar_launch_find(const SfNsfAr& n, const SfArLaunch& L, const SfArRound& R, hipStream_t st) {
+  if (sf_nsfar16_eligible(n)) return sf_nsfar16_find(n, L, R, st);
+  hipLaunchKernelGGL(k_ar_find, dim3(R.n_surv * R.chunks), dim3(64), sf_nsfar_lds_bytes(n, 2, 1), st, args_of(n), L, R);
+  return hipGetLastError();
+}
+static hipError_t ar_launch_resolve(const SfNsfAr& n, const SfArLaunch& L, const SfArRound& R, hipStream_t st) {
+  if (sf_nsfar16_eligible(n)) return sf_nsfar16_resolve(n, L, R, st);
+  hipLaunchKernelGGL(k_ar_resolve, dim3((R.n_surv + 63u) / 64u), dim3(64), sf_nsfar_lds_bytes(n, 2, 1), st, args_of(n), L, R);
+  return hipGetLastError();
+}
+
+int sf_nsfar_sample(SfNsfAr* n, const float* x, long M, long S, const uint32_t* slots, long n_slots, const float* lo, const float* hi,
+                    uint32_t k0, uint32_t k1, unsigned long long slot_offset, int max_attempts, float* out, int32_t* n_drawn,
+                    int32_t* count, int64_t* n_unfilled, hipStream_t st, std::string& err, hipEvent_t ev0, hipEvent_t ev1) {
+  SF_TRY_ERR(hipMemsetAsync(n->d_ctr, 0, 8 * sizeof(unsigned long long), st));
   // no ceiling asked for: the row-level progress rule of the kernel, and 2^20 attempts per slot at the very most
   const uint32_t cap = count ? 1u : (max_attempts > 0 ? (uint32_t)max_attempts : (1u << 20));
   int32_t* g_try = nullptr;
@@ -1283,17 +1149,9 @@ int sf_nsfar_sample(SfNsfAr* n, const float* x, long M, long S, const uint32_t* 
     }
   }
   unsigned int* d_ns = reinterpret_cast<unsigned int*>(n->d_ctr + 4);   // [0], [1]: survivor counts of the two lists
-  const bool tiles16 = sf_nsfar16_eligible(*n);   // 16-sample register tiles, four independent waves per workgroup (sf_nsfar16.hip)
-  const SfAr16Launch L = {x, S, slots, n_slots, lo, hi, k0, k1, slot_offset, cap, out, n_drawn, count, n->d_ctr,
-                          reinterpret_cast<unsigned int*>(n->d_ctr + 1), g_try, g_try ? g_try + M : nullptr, walk_R, walk_C, window, n->d_surv[0], d_ns};
-  if (tiles16) {
-    SF_TRY_ERR(sf_nsfar16_launch(*n, L, cus, st));
-  } else {
-    hipLaunchKernelGGL(k_ar_sample, dim3((unsigned)grid), dim3(64), lds, st, args_of(*n), x, S, slots, n_slots, lo, hi, k0, k1, slot_offset, cap, out,
-                       n_drawn, count, n->d_ctr, reinterpret_cast<unsigned int*>(n->d_ctr + 1), g_try, g_try ? g_try + M : nullptr, walk_R, walk_C,
-                       window, n->d_surv[0], d_ns);
-  }
-  SF_TRY_ERR(hipGetLastError());
+  const SfArLaunch L = {x, S, slots, n_slots, lo, hi, k0, k1, slot_offset, cap, out, n_drawn, count, n->d_ctr,
+                        reinterpret_cast<unsigned int*>(n->d_ctr + 1), g_try, g_try ? g_try + M : nullptr, walk_R, walk_C, window, n->d_surv[0], d_ns};
+  SF_TRY_ERR(ar_launch_persistent(*n, L, st));
   if (ev1) SF_TRY_ERR(hipEventRecord(ev1, st));
   unsigned long long* h = n->h_ctr;   // (pinned: a read-back into pageable memory is a staged, host-synchronous copy)
   for (int i = 0; i < 8; ++i) h[i] = 0;
@@ -1309,36 +1167,21 @@ int sf_nsfar_sample(SfNsfAr* n, const float* x, long M, long S, const uint32_t* 
       while (2u * A <= base && (uint64_t)(2u * A) * ns <= (1ull << 22) && 2u * A <= 65536u) A *= 2;
       if ((uint64_t)base + A > cap) A = (uint32_t)(((uint64_t)cap - base + 63u) / 64u * 64u);
       const uint32_t att_end = (uint64_t)base + A > cap ? cap : base + A;
-      const uint32_t chunks = A / 64u;
+      const SfArRound R = {n->d_surv[cur], ns, n->d_best, base, A / 64u, att_end, n->d_surv[cur ^ 1], d_ns + (cur ^ 1)};   // (64 attempts per find workgroup)
       SF_TRY_ERR(hipMemsetAsync(n->d_best, 0xff, (size_t)ns * sizeof(uint32_t), st));
       SF_TRY_ERR(hipMemsetAsync(d_ns + (cur ^ 1), 0, sizeof(unsigned int), st));
-      if (tiles16) {
-        SF_TRY_ERR(sf_nsfar16_find(*n, L, n->d_surv[cur], ns, base, chunks, att_end, n->d_best, n->d_ctr, st));
-        SF_TRY_ERR(sf_nsfar16_resolve(*n, L, n->d_surv[cur], ns, n->d_best, att_end, att_end - base, n->d_surv[cur ^ 1], d_ns + (cur ^ 1), st));
-      } else {
-        hipLaunchKernelGGL(k_ar_find, dim3(ns * chunks), dim3(64), lds, st, args_of(*n), x, S, n->d_surv[cur], ns, base, chunks, att_end, lo, hi, k0, k1,
-                           slot_offset, n->d_best, n->d_ctr);
-        hipLaunchKernelGGL(k_ar_resolve, dim3((ns + 63u) / 64u), dim3(64), lds, st, args_of(*n), x, S, n->d_surv[cur], ns, n->d_best, att_end, cap, lo, hi,
-                           k0, k1, slot_offset, out, n_drawn, g_try, g_try ? g_try + M : nullptr, att_end - base, n->d_surv[cur ^ 1], d_ns + (cur ^ 1),
-                           reinterpret_cast<unsigned int*>(n->d_ctr + 1));
-      }
-      SF_TRY_ERR(hipGetLastError());
+      SF_TRY_ERR(ar_launch_find(*n, L, R, st));
+      SF_TRY_ERR(ar_launch_resolve(*n, L, R, st));
       base = att_end;
       cur ^= 1;
     }
     const unsigned int left = reinterpret_cast<const unsigned int*>(h + 4)[cur];
     if (left > 0) {   // (the ceiling was reached with slots still open: NaN rows)
       SF_TRY_ERR(hipMemsetAsync(n->d_best, 0xff, (size_t)left * sizeof(uint32_t), st));
-      if (tiles16) {
-        SfAr16Launch Lf = L;
-        Lf.g_try = nullptr; Lf.g_acc = nullptr;
-        SF_TRY_ERR(sf_nsfar16_resolve(*n, Lf, n->d_surv[cur], left, n->d_best, cap, 0u, n->d_surv[cur ^ 1], d_ns + (cur ^ 1), st));
-      } else {
-        hipLaunchKernelGGL(k_ar_resolve, dim3((left + 63u) / 64u), dim3(64), lds, st, args_of(*n), x, S, n->d_surv[cur], left, n->d_best, cap, cap, lo, hi,
-                           k0, k1, slot_offset, out, n_drawn, (int32_t*)nullptr, (int32_t*)nullptr, 0u, n->d_surv[cur ^ 1], d_ns + (cur ^ 1),
-                           reinterpret_cast<unsigned int*>(n->d_ctr + 1));
-      }
-      SF_TRY_ERR(hipGetLastError());
+      SfArLaunch Lf = L;
+      Lf.g_try = nullptr; Lf.g_acc = nullptr;
+      const SfArRound R = {n->d_surv[cur], left, n->d_best, cap, 0u, cap, n->d_surv[cur ^ 1], d_ns + (cur ^ 1)};   // (nothing tried: write-off only)
+      SF_TRY_ERR(ar_launch_resolve(*n, Lf, R, st));
     }
     SF_TRY_ERR(hipMemcpyAsync(h, n->d_ctr, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     SF_TRY_ERR(hipStreamSynchronize(st));

@@ -17,15 +17,18 @@
 //   * the spline inverse runs on the head tiles as the MFMA left them (a16_spline_inv: the width pair and the height pair of lane
 //     groups work on four bins each and exchange the selected bin: twelve cross-lane moves, no transposition through memory);
 //   * occupancy is set by registers alone: three waves per SIMD (two / one for the two-tile shapes) instead of half a wave.
-// Control flow (work queue, retry compaction, speculation once the list has run dry, survivor hand-over to the find / resolve
-// rounds, which run the same candidate routine) is k_ar_sample's with 16 entries per wave; the four waves of a workgroup never
-// meet; the evaluation statistics stay in the wave until it leaves (per round they were two atomics on the queue head's cache line).
+// Control flow (work queue, retry compaction, speculation once the list has run dry, survivor hand-over, the find / resolve rounds)
+// is that of sf_ar_sampler.h with 16 entries per wave, lane < 16 carrying the side effects -- written out in this file's three
+// kernels, not instantiated from that header: any inlined layer between these kernels and a16_candidate changes the optimiser's
+// output for the two-tile shapes (D >= 6: two to three times the spilled registers), so the bodies stay in the kernels until
+// the templates can be used at the parent's register counts.  A change to the control flow is made there AND here.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 
+#include "sf_ar_sampler.h"
 #include "sf_device.h"
 #include "sf_internal.h"
 #include "sf_nsfar.h"
@@ -48,7 +51,7 @@ struct Ar16Args {
   int o_F0, o_fb0, o_F1, o_fb1, o_F2, o_b2;
   float B, cw, cd;
   float th_scale[8], th_shift[8];
-  SfAr16Launch L;
+  SfArLaunch L;
 #ifdef SF_A16_TRACE
   unsigned long long* trace;   // developer build: cycle stamps of wave 0 of workgroup 0
 #endif
@@ -280,7 +283,7 @@ template <int DD, int NI, int KS, int TPT>
 __device__ __forceinline__ bool a16_candidate(const Ar16Args& a, const ZSplC& sc, long g, unsigned long long slot, uint32_t att, int lane,
                                               bool active, float (&th)[DD]) {
   const int g4 = lane >> 4;
-  const SfAr16Launch& L = a.L;
+  const SfArLaunch& L = a.L;
   A16_TS(0);
   f32x4 E[NI], H1[DD * TPT], H2[DD * TPT];
 #pragma unroll
@@ -364,12 +367,6 @@ __device__ __forceinline__ bool a16_candidate(const Ar16Args& a, const ZSplC& sc
   return ok;
 }
 
-// order the LDS traffic of ONE wave (the retry list is wave-private)
-__device__ __forceinline__ void a16_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
 // Rejection sampler: every wave works (slot, attempt) items, sixteen at a time -- its own rejects first -- until the slot list is
 // exhausted (k_ar_sample's queue, walk order, speculation and survivor hand-over; see there).  Lane l serves entry l & 15; the
 // four lanes of an entry compute the same candidate, lane < 16 carries the side effects.
@@ -380,7 +377,7 @@ template <int DD, int NI, int KS, int TPT>
 __global__ __launch_bounds__(256, TPT == 1 ? SF_A16_WGS : (DD <= 5 ? 2 : 1)) void k_ar_samp16(Ar16Args a) {
   __shared__ unsigned long long r_slot[4][16];
   __shared__ uint32_t r_att[4][16];
-  const SfAr16Launch& L = a.L;
+  const SfArLaunch& L = a.L;
   const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int s = lane & 15;
   const bool lead = lane < 16;
@@ -449,7 +446,7 @@ __global__ __launch_bounds__(256, TPT == 1 ? SF_A16_WGS : (DD <= 5 ? 2 : 1)) voi
     }
     const uint32_t att = att0 + (uint32_t)sub;
     const bool active = exists && att < L.window_end;
-    a16_wave_sync();   // (the retry list has been read)
+    ar_wave_sync();   // (the retry list has been read)
     const long g = !exists ? 0 : (small ? (long)((uint32_t)slot / (uint32_t)S) : (long)(slot / (unsigned long long)S));
     float th[DD];
     const bool ok = a16_candidate<DD, NI, KS, TPT>(a, sc, g, slot, att, lane, active, th);
@@ -502,7 +499,7 @@ __global__ __launch_bounds__(256, TPT == 1 ? SF_A16_WGS : (DD <= 5 ? 2 : 1)) voi
       r_att[wv][pos] = att0 + (uint32_t)W;
     }
     n_retry = __popcll(m);
-    a16_wave_sync();
+    ar_wave_sync();
   }
 }
 
@@ -531,7 +528,7 @@ template <int DD, int NI, int KS, int TPT>
 __global__ __launch_bounds__(256, TPT == 1 ? SF_A16_WGS : (DD <= 5 ? 2 : 1)) void k_ar_resolve16(Ar16Args a, const uint32_t* __restrict__ surv, unsigned int n_surv,
                                                                   const uint32_t* __restrict__ best, uint32_t tried_end, uint32_t tried_now,
                                                                   uint32_t* __restrict__ next, unsigned int* __restrict__ n_next) {
-  const SfAr16Launch& L = a.L;
+  const SfArLaunch& L = a.L;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const ZSplC sc = {a.K, a.B, a.cw, a.cd};
   const unsigned int e = blockIdx.x * 64u + 16u * (unsigned)wv + (unsigned)(lane & 15);
@@ -591,7 +588,7 @@ bool sf_nsfar16_eligible(const SfNsfAr& n) {
          (n.s16_ni == 1 || n.s16_ni == 2);
 }
 
-static Ar16Args a16_args(const SfNsfAr& n, const SfAr16Launch& L) {
+static Ar16Args a16_args(const SfNsfAr& n, const SfArLaunch& L) {
   Ar16Args a;
   a.img = n.d_img; a.dimof = n.d_dimof; a.xmean = n.d_xmean; a.xstd = n.d_xstd;
   a.D = n.D; a.C = n.C; a.T = n.T; a.K = n.K; a.affine = n.affine;
@@ -631,7 +628,7 @@ static hipError_t a16_dispatch(const SfNsfAr& n, F f) {
 #undef A16_CASE
 }
 
-hipError_t sf_nsfar16_launch(const SfNsfAr& n, const SfAr16Launch& L, int cus, hipStream_t st) {
+hipError_t sf_nsfar16_launch(const SfNsfAr& n, const SfArLaunch& L, int cus, hipStream_t st) {
   Ar16Args a = a16_args(n, L);
 #ifdef SF_A16_TRACE
   static unsigned long long* d_tr = nullptr;
@@ -653,22 +650,21 @@ hipError_t sf_nsfar16_launch(const SfNsfAr& n, const SfAr16Launch& L, int cus, h
   return a16_dispatch(n, [&](auto dd, auto ni, auto ks, auto tpt) { return launch16<decltype(dd)::value, decltype(ni)::value, decltype(ks)::value, decltype(tpt)::value>(a, cus, st); });
 }
 
-hipError_t sf_nsfar16_find(const SfNsfAr& n, const SfAr16Launch& L, const uint32_t* surv, unsigned int n_surv, uint32_t base, uint32_t chunks,
-                           uint32_t att_end, uint32_t* best, unsigned long long* ctr, hipStream_t st) {
+// the chip-wide rounds: R unpacked into the kernels' loose arguments (they stay in scalar registers; ctr = the call's counters)
+hipError_t sf_nsfar16_find(const SfNsfAr& n, const SfArLaunch& L, const SfArRound& R, hipStream_t st) {
   const Ar16Args a = a16_args(n, L);
   return a16_dispatch(n, [&](auto dd, auto ni, auto ks, auto tpt) {
-    hipLaunchKernelGGL((k_ar_find16<decltype(dd)::value, decltype(ni)::value, decltype(ks)::value, decltype(tpt)::value>), dim3(n_surv * chunks), dim3(256), 0, st, a, surv, n_surv, base, chunks,
-                       att_end, best, ctr);
+    hipLaunchKernelGGL((k_ar_find16<decltype(dd)::value, decltype(ni)::value, decltype(ks)::value, decltype(tpt)::value>), dim3(R.n_surv * R.chunks), dim3(256), 0, st, a, R.surv, R.n_surv,
+                       R.base, R.chunks, R.att_end, R.best, L.cursor);
     return hipGetLastError();
   });
 }
 
-hipError_t sf_nsfar16_resolve(const SfNsfAr& n, const SfAr16Launch& L, const uint32_t* surv, unsigned int n_surv, const uint32_t* best,
-                              uint32_t tried_end, uint32_t tried_now, uint32_t* next, unsigned int* n_next, hipStream_t st) {
+hipError_t sf_nsfar16_resolve(const SfNsfAr& n, const SfArLaunch& L, const SfArRound& R, hipStream_t st) {
   const Ar16Args a = a16_args(n, L);
   return a16_dispatch(n, [&](auto dd, auto ni, auto ks, auto tpt) {
-    hipLaunchKernelGGL((k_ar_resolve16<decltype(dd)::value, decltype(ni)::value, decltype(ks)::value, decltype(tpt)::value>), dim3((n_surv + 63u) / 64u), dim3(256), 0, st, a, surv, n_surv, best,
-                       tried_end, tried_now, next, n_next);
+    hipLaunchKernelGGL((k_ar_resolve16<decltype(dd)::value, decltype(ni)::value, decltype(ks)::value, decltype(tpt)::value>), dim3((R.n_surv + 63u) / 64u), dim3(256), 0, st, a, R.surv, R.n_surv,
+                       (const uint32_t*)R.best, R.att_end, R.att_end - R.base, R.next, R.n_next);
     return hipGetLastError();
   });
 }

@@ -270,6 +270,28 @@ def test_autoregressive_nsf_deep_tail_rounds_keep_the_lowest_accepted_attempt():
     assert (bad_g <= np.minimum(off_g, 3)).all() and bad_g.sum() <= 4, (bad_g, off_g)
 
 
+def test_autoregressive_nsf_deep_tail_rounds_on_the_lds_engine():
+    """The deep-tail case on a shape that takes the 64-candidate LDS engine by itself (33 hidden units per type): the same
+    persistent loop and FIND / RESOLVE rounds (sf_ar_sampler.h) around the other candidate routine, in-process.  Box: the
+    45..55 % quantiles of the oracle's free draws; the oracle alone needs 59 073 attempts for the 72 slots of this seed (820 per
+    slot, the assertion asks for more than 256), so most slots outlive the 256-attempt window.  Bars as in the register-tile test above."""
+    ospec, spec, flat, theta, x = make_case("nsfar_33", B=3, spread=0.2)
+    f = _flow(spec, flat)
+    assert f.describe()["sampler_tiles16"] == 0
+    S, seed = 24, 77
+    free, _ = OP.sample(ospec, torch.as_tensor(flat), x, 4000, 5, dtype=torch.float32)
+    lo = np.quantile(free.reshape(-1, spec.D), 0.45, axis=0).astype(np.float32)
+    hi = np.quantile(free.reshape(-1, spec.D), 0.55, axis=0).astype(np.float32)
+    got, nd = f.sample(x, S, lo, hi, seed=seed, return_counts=True)
+    got, nd = got.cpu().double().numpy(), nd.cpu().numpy()
+    ref, rnd = OP.sample(ospec, torch.as_tensor(flat), x, S, seed, lo, hi, dtype=torch.float32)
+    assert f.last_unfilled == 0 and np.isfinite(got).all() and ((got >= lo) & (got <= hi)).all()
+    assert rnd.sum() > 256 * S * len(x)          # (the rounds really ran)
+    err = np.abs((got - ref) / (hi - lo).astype(np.float64)).max(-1)
+    bad_g, off_g = (err > 1e-3).sum(1), np.abs(nd - rnd)
+    assert (bad_g <= np.minimum(off_g, 3)).all() and bad_g.sum() <= 4, (bad_g, off_g)
+
+
 @pytest.mark.parametrize("name", ["maf_cfg1", "nsf_cfg3", "nsf_odd", "maf_wide", "nsf_nb1", "maf_span6", "maf_span_h64"])
 def test_context_table_round_equals_per_draw_round(name):
     """sf_flow_prepare_context only moves the context products out of the per-draw work: a dense round and a
