@@ -511,6 +511,65 @@ int sf_scatter_empirical(const float* flux /*[N,C] device*/, int64_t N, int32_t 
 int sf_apply_scalings(const float* flux, const float* err, int64_t N, int32_t C, const sf_noise_band* bands /*[C] host*/,
                       const float* table /*[n_table] host*/, int64_t n_table, float* out, float* err_out, void* stream);
 
+/* ---- spectral libraries: observed-frame spectra features (csrc/sf_spectra.hip; driven by synference_amd/spectra.py) ------
+ * Every pointer is a DEVICE pointer; the struct itself is read on the host.  Field order and types are mirrored by the ctypes
+ * Structure of the same name (synference_amd/_lib.py).  Per row i of flux [N, ld_flux] on the ascending grid wave[L] (um):
+ *   SF_SPECTRA_TRANSFORM (ref: utils.py:185-254): wz = wave (1 + z[i]); sigma = sqrt(max(s_inst^2 - s_th^2, 0)) / pix in fp64,
+ *     s_inst = wz / interp(wz, curve_wave, curve_r) / 2 sqrt(2 ln 2), s_th the same with theory_r (theory_r_arr[L] when not
+ *     NULL), pix = the median of diff(wz) = the mean of the differences at med_lo and med_hi (the host names the middle one
+ *     or two); the variable-width Gaussian (sigma <= 0.01: copied; else weights exp(-x^2 / 2 sigma^2), |x| <= ceil(trunc sigma),
+ *     divided by their sum, indices clamped to the row); then SpectRes with fill 0 onto observed_wave[M]; the flux is not
+ *     divided by 1 + z.  out [N, ld_out], M values per row.
+ *   SF_SPECTRA_CONVOLVE (ref: utils.py:129-182): the Gaussian alone with sigma_pixels[i * sigma_stride + .] (stride 0: one
+ *     row for all); out holds L values per row, no normalisation, units or clip.
+ *   SF_SPECTRA_UNITS: nothing is convolved or rebinned; out[i, j] = flux[i, col0 + j], j < M, through the steps below.
+ *   A pixel whose half-width exceeds h_limit, or whose sigma is NaN, comes out NaN: h_limit bounds the tap loop.
+ * Normalisation (ref: sbi_runner.py:1096-1178): tophat and bandpass are both a linear functional of the spectrum, so the
+ * host hands over its coefficients: the factor is sum(flux norm_table[L]) over the raw row (SF_SPECTRA_NORM_REST, and either
+ * frame in SF_SPECTRA_UNITS, where the reference normalises on the uncropped theory grid too) or sum(bins norm_table[M])
+ * over the rebinned row (SF_SPECTRA_NORM_OBSERVED); the row is divided by it, a factor of 0 gives a row of 0.
+ * Units and clip (ref: 1361-1381): LINEAR v unit_scale; LOG10 log10(v unit_scale); AB -2.5 log10(v unit_scale) + 8.9 with
+ * unit_scale = Jy per grid unit (negative flux NaN, zero +inf); then clipped to [clip_lo, clip_hi], NaN kept.
+ * SF_ERR_INVALID with a message and nothing launched: L above SF_SPECTRA_MAX_L (two float arrays of L in LDS) unless
+ * SF_SPECTRA_UNITS, a curve above SF_SPECTRA_MAX_CURVE nodes, fewer than 2 pixels on a grid that needs bin edges, h_limit
+ * outside 1 .. SF_SPECTRA_MAX_HALF_WIDTH, a stride shorter than its row.  N == 0: SF_OK.  Asynchronous on `stream`. */
+#define SF_SPECTRA_UNITS 0
+#define SF_SPECTRA_TRANSFORM 1
+#define SF_SPECTRA_CONVOLVE 2
+#define SF_SPECTRA_NORM_NONE 0
+#define SF_SPECTRA_NORM_REST 1
+#define SF_SPECTRA_NORM_OBSERVED 2
+#define SF_SPECTRA_UNIT_LINEAR 0
+#define SF_SPECTRA_UNIT_LOG10 1
+#define SF_SPECTRA_UNIT_AB 2
+#define SF_SPECTRA_MAX_L 16384
+#define SF_SPECTRA_MAX_CURVE 256
+#define SF_SPECTRA_MAX_HALF_WIDTH 65536
+typedef struct sf_spectra_desc {
+  const float* flux;            /* [N, ld_flux] */
+  const double* wave;           /* [L] um, ascending */
+  const double* z;              /* [N]; TRANSFORM only */
+  const double* sigma_pixels;   /* CONVOLVE only */
+  const double* observed_wave;  /* [M] um, ascending; TRANSFORM only */
+  const double* curve_wave;     /* [n_curve] um, ascending */
+  const double* curve_r;        /* [n_curve] */
+  const double* theory_r_arr;   /* [L] or NULL: then theory_r */
+  const double* norm_table;     /* [L] or [M]; NULL with SF_SPECTRA_NORM_NONE */
+  float* out;                   /* [N, ld_out] */
+  int64_t N, ld_flux, ld_out, sigma_stride;
+  int32_t mode;                 /* SF_SPECTRA_UNITS / TRANSFORM / CONVOLVE */
+  int32_t L, M, n_curve;
+  int32_t col0;                 /* UNITS: first kept column */
+  int32_t norm_frame;           /* SF_SPECTRA_NORM_* */
+  int32_t unit_code;            /* SF_SPECTRA_UNIT_* */
+  int32_t med_lo, med_hi;       /* TRANSFORM: the middle difference(s) of diff(wave) */
+  int32_t h_limit;
+  double theory_r;              /* may be inf */
+  double trunc;
+  float unit_scale, clip_lo, clip_hi;
+} sf_spectra_desc;
+int sf_spectra_transform(const sf_spectra_desc* desc, void* stream);
+
 /* PIT ranks of the truths among the posterior draws: out[g,d] = #{draws < truth} / #{finite draws}.
  * Replaces the host pass at ref: sbi_runner.py:7153-7158. */
 int sf_pit_ranks(const float* samples /*[N,S,D]*/, const float* truth /*[N,D]*/, int64_t N, int64_t S, int32_t D,

@@ -9,7 +9,7 @@ fmt() {
     sed 's/.*remark: [^ ]* //; s/\[-Rpass-analysis=kernel-resource-usage\]//' | paste - - - - - - - - - |
     sed 's/Function Name: //; s/[ \t]\+/ /g'   # (names stay mangled: template arguments are readable as Li<N>E / Lb<0|1>E)
 }
-for f in sf_maf16.hip sf_kernels.hip sf_train.hip sf_mlp.hip sf_post.hip sf_nsfar.hip sf_nsfar16.hip; do
+for f in sf_maf16.hip sf_kernels.hip sf_train.hip sf_mlp.hip sf_post.hip sf_nsfar.hip sf_nsfar16.hip sf_spectra.hip; do
   echo "## $f"; hipcc $FLAGS -c $f -o /dev/null 2>&1 | fmt
 done
 for k in 0 1; do for h in 2; do

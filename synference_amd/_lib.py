@@ -49,6 +49,18 @@ class sf_noise_band(C.Structure):
                                          "std_at_limit", "err_value", "min_err", "max_err")]
 
 
+class sf_spectra_desc(C.Structure):
+    """The call descriptor of ``sf_spectra_transform`` (field order of include/synference_hip.h); every pointer is a device
+    address."""
+    _fields_ = [(n, C.c_void_p) for n in ("flux", "wave", "z", "sigma_pixels", "observed_wave", "curve_wave", "curve_r",
+                                          "theory_r_arr", "norm_table", "out")] + \
+               [(n, C.c_int64) for n in ("N", "ld_flux", "ld_out", "sigma_stride")] + \
+               [(n, C.c_int32) for n in ("mode", "L", "M", "n_curve", "col0", "norm_frame", "unit_code", "med_lo", "med_hi",
+                                         "h_limit")] + \
+               [("theory_r", C.c_double), ("trunc", C.c_double)] + \
+               [(n, C.c_float) for n in ("unit_scale", "clip_lo", "clip_hi")]
+
+
 # name -> (restype, argtypes); mirrors include/synference_hip.h one for one
 PROTOTYPES = {
     "sf_flow_create": (C.c_int, [C.POINTER(sf_flow_desc), C.POINTER(C.c_void_p)]),
@@ -76,6 +88,7 @@ PROTOTYPES = {
                                        C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sf_apply_scalings": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(sf_noise_band), c_f32p, C.c_int64,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sf_spectra_transform": (C.c_int, [C.POINTER(sf_spectra_desc), C.c_void_p]),
     "sf_pit_ranks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
     "sf_tarp_coverage": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
                                    C.c_int32, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -152,8 +152,110 @@ class SBI_Fitter:
             return self.create_feature_array_from_raw_photometry(normed_flux_units=flux_units, extra_features=extra_features,
                                                                  **kwargs)
         if self.observation_type == "spectra":
-            raise ValueError("feature arrays from raw spectra are outside the HIP path")
+            return self.create_feature_array_from_raw_spectra(normed_flux_units=flux_units, extra_features=extra_features,
+                                                              **kwargs)
         raise ValueError(f"Observation type {self.observation_type} not supported. Please use 'photometry' or 'spectra'.")
+
+    def create_feature_array_from_raw_spectra(self, extra_features=["redshift"], crop_wavelength_range: Union[tuple, list] = None,
+                                              normed_flux_units: str = "AB", flux_norm_method: Optional[str] = None,
+                                              flux_norm_parameters: dict = None, parameters_to_remove: list = None,
+                                              parameters_to_add: list = None, parameter_transformations: dict = None,
+                                              resample_wavelengths=None, inst_resolution_wavelengths=None,
+                                              inst_resolution_r=None, theory_r: float = np.inf,
+                                              min_flux_value: float = -np.inf, max_flux_value: float = np.inf):
+        """ref: sbi_runner.py:1180-1427 -- the library's (L, N) spectra (wavelengths in um as ``raw_observation_names``) become
+        the (N, M + extras) float32 feature array, with the per-spectrum work on the device (``sf_spectra_transform``).
+
+        The reference's argument names, order and defaults.  With ``redshift`` among the parameters every spectrum is
+        redshifted, convolved with the instrument's line-spread function (``inst_resolution_wavelengths`` in um,
+        ``inst_resolution_r``, less the model's own ``theory_r``) and rebinned onto ``resample_wavelengths`` (um;
+        ``crop_wavelength_range`` then crops those, in the observed frame); without it ``crop_wavelength_range`` crops the
+        theory grid and nothing is convolved or rebinned.  ``flux_norm_method`` "tophat" (``center``, ``width`` in um) or
+        "bandpass" (``filter``: an object with ``.lam`` and ``.transmission``, or a ``(wavelength_um, transmission)`` pair)
+        divides every spectrum by its mean flux there, on the theory grid with ``flux_norm_parameters["rest_frame"]``, else
+        on the final grid; then ``normed_flux_units`` ("AB", "log10 <unit>" or a unit of ``noise_models.PHYSICAL_UNITS``),
+        the clip to [``min_flux_value``, ``max_flux_value``] and the ``extra_features`` columns from the parameter array.
+        Wavelengths are plain arrays in um (anything with ``to_value("um")`` is converted).  ``self.feature_wavelengths``
+        holds the M output wavelengths.  Deviations from the reference: DESIGN.md, "Spectra features"."""
+        from . import spectra as SP
+        if self.observation_type != "spectra":
+            raise ValueError("This method is only for spectra models.")
+        if self.raw_observation_grid is None:
+            raise ValueError("Raw observation library is not set. Please provide a valid library.")
+        extra_features = [] if extra_features is None else extra_features
+        if not isinstance(extra_features, list):
+            raise ValueError("extra_features must be a list of feature names.")
+        parameters_to_remove = [] if parameters_to_remove is None else parameters_to_remove
+        parameters_to_add = [] if parameters_to_add is None else parameters_to_add
+        norm_pars = {} if flux_norm_parameters is None else flux_norm_parameters
+        if flux_norm_method is not None and (callable(flux_norm_method) or flux_norm_method not in ("tophat", "bandpass")):
+            raise ValueError(f'flux_norm_method {flux_norm_method!r} is outside the HIP path: use "tophat" or "bandpass"')
+        if getattr(self, "parameter_array", None) is None:
+            raise ValueError("no parameter array: build the fitter from a library or pass parameter_array")
+        pnames = [str(p) for p in self.parameter_names]
+        extra_cols = []
+        for feature in extra_features:
+            if feature not in [str(p) for p in self.fitted_parameter_names] or feature not in pnames:
+                raise ValueError(f"Feature {feature} not found in parameter names.")
+            extra_cols.append(pnames.index(feature))
+        wavs = SP._grid(np.array(self.raw_observation_names, dtype=float), "the library's wavelength grid")
+        grid = self.raw_observation_grid
+        if grid.ndim != 2 or grid.shape[0] != len(wavs) or grid.shape[1] != self.parameter_array.shape[0]:
+            raise ValueError("the spectra grid must be (len(raw_observation_names), number of parameter rows)")
+        unit_code, unit_scale = SP.unit_conversion(self._grid_flux_unit(), normed_flux_units)
+        has_redshift = "redshift" in pnames
+        is_rest_norm = bool(norm_pars.get("rest_frame", False))
+        kw = dict(unit_code=unit_code, unit_scale=unit_scale, clip=(min_flux_value, max_flux_value))
+        if has_redshift:
+            # (the reference asserts: the same exception type and messages)
+            if resample_wavelengths is None:
+                raise AssertionError("resample_wavelengths must be provided when transforming to observed frame.")
+            if inst_resolution_wavelengths is None:
+                raise AssertionError("inst_resolution_wavelengths must be provided for convolution.")
+            if inst_resolution_r is None:
+                raise AssertionError("inst_resolution_r must be provided for convolution.")
+            out_wavs = SP._grid(resample_wavelengths, "resample_wavelengths")
+            if crop_wavelength_range is not None:
+                logger.warning('Assuming crop_wavelength_range is in observed frame when "redshift" is a feature.')
+                out_wavs = out_wavs[(out_wavs >= crop_wavelength_range[0]) & (out_wavs <= crop_wavelength_range[1])]
+            resample_wavelengths = out_wavs
+            kw.update(observed_wave=out_wavs, resolution_curve_wave=inst_resolution_wavelengths,
+                      resolution_curve_r=inst_resolution_r, theory_r=theory_r)
+            zcol = np.asarray(self.parameter_array[:, pnames.index("redshift")], np.float64)
+        else:
+            mask = np.ones(len(wavs), bool) if crop_wavelength_range is None else \
+                (wavs >= crop_wavelength_range[0]) & (wavs <= crop_wavelength_range[1])
+            first = int(np.argmax(mask)) if mask.any() else 0
+            kw.update(columns=(first, int(mask.sum())))
+            out_wavs = wavs[mask]
+        if flux_norm_method is not None:
+            on_theory = is_rest_norm or not has_redshift      # without a redshift both frames are the uncropped theory grid
+            kw.update(norm_frame=SP.NORM_REST if on_theory else SP.NORM_OBSERVED,
+                      norm_table=SP.norm_coefficients(wavs if on_theory else out_wavs, flux_norm_method, norm_pars))
+        N, L, M = grid.shape[1], len(wavs), len(out_wavs)
+        feat = torch.empty((N, M + len(extra_cols)), dtype=torch.float32, device=self.device)
+        rows = max(1, (1 << 30) // (4 * L))                   # the (L, N) grid transposed in row chunks of about 1 GiB
+        for a in range(0, N, rows):
+            b = min(N, a + rows)
+            chunk = torch.from_numpy(np.ascontiguousarray(grid[:, a:b].T, dtype=np.float32)).to(self.device)
+            SP.spectra_features(chunk, wavs, z=zcol[a:b] if has_redshift else None, out=feat[a:b], **kw)
+        for i, c in enumerate(extra_cols):
+            feat[:, M + i] = torch.from_numpy(np.asarray(self.parameter_array[:, c], np.float32)).to(self.device)
+        self.feature_array = np.ascontiguousarray(feat.cpu().numpy())
+        self.feature_wavelengths = np.array(out_wavs, dtype=np.float64)
+        self.feature_names = ["spectra"] + extra_features
+        self.feature_units = [normed_flux_units]
+        self.has_features = True
+        self.feature_array_flags = {"extra_features": extra_features, "crop_wavelength_range": crop_wavelength_range,
+                                    "normed_flux_units": normed_flux_units, "flux_norm_method": flux_norm_method,
+                                    "flux_norm_parameters": flux_norm_parameters,
+                                    "parameters_to_remove": parameters_to_remove, "parameters_to_add": parameters_to_add,
+                                    "parameter_transformations": parameter_transformations,
+                                    "resample_wavelengths": resample_wavelengths}
+        self.update_parameter_array(parameters_to_remove=parameters_to_remove, parameters_to_add=parameters_to_add,
+                                    parameter_transformations=parameter_transformations)
+        logger.info(f"Spectra feature array created with shape {self.feature_array.shape}.")
+        return self.feature_array, self.feature_names
 
     def create_feature_array_from_raw_photometry(self, normalize_method: Optional[str] = None, extra_features: list = None,
                                                  normed_flux_units: str = "AB", normalization_unit: str = "AB",
@@ -845,6 +947,8 @@ class SBI_Fitter:
         param_dict.update(extras)
         if has_grid:
             param_dict["feature_array_flags"] = getattr(self, "feature_array_flags", {})
+            if getattr(self, "feature_wavelengths", None) is not None:      # spectra features: the M output wavelengths in um
+                param_dict["feature_wavelengths"] = self.feature_wavelengths
             param_dict["feature_array"] = self.feature_array
             param_dict["parameter_array"] = self.fitted_parameter_array
         if "stats" in param_dict:
@@ -921,6 +1025,8 @@ class SBI_Fitter:
                 if "feature_array_flags" in params:
                     self.feature_array_flags = params["feature_array_flags"]
                     self.has_features = True
+                if "feature_wavelengths" in params:
+                    self.feature_wavelengths = params["feature_wavelengths"]
                 if load_arrays and params.get("feature_array") is not None:
                     self.fitted_parameter_array = params["parameter_array"]
                     self.feature_array = params["feature_array"]
