@@ -652,6 +652,50 @@ int sf_knn(const float* base /*[N,C] device*/, int64_t N, int32_t C, const float
 int sf_kde_logsumexp(const float* base_w /*[N,C] device*/, int64_t N, int32_t C, const float* query_w /*[M,C] device*/,
                      int64_t M, double* out /*[M] device*/, void* stream);
 
+/* ---- L-C2ST: the classifiers of the local calibration test (csrc/sf_lc2st.hip; synference_amd/lc2st.py; DESIGN.md section 15;
+ * ref: sbi_runner.py:986-1063, sbi.diagnostics.lc2st.LC2ST with sklearn's MLPClassifier) ---------------------------------------
+ * A handle holds n_cls independent classifiers over ONE row matrix rows[R, n_in]: two ReLU layers of `width` units and a logistic
+ * output, Adam on the mean binary cross-entropy plus alpha / (2 n) |W|^2, minibatches of `batch` rows (the last one shorter) in a
+ * fresh keyed order every epoch, the validation accuracy after every epoch, sklearn's stopping rule when early_stopping is set
+ * (count of epochs with score < best + tol; stop when it exceeds n_iter_no_change; the best-score weights are the result).
+ * Classifier c trains on the rows with vmask[c][r] == 0 against labels[c][r] (0 / 1) and is scored on the rows with vmask 1.
+ * A parameter vector is sklearn's, dense and row major: W1[n_in][width], b1[width], W2[width][width], b2[width], w3[width], b3.
+ * The order of epoch e of classifier c: position j visits training row number F(j), F a four-round Feistel bijection walked
+ * into [0, n_train), its round keys philox4x32_10((c, e, 0, 0), (seed_lo, seed_hi ^ 0x4C433200)) (lc2st.keyed_order).
+ * rows and labels are read by every later call and stay the caller's; vmask and init_weights are consumed by create.
+ * 1 <= n_in <= SF_C2ST_MAX_IN, 1 <= width <= SF_C2ST_MAX_W, 1 <= R < 2^31: anything else is SF_ERR_INVALID with a message that
+ * names the limit; no device: SF_ERR_NO_DEVICE. */
+#define SF_C2ST_MAX_IN 80
+#define SF_C2ST_MAX_W 128
+typedef struct sf_c2st sf_c2st;
+typedef struct {
+  int32_t n_in, width, n_cls, max_iter, n_iter_no_change, early_stopping, batch;
+  int64_t R;
+  uint64_t seed;
+  float lr, beta1, beta2, eps, alpha;
+  double tol;
+  const float* rows;          /* [R, n_in] device */
+  const uint8_t* labels;      /* [n_cls, R] device */
+  const uint8_t* vmask;       /* [n_cls, R] device */
+  const float* init_weights;  /* [n_cls, num_params] device */
+} sf_c2st_desc;
+int sf_c2st_create(const sf_c2st_desc* desc, sf_c2st** out, void* stream);
+void sf_c2st_destroy(sf_c2st* h);
+int64_t sf_c2st_num_params(const sf_c2st* h);
+/* One launch: classifiers first .. first + count - 1, one workgroup each, run up to `epochs` more epochs from the state the
+ * handle keeps (weights, Adam moments and step, best snapshot, counters) and stop early by the rule or at max_iter.  finish != 0
+ * ends the classifiers of the range where they stand (the best snapshot becomes the result).  Blocking; *n_active: classifiers
+ * of the range not yet done.  The result does not depend on how the epochs are split over launches. */
+int sf_c2st_train(sf_c2st* h, int32_t first, int32_t count, int32_t epochs, int32_t finish, int32_t* n_active, void* stream);
+/* rows_o[S, n_in]: stats[i] = mean_s (p - 0.5)^2 (fp64, ascending s) with p = 1 - sigmoid(logit) of classifier first + i;
+ * probs[i, s] = p when probs is not NULL.  Asynchronous on `stream`. */
+int sf_c2st_scores(sf_c2st* h, int32_t first, int32_t count, const float* rows_o /*device*/, int64_t S,
+                   double* stats /*[count] device*/, float* probs /*[count,S] device or NULL*/, void* stream);
+/* To HOST arrays, each may be NULL: weights[n_cls, num_params]; score_log[n_cls, max_iter], the correct validation rows after
+ * each epoch (-1: epoch not run); state[n_cls, 8] = n_iter, Adam steps, no-improvement count, best_iter, done, n_train, n_val,
+ * best count.  Blocking. */
+int sf_c2st_get(sf_c2st* h, float* weights, int32_t* score_log, int32_t* state, void* stream);
+
 /* ---- hand-over to the host ----------------------------------------------------------------
  * host_dst[i] = (double) dev_src[i], i < n: the draws of a catalogue call leave HBM as fp32 in pieces through a ring of pinned
  * staging buffers on a private copy stream and are widened into the caller's float64 array (any host memory, not necessarily

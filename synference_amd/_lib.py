@@ -61,6 +61,15 @@ class sf_spectra_desc(C.Structure):
                [(n, C.c_float) for n in ("unit_scale", "clip_lo", "clip_hi")]
 
 
+class sf_c2st_desc(C.Structure):
+    """The L-C2ST classifier set (field order of include/synference_hip.h); the four arrays are device addresses."""
+    _fields_ = [(n, C.c_int32) for n in ("n_in", "width", "n_cls", "max_iter", "n_iter_no_change", "early_stopping", "batch")] + \
+               [("R", C.c_int64), ("seed", C.c_uint64)] + \
+               [(n, C.c_float) for n in ("lr", "beta1", "beta2", "eps", "alpha")] + \
+               [("tol", C.c_double)] + \
+               [(n, C.c_void_p) for n in ("rows", "labels", "vmask", "init_weights")]
+
+
 # name -> (restype, argtypes); mirrors include/synference_hip.h one for one
 PROTOTYPES = {
     "sf_flow_create": (C.c_int, [C.POINTER(sf_flow_desc), C.POINTER(C.c_void_p)]),
@@ -167,6 +176,12 @@ PROTOTYPES = {
     "sf_knn": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_void_p,
                          C.c_void_p, C.c_void_p]),
     "sf_kde_logsumexp": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "sf_c2st_create": (C.c_int, [C.POINTER(sf_c2st_desc), C.POINTER(C.c_void_p), C.c_void_p]),
+    "sf_c2st_destroy": (None, [C.c_void_p]),
+    "sf_c2st_num_params": (C.c_int64, [C.c_void_p]),
+    "sf_c2st_train": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_void_p]),
+    "sf_c2st_scores": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sf_c2st_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sf_flux_to_abmag": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sf_last_error": (C.c_char_p, []),
     "sf_version": (C.c_char_p, []),

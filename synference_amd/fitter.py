@@ -115,6 +115,7 @@ class SBI_Fitter:
         self._feature_scalar = None      # prior_method="manual" (sbi_runner.py:287-288)
         self._target_scalar = None
         self.posteriors = None
+        self.last_lc2st = None
         self.stats = None
         self._prior = None
         self._train_indices = self._test_indices = None
@@ -1633,3 +1634,58 @@ class SBI_Fitter:
         pit = np.nan_to_num(ranks * n_valid, nan=0.0).sum(1) / (sd.shape[1] * sd.shape[2])
         pit = np.sort(pit)
         return pit / pit[-1]
+
+    def lc2st(self, x_obs, posterior=None, X_test=None, y_test=None, *, num_posterior_samples: int = 10000,
+              num_trials_null: int = 100, alpha: float = 0.05, seed: Optional[int] = None, **lc2st_kwargs) -> dict:
+        """The L-C2ST local calibration test at ``x_obs`` (ref: sbi_runner.py:986-1063; Linhart et al. 2023): is the posterior
+        calibrated at THIS observation?  ``X_test`` / ``y_test`` are the calibration pairs (default: the training split, as in
+        the reference).  One posterior draw per calibration row comes from ``posterior.sample_catalogue(X, 1)``, the
+        ``num_posterior_samples`` draws at ``x_obs`` stay on the device, and 1 + ``num_trials_null`` classifiers train in one
+        launch sequence (``lc2st.LC2ST``).  The reference plots and returns nothing; this returns, and
+        keeps as ``self.last_lc2st``, ``p_value``, ``reject`` (p_value < alpha), ``statistic``, ``null_statistics`` (T,),
+        ``probs_data`` (S,), ``probs_null`` (T, S) and ``n_iter`` (T + 1,).  ``x_obs`` may be (C,), (1, C) or (M, C); with M
+        rows every entry gains a leading M axis.  ``seed`` (None: the posterior's next seed) keys the draws and the
+        classifiers; under a process group every rank runs the whole test on rank 0's seed.  ``lc2st_kwargs`` go to
+        ``LC2ST`` (``hidden_width``, ``max_iter``, ``n_iter_no_change``, ``timeout_seconds``, ...)."""
+        from .lc2st import LC2ST
+        from .posterior import broadcast_seed
+        if X_test is None:
+            if self._X_train is None:
+                raise ValueError("No training data found. Please set the training data first.")
+            X_test = self._X_train
+        if y_test is None:
+            if self._y_train is None:
+                raise ValueError("No training labels found. Please set the training labels first.")
+            y_test = self._y_train
+        if posterior is None:
+            if self.posteriors is None:
+                raise ValueError("No posterior found. Please set the posterior first.")
+            posterior = self.posteriors
+        if seed is None:
+            seed = posterior._next_seed(None)
+        seed = int(broadcast_seed(seed))
+        X = torch.as_tensor(np.asarray(X_test, dtype=np.float32))
+        y = torch.as_tensor(np.asarray(y_test, dtype=np.float32)).reshape(X.shape[0], -1)
+        cal = posterior.sample_catalogue(X, 1, seed)[:, 0, :]                   # (N, D) on the device, no per-row loop
+        ok = torch.isfinite(cal).all(1)
+        if not bool(ok.all()):
+            logger.warning("lc2st: %d calibration rows without a posterior draw are left out", int((~ok).sum()))
+            keep = ok.cpu()
+            X, y, cal = X[keep], y[keep], cal[ok]
+        test = LC2ST(y, X, cal, seed=seed, num_trials_null=num_trials_null, device=cal.device, **lc2st_kwargs)
+        test.train_all()
+        xo = torch.as_tensor(np.asarray(x_obs, dtype=np.float32))
+        xo = xo[None, :] if xo.dim() == 1 else xo
+        n_iter = test.training_state()["n_iter"]
+        rows = []
+        for m in range(xo.shape[0]):
+            draws = posterior.sample_catalogue(xo[m:m + 1], int(num_posterior_samples), (seed + 1) & (2 ** 63 - 1))[0]
+            draws = draws[torch.isfinite(draws).all(1)]
+            probs_data, stat = test.get_scores(draws, xo[m], return_probs=True, trained_clfs=test.trained_clfs)
+            probs_null, null = test.get_statistics_under_null_hypothesis(draws, xo[m], return_probs=True)
+            p = float((stat.mean() < null).mean())
+            rows.append({"p_value": p, "reject": bool(p < alpha), "statistic": float(stat.mean()), "null_statistics": null,
+                         "probs_data": probs_data[0], "probs_null": probs_null, "n_iter": n_iter})
+        out = rows[0] if len(rows) == 1 else {k: np.stack([np.asarray(r[k]) for r in rows]) for k in rows[0]}
+        self.last_lc2st = out
+        return out
