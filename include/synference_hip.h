@@ -122,6 +122,10 @@ int sf_flow_pack_table16(const sf_flow* f, int32_t* src1, int32_t* src2, int64_t
  * bf16 element i (part 0: hi = bf16(w), part 1: lo = bf16(w - hi)), -1 = zero; size 0 when the flow has none */
 int64_t sf_flow_packed16b_size(const sf_flow* f);
 int sf_flow_pack_table16b(const sf_flow* f, int32_t* src, int64_t n);
+/* compact image of the fused fp32 16-row sampler (csrc/sf_layout.h, packed16c): floats per transform (0 when the flow has none)
+ * and, for ONE transform, src[i] = offset of float i inside that transform of the 16-row image, -1 = padding */
+int64_t sf_flow_packed16c_size(const sf_flow* f);
+int sf_flow_pack_table16c(const sf_flow* f, int32_t* src, int64_t n);
 /* cooperative 16-row training image (MAF, num_blocks 2, D <= 8; csrc/sf_layout.h SfTrcDev): sizes (0 when the flow has
  * none), gather table, logical parameter -> gradient-partial index, and the descriptor as int32 words in declaration order */
 int64_t sf_flow_trainc_size(const sf_flow* f);

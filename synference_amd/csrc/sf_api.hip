@@ -54,6 +54,10 @@ static int ensure_device(sf_flow* f) {
     SF_TRY_SET(hipMemcpy(d.d_s16a, f->L.src16a.data(), n16 * sizeof(int32_t), hipMemcpyHostToDevice));
     SF_TRY_SET(hipMemcpy(d.d_s16b, f->L.src16b.data(), n16 * sizeof(int32_t), hipMemcpyHostToDevice));
   }
+  if (f->L.dev.m16_ok && f->L.n_packed16 > 0 && sf_maf16_compact_fix(f->L.dev) == 1) {   // (only where a kernel reads it)
+    SF_TRY_SET(d.d_packed16c.alloc((size_t)f->L.dev.t16c_stride * f->L.dev.T));
+    SF_TRY_SET(d.d_s16c.upload(f->L.src16c));
+  }
   if ((f->L.dev.m16_ok || f->L.nsfS.ok) && f->L.n_packed16B > 0) {
     const size_t nB = (size_t)f->L.n_packed16B;
     SF_TRY_SET(d.d_packed16B.alloc(nB));
@@ -171,6 +175,15 @@ int sf_flow_pack_table16b(const sf_flow* f, int32_t* src, int64_t n) {
   return SF_OK;
 }
 
+int64_t sf_flow_packed16c_size(const sf_flow* f) { return (f && f->L.dev.m16_ok) ? (int64_t)f->L.src16c.size() : 0; }
+
+int sf_flow_pack_table16c(const sf_flow* f, int32_t* src, int64_t n) {
+  if (!f || !src) return sf_fail(SF_ERR_INVALID, "null argument");
+  if (!f->L.dev.m16_ok || n == 0 || n != (int64_t)f->L.src16c.size()) return sf_fail(SF_ERR_INVALID, "no compact fused image or size mismatch");
+  std::memcpy(src, f->L.src16c.data(), (size_t)n * sizeof(int32_t));
+  return SF_OK;
+}
+
 int64_t sf_flow_trainc_size(const sf_flow* f) { return (f && (f->L.trc.ok || f->L.nsc.ok)) ? f->L.n_imgC : 0; }
 int64_t sf_flow_trainc_grad_size(const sf_flow* f) { return (f && (f->L.trc.ok || f->L.nsc.ok)) ? f->L.n_gradC : 0; }
 int64_t sf_flow_cst_size(const sf_flow* f) { return f ? (int64_t)f->L.cst.size() : 0; }
@@ -190,6 +203,7 @@ int sf_flow_trainc_table(const sf_flow* f, int32_t* src1, int32_t* src2, int64_t
   return SF_OK;
 }
 
+static SfDev sampler_dev(const sf_flow* f, const float* x);
 int sf_flow_describe(const sf_flow* f, char* buf, size_t buflen) {
   if (!f || !buf) return sf_fail(SF_ERR_INVALID, "null argument");
   const SfDev& v = f->L.dev;
@@ -241,6 +255,11 @@ int sf_flow_describe(const sf_flow* f, char* buf, size_t buflen) {
   add("o16_wk1", v.o16_wk[1]); add("o16_bk0", v.o16_bk[0]); add("o16_bk1", v.o16_bk[1]); add("o16_hv", v.o16_hv);
   add("o16_hvb", v.o16_hvb); add("o16_wh", v.o16_wh); add("o16_bh", v.o16_bh); add("o16_wp", v.o16_wp); add("t16_a_tab", v.t16_a_tab);
   add("t16_a", v.t16_a); add("t16B_stride", v.t16B_stride); add("nP16", v.nP16); add("o16B_wk0", v.o16B_wk[0]); add("o16B_wk1", v.o16B_wk[1]);
+  add("t16c_stride", v.t16c_stride); add("o16c_bk1", v.o16c_bk1); add("o16c_hvb", v.o16c_hvb); add("o16c_bh", v.o16c_bh);
+  add("o16c_wh", v.o16c_wh); add("o16c_wp", v.o16c_wp); add("o16c_blk", v.o16c_blk); add("c16_fix", sf_maf16_compact_fix(v));
+  // the one run-time entry: would a sampling launch over the rows of the prepared context table take the fused kernels NOW
+  // (table attached, W' and the compact image fresh)?  0 without a prepared table.
+  add("sampler_fused", (f->dev_ready && f->ctab_x) ? (sf_maf16_plan(sampler_dev(f, f->ctab_x)).fused ? 1 : 0) : 0);
   add("m16_ok", v.m16_ok); add("m16_span", v.m16_span); add("nT16", v.nT16); add("nC16", v.nC16); add("t16_stride", v.t16_stride);
   s += "\"g16_tile\": [";
   for (int i = 0; i < SF_DMAX; ++i) s += std::to_string(v.g16_tile[i]) + (i + 1 < SF_DMAX ? ", " : "], ");
@@ -462,6 +481,7 @@ int sf_flow_prepare_context(sf_flow* f, const float* x, int64_t M, void* stream)
   m.ctab_R = R; m.ctab_NV = NV;
   if (f->wp_stale && m.kind == SF_MAF && m.m16_ok && m.packed16 && m.o16_wp >= 0) {   // the fused first layer follows the parameters
     SF_TRY_SET(sf_launch_maf_fuse16(m, (hipStream_t)stream));
+    if (f->d_packed16c) SF_TRY_SET(sf_launch_maf_compact16(m, f->d_s16c, f->d_packed16c, (hipStream_t)stream));   // ... and so does the compact image
     f->wp_stale = false;
   }
   SF_TRY_SET(sf_launch_ctab(m, x, (long)M, f->d_ctab, (hipStream_t)stream));

@@ -87,7 +87,11 @@ int sf_sampler_fp32_for(int kind);  // the mode a flow of this kind samples in (
 void sf_ctab_shape(const SfDev& m, int& R, int& NV);
 hipError_t sf_launch_ctab(const SfDev& m, const float* x, long M, float* tab, hipStream_t st);
 hipError_t sf_launch_maf_ctab16(const SfDev& m, const float* x, long M, float* tab, hipStream_t st);
-hipError_t sf_launch_maf_fuse16(const SfDev& m, hipStream_t st);
+hipError_t sf_launch_maf_fuse16(const SfDev& m, hipStream_t st);   // W' = (W1 o M)(W0 o M0) into o16_wp of every transform
+// the compact fused image of every transform from the 16-row image (after sf_launch_maf_fuse16: it carries W'); tab: SfLayout::src16c
+hipError_t sf_launch_maf_compact16(const SfDev& m, const int32_t* tab, float* out, hipStream_t st);
+// the compact image's offsets against the compile-time ones of the unrolled fused kernels: 1 equal, 0 not, -1 no such kernel for the shape
+int sf_maf16_compact_fix(const SfDev& m);
 // Which 16-row MAF kernels (sf_maf16.hip) a view of a flow runs on, in the process's sampler arithmetic: the one place that decides.
 struct SfMaf16Plan {
   bool ok16 = false;       // the flow has the 16-row path at all (fp32 image; sf_maf16_enabled adds the launch's own condition)
@@ -97,10 +101,11 @@ struct SfMaf16Plan {
   bool head_mfma = false;  // head rows on the matrix pipe (aligned placement with the head tile in the image: D <= 8)
   int dd = 0;              // D (3..5) when the unrolled kernels apply (this view has the context table, degree p alone in tile p - 2,
                            // the packer's offsets are the hard-wired ones), else 0: the kernels that dispatch per pass
-  bool fused = false;      // ... with the fused first layer (fp32, the table carries the c0' rows)
+  bool fused = false;      // ... with the fused first layer (fp32, the table carries the c0' rows, the compact image is fresh and
+                           // the packer's offsets in it are the hard-wired ones)
 };
 SfMaf16Plan sf_maf16_plan(const SfDev& m);
-hipError_t sf_launch_maf_find16_zin(const SfDev& m, const SfSampleArgsHost& a, hipStream_t st);   // W' = (W1 o M)(W0 o M0) into o16_wp of every transform
+hipError_t sf_launch_maf_find16_zin(const SfDev& m, const SfSampleArgsHost& a, hipStream_t st);
 hipError_t sf_launch_pack(const float* flat, const int32_t* s1, const int32_t* s2, float* packed, long n,
                           hipStream_t st);
 hipError_t sf_launch_pack_bf16(const float* flat, const int32_t* src, unsigned short* out, long n, hipStream_t st);
@@ -183,6 +188,8 @@ struct SfFlowDev {   // ensure_device (sf_api.hip)
   SfBuf<int32_t> d_s1, d_s2;
   SfBuf<float> d_packed16;      // 16-row image of the incremental MAF inverse (sf_maf16.hip)
   SfBuf<int32_t> d_s16a, d_s16b;
+  SfBuf<float> d_packed16c;     // compact fused image (sf_layout.h: packed16c), rebuilt with W' (wp_stale)
+  SfBuf<int32_t> d_s16c;        // its gather table, one transform
   SfBuf<unsigned short> d_packed16B;  // split-bf16 hidden blocks of the 16-row sampler (sf_layout.h)
   SfBuf<int32_t> d_s16B;
   SfBuf<unsigned short> d_packedB;    // bf16 hidden operand image (hidden_bf16)
@@ -246,7 +253,8 @@ struct sf_flow : SfFlowDev, SfFlowTrain, SfFlowTrainC, SfFlowGt, SfFlowRej {
   double* d_losspart = nullptr;      // (a view of d_losspart_mem, not an owner)
   SfBuf<double> d_losspart_mem;
   bool losspart_used = false;
-  bool wp_stale = true;              // the fused first-layer blocks (o16_wp) lag behind packed16: recomputed before the next context table
+  bool wp_stale = true;              // the fused first-layer blocks (o16_wp) and the compact image (d_packed16c) lag behind packed16:
+                                     // recomputed before the next context table
   bool sample_out_f64 = false;       // sf_flow_set_sample_output_f64: `out` of sf_flow_sample / _slots is a double array
   long long sample_row_offset = 0;   // sf_flow_set_sample_row_offset: first row of the next sampling calls in its catalogue
   double sample_time_limit_s = 0.0;  // > 0: sf_flow_sample* stop opening new attempt windows after this much wall time
@@ -265,6 +273,7 @@ struct sf_flow : SfFlowDev, SfFlowTrain, SfFlowTrainC, SfFlowGt, SfFlowRej {
     v.packedB = d_packedB;
     v.packed16 = packed16_stale ? nullptr : d_packed16.get();
     v.packed16B = reinterpret_cast<const uint32_t*>(d_packed16B.get());
+    v.packed16c = (packed16_stale || wp_stale) ? nullptr : d_packed16c.get();
     v.ctab = nullptr;  // set per launch by the sampler entry points
     return v;
   }

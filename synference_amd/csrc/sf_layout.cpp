@@ -1066,6 +1066,32 @@ bool sf_build_layout(const sf_flow_desc& d, SfLayout& L) {
   L.n_packed16B = (int64_t)L.src16B.size();
   if (!v.m16_ok && !L.nsfS.ok) { L.src16B.clear(); L.n_packed16B = 0; }
   if (v.m16_ok && (size_t)v.t16_stride * sizeof(float) > 152 * 1024) v.m16_ok = 0;
+  // ---- compact fused image (sf_layout.h, packed16c): where each of its floats sits in a transform of the 16-row image
+  // (only for the shapes of the unrolled fused kernels, sf_maf16.hip: D = 3..5 with one hidden tile per degree)
+  if (d.kind == SF_MAF && v.m16_ok && !v.m16_span && v.o16_wp >= 0 && v.o16_wh >= 0 && NB <= 2 && D >= 3 && D <= 5 && v.nT16 == D - 1) {
+    const int NT = v.nT16;
+    auto run = [&](int from, int n) { for (int i = 0; i < n; ++i) L.src16c.push_back(from + i); };
+    auto align = [&](size_t q) { while (L.src16c.size() % q) L.src16c.push_back(-1); };
+    auto here = [&]() { return (int)L.src16c.size(); };
+    v.o16c_bk1 = here();
+    if (NB == 2) run(v.o16_bk[1], NT * 16);
+    v.o16c_hvb = here();
+    run(v.o16_hvb, 2 * D);
+    align(4);
+    v.o16c_bh = here();
+    run(v.o16_bh, 16);
+    v.o16c_wh = here();
+    run(v.o16_wh, NT * 256);
+    v.o16c_wp = here();
+    const int KN = std::min(NT, D - 1);   // (k_maf_fuse16: the dimension of degree D feeds nothing)
+    run(v.o16_wp, (KN * NT - KN * (KN - 1) / 2) * 16);
+    v.o16c_blk = here();
+    if (NB == 2)
+      for (int ot = 0; ot < NT; ++ot)
+        for (int it = 0; it <= ot; ++it) run(v.o16_wk[1] + (ot * NT + it) * 256, 256);
+    align(256);
+    v.t16c_stride = here();
+  }
   L.n_packedB = (int64_t)L.srcB.size();
   // ---- LDS staging plan (budget: 152 KiB of the 160 KiB LDS; the rest holds the persistent sampler's control block) ---------------------------------
   {

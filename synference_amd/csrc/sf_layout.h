@@ -83,6 +83,16 @@ struct SfDev {
   // dimensions; filled by k_maf_fuse16 from the packed image (not by the gather table), read by the fp32 sampler kernels
   // together with the table rows c0' = b1 + (W1 o M) c0
   int o16_wp;
+  // compact fused image (the shapes of the unrolled fused kernels only -- aligned placement, NB <= 2, D = 3..5 with one hidden tile
+  // per degree -- else t16c_stride = 0): per transform ONE contiguous block of exactly
+  // what the fused fp32 passes read (sf_pass16g / sf_transform16g) -- the second block's bias rows, the head biases in both forms,
+  // the head tile, W', and the second block's fragments on and below the diagonal (entry ot (ot + 1) / 2 + it) -- so that a
+  // transform is staged with 1 KiB wave-instructions and no unread byte.  Gathered on the device from the 16-row image whenever W'
+  // is recomputed (k_maf_compact16 behind k_maf_fuse16); SfLayout::src16c says from where.  Sub-blocks 16-byte aligned, the
+  // whole a multiple of 256 floats.
+  const float* packed16c;
+  int t16c_stride;
+  int o16c_bk1, o16c_hvb, o16c_bh, o16c_wh, o16c_wp, o16c_blk;
   // split-bf16 hidden blocks of the 16-row sampler: 32-bit words (2 bf16 each), [ot][pair][hi|lo][64 lanes][4 words]
   const uint32_t* packed16B;
   int t16B_stride, nP16, o16B_wk[2];  // words per transform, in-tile pairs, block offsets in words
@@ -201,6 +211,8 @@ struct SfLayout {
                                         // (part << 30), part 0 = hi = bf16(w), 1 = lo = bf16(w - hi); -1 = zero
   int64_t n_packed16B = 0;
   int64_t n_packed16 = 0;
+  std::vector<int32_t> src16c;          // compact fused image, ONE transform (dev.t16c_stride entries, the same for every transform):
+                                        // offset of the float inside the transform's 16-row image, -1 = padding (zero)
   int64_t n_packedB = 0;
   std::vector<float> cst;             // constants image
   std::string error;

@@ -195,6 +195,41 @@ struct SfFix16 {
   }
 };
 
+// The same for the compact fused image (sf_layout.h, packed16c): what the PREC 2 kernels stage and read instead of part A and
+// the second block.  apply() points the offsets the fused passes use (sf_pass16g / sf_transform16g) into it; the second
+// block's fragments start at o_blk.
+template <int NB, int DD>
+struct SfFixC16 {
+  static constexpr int NT = DD - 1, ENT = NT * (NT + 1) / 2;   // W' entries = fragments of a block on and below the diagonal
+  static constexpr int o_bk1 = 0, o_hvb = NB == 2 ? NT * 16 : 0, o_bh = o_hvb + (2 * DD + 3) / 4 * 4, o_wh = o_bh + 16;
+  static constexpr int o_wp = o_wh + NT * 256, o_blk = o_wp + ENT * 16;
+  static constexpr int size = (o_blk + (NB == 2 ? ENT * 256 : 0) + 255) / 256 * 256;
+  static constexpr int groups = size / 256;   // 1 KiB wave-instructions per transform
+  static bool matches(const SfDev& m) {
+    return m.nT16 == NT && m.o16c_bk1 == o_bk1 && m.o16c_hvb == o_hvb && m.o16c_bh == o_bh && m.o16c_wh == o_wh && m.o16c_wp == o_wp &&
+           m.o16c_blk == o_blk && m.t16c_stride == size;
+  }
+  static __device__ __forceinline__ void apply(SfDev& m) {
+    m.o16_bk[1] = o_bk1; m.o16_hvb = o_hvb; m.o16_bh = o_bh; m.o16_wh = o_wh; m.o16_wp = o_wp;
+  }
+};
+// LDS floats in front of a sampler kernel's control words / epilogue constants: the staged operands (+ the draw-state scratch)
+template <int PREC>
+static __host__ __device__ __forceinline__ int sf_lds_floats16(const SfDev& m, bool cp) {
+  if constexpr (PREC == 2) return m.t16c_stride + 4 * SF_G16_SCR;   // (then the draw-state scratch of the four waves)
+  else return (m.ctab ? m.t16_a_tab : m.t16_a) + SfHid16<PREC>::lds_floats(m, cp);
+}
+// Staging of one transform's compact image (G KiB; all four waves, the caller brackets it with barriers): direct global -> LDS
+// copies, 1 KiB wave-instructions dealt to the four waves.
+template <int G>
+__device__ __forceinline__ void sf_stage16c(const float* src, int wave) {
+  const float4* __restrict__ g = reinterpret_cast<const float4*>(src) + (threadIdx.x & 63);
+  float4* __restrict__ l = reinterpret_cast<float4*>(sf_lds16);
+  for (int gi = __builtin_amdgcn_readfirstlane(wave); gi < G; gi += 4)
+    __builtin_amdgcn_global_load_lds((const void*)(g + gi * 64), (void __attribute__((address_space(3)))*)(l + gi * 64), 16, 0, 0);
+  __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0): the copies have landed
+}
+
 // DD > 0 (HM, aligned placement with ONE degree group per tile, D == DD <= 5): the passes of a transform are unrolled
 // with the tile of each known at compile time (pass p works on tile p - 2) -- no dispatch, and the per-tile state is
 // updated in place instead of being copied into the registers every arm of the switch has to agree on.
@@ -209,13 +244,14 @@ struct SfFix16 {
 template <int NB, bool SPAN, bool HM, int DD = 0, int PREC = 0>
 __global__ __launch_bounds__(256, (SPAN ? 3 : (PREC == 2 ? SF_SAMP16_WG_FUSED : 4))) void k_maf_samp16(SfSamp16Args args_in) {
   static_assert(DD == 0 || (HM && !SPAN && DD >= 2 && DD <= 5), "unrolled passes: head tile, aligned placement, D <= 5");
+  static_assert(PREC != 2 || DD >= 3, "fused first layer: unrolled kernels only (m_fix and the compact image's offsets)");
   using HID = SfHid16<PREC>;
   constexpr int TPW = SF_SAMP16_TPW;
   constexpr int IPW = 64 * TPW;
   const int wave = threadIdx.x >> 6;
+  using FC = SfFixC16<NB, (PREC == 2 ? DD : 2)>;   // (PREC 2 only: the compact image)
   // with the per-galaxy context table the context block Wc is never read: only the prefix of part A before it is staged
-  unsigned int* ctrl = reinterpret_cast<unsigned int*>(
-      sf_lds16 + (args_in.m.ctab ? args_in.m.t16_a_tab : args_in.m.t16_a) + HID::lds_floats(args_in.m, !SPAN));
+  unsigned int* ctrl = reinterpret_cast<unsigned int*>(sf_lds16 + sf_lds_floats16<PREC>(args_in.m, !SPAN));
   unsigned int pf;
   sf_q_begin<IPW>(args_in.a, ctrl, pf);
   // per-slot constants of the epilogue, once per workgroup, behind the queue's control words
@@ -238,6 +274,7 @@ __global__ __launch_bounds__(256, (SPAN ? 3 : (PREC == 2 ? SF_SAMP16_WG_FUSED : 
     const SfDev& m_arg = ap->m;
     SfDev m_fix;  // (DD > 0: the descriptor with the image offsets replaced by their compile-time values)
     if constexpr (DD > 0) { m_fix = m_arg; SfFix16<NB, DD>::apply(m_fix); }
+    if constexpr (PREC == 2) FC::apply(m_fix);   // (the fused passes read the compact image)
     const SfDev& m = DD > 0 ? m_fix : m_arg;
     const SfSampleArgsHost& a = ap->a;
     const int lane = (threadIdx.x & 63) + sf_opaque_zero();  // lane-derived addresses are recomputed per iteration
@@ -307,14 +344,15 @@ __global__ __launch_bounds__(256, (SPAN ? 3 : (PREC == 2 ? SF_SAMP16_WG_FUSED : 
       { const unsigned long long n = __builtin_amdgcn_s_memrealtime(); qs_ph[qs_o + (t == m.T - 1 ? 1 : 3)] += n - qs_t_mark; qs_t_mark = n; }
 #endif
       __syncthreads();
-      // part A of the fp32 image and the hidden blocks, one behind the other in LDS
-      sf_stage16<PREC, !SPAN>(m, t, S.tab ? m.t16_a_tab : m.t16_a, wave);
+      // PREC 2: the compact image; else part A of the fp32 image and the hidden blocks, one behind the other in LDS
+      if constexpr (PREC == 2) sf_stage16c<FC::groups>(m.packed16c + (size_t)t * FC::size, wave);
+      else sf_stage16<PREC, !SPAN>(m, t, S.tab ? m.t16_a_tab : m.t16_a, wave);
       __syncthreads();
 #ifdef SF_Q_STATS
       { const unsigned long long n = __builtin_amdgcn_s_memrealtime(); qs_ph[qs_o + 2] += n - qs_t_mark; qs_t_mark = n; }
 #endif
       const float* tp = sf_lds16;
-      const void* tpB = sf_lds16 + (S.tab ? m.t16_a_tab : m.t16_a);
+      const void* tpB = sf_lds16 + (PREC == 2 ? FC::o_blk : (S.tab ? m.t16_a_tab : m.t16_a));   // the hidden blocks
 #pragma unroll 1
       for (int j = 0; j < TPW; ++j) {
         // a wave whose tile holds no item (tail iterations with few entries) skips the flow: its issue slots go to the
@@ -328,7 +366,7 @@ __global__ __launch_bounds__(256, (SPAN ? 3 : (PREC == 2 ? SF_SAMP16_WG_FUSED : 
           }
           if (HM) S.hdone = sf_ld4(tp + m.o16_bh + g4 * 4);
           if constexpr (PREC == 2) {
-            float* scr = (float*)tpB + HID::blk_floats(m) + wave * SF_G16_SCR + s * SF_G16_ROW;
+            float* scr = sf_lds16 + FC::size + wave * SF_G16_SCR + s * SF_G16_ROW;
             sf_transform16g<NB, DD>(m, tp, static_cast<const float*>(tpB), S, dsl, u_cur, scr, lane, g4);
           } else {
             S.xr = a.x + gal_cur * m.C;
@@ -490,11 +528,13 @@ __global__ __launch_bounds__(256, (SPAN ? 3 : (PREC == 2 ? SF_SAMP16_WG_FUSED : 
 template <int NB, int DD, int PREC = 0>
 __global__ __launch_bounds__(256, 4) void k_maf_find16s(SfDev m, SfSampleArgsHost a) {
   using HID = SfHid16<PREC>;
+  using FC = SfFixC16<NB, DD>;   // (PREC 2 only: the compact image)
   SfFix16<NB, DD>::apply(m);  // (the launcher only picks this kernel when the packer's offsets are these)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int s = lane & 15, g4 = lane >> 4;
-  float* ecb = sf_lds16 + m.t16_a_tab + HID::lds_floats(m, true);
+  float* ecb = sf_lds16 + sf_lds_floats16<PREC>(m, true);
   sf_ecb16_build<false>(ecb, m, a);  // (80 words: the launcher adds no room for the column -> slot table)
+  if constexpr (PREC == 2) FC::apply(m);   // (the fused passes read the compact image)
   const int NT = m.nT16;
   f32x4 u_cur, u_oth;
   long gal_cur = 0, gal_oth = 0;
@@ -516,10 +556,11 @@ __global__ __launch_bounds__(256, 4) void k_maf_find16s(SfDev m, SfSampleArgsHos
     if constexpr (PREC == 2) sf_pre16g_load<DD - 1>(S, g4);
     else sf_c0_prefetch(S, 0, g4);
     __syncthreads();
-    sf_stage16<PREC, true>(m, t, m.t16_a_tab, wave);
+    if constexpr (PREC == 2) sf_stage16c<FC::groups>(m.packed16c + (size_t)t * FC::size, wave);
+    else sf_stage16<PREC, true>(m, t, m.t16_a_tab, wave);
     __syncthreads();
     const float* tp = sf_lds16;
-    const void* tpB = sf_lds16 + m.t16_a_tab;
+    const void* tpB = sf_lds16 + (PREC == 2 ? FC::o_blk : m.t16_a_tab);
 #pragma unroll 1
     for (int j = 0; j < 2; ++j) {
       if (((long)blockIdx.x * 8 + j * 4 + wave) * 16 < a.n_items) {  // (wave-uniform: the tile holds an item)
@@ -530,7 +571,7 @@ __global__ __launch_bounds__(256, 4) void k_maf_find16s(SfDev m, SfSampleArgsHos
         }
         S.hdone = sf_ld4(tp + m.o16_bh + g4 * 4);
         if constexpr (PREC == 2) {
-          float* scr = (float*)tpB + HID::blk_floats(m) + wave * SF_G16_SCR + s * SF_G16_ROW;
+          float* scr = sf_lds16 + FC::size + wave * SF_G16_SCR + s * SF_G16_ROW;
           sf_transform16g<NB, DD>(m, tp, static_cast<const float*>(tpB), S, dsl, u_cur, scr, lane, g4);
         } else {
           sf_transform16s<HID, NB, DD>(m, tp, tpB, S, NT, dsl, u_cur, lane, g4);
@@ -622,6 +663,12 @@ static hipError_t sf_visit_unrolled16(int NB, int dd, F&& f) {
   return hipErrorInvalidValue;
 }
 
+// the compact image's offsets against the compile-time ones of the fused kernels: 1 equal, 0 not, -1 no such kernel for the shape
+int sf_maf16_compact_fix(const SfDev& m) {
+  if (m.t16c_stride <= 0 || m.D < 3 || m.D > 5 || m.nT16 != m.D - 1 || m.NB < 1 || m.NB > 2) return -1;
+  if (m.NB == 1) return m.D == 3 ? SfFixC16<1, 3>::matches(m) : (m.D == 4 ? SfFixC16<1, 4>::matches(m) : SfFixC16<1, 5>::matches(m));
+  return m.D == 3 ? SfFixC16<2, 3>::matches(m) : (m.D == 4 ? SfFixC16<2, 4>::matches(m) : SfFixC16<2, 5>::matches(m));
+}
 // the unrolled-pass kernels apply when degree p - 1 sits alone in tile p - 2 (otherwise: the dispatching kernel)
 static int sf_maf16_seq_d(const SfDev& m) {
   if (!m.ctab || m.m16_span || m.D < 3 || m.D > 5 || m.nT16 != m.D - 1) return 0;
@@ -642,14 +689,14 @@ SfMaf16Plan sf_maf16_plan(const SfDev& m) {
   pl.span = m.m16_span != 0;
   pl.head_mfma = !m.m16_span && m.o16_wh >= 0;
   pl.dd = pl.head_mfma ? sf_maf16_seq_d(m) : 0;
-  pl.fused = pl.dd > 0 && pl.fp32 && m.o16_wp >= 0 && m.ctab_R == 2 * m.nT16 * 16;
+  pl.fused = pl.dd > 0 && pl.fp32 && m.o16_wp >= 0 && m.ctab_R == 2 * m.nT16 * 16 && m.packed16c != nullptr && sf_maf16_compact_fix(m) == 1;
   return pl;
 }
 
 template <int NB, int DD, int PREC>
 static hipError_t sf_launch_find16s(const SfDev& m, const SfSampleArgsHost& a, hipStream_t st) {
   static SfAttrCache attr;
-  const size_t sh = ((size_t)m.t16_a_tab + (size_t)SfHid16<PREC>::lds_floats(m, true)) * sizeof(float) + 80 * sizeof(float);
+  const size_t sh = (size_t)sf_lds_floats16<PREC>(m, true) * sizeof(float) + 80 * sizeof(float);
   if (hipError_t e = sf_lds_optin16(k_maf_find16s<NB, DD, PREC>, attr); e != hipSuccess) return e;
   hipLaunchKernelGGL((k_maf_find16s<NB, DD, PREC>), dim3((unsigned)((a.n_items + 127) / 128)), dim3(256), sh, st, m, a);
   return hipGetLastError();
@@ -806,6 +853,20 @@ hipError_t sf_launch_maf_fuse16(const SfDev& m, hipStream_t st) {
   hipLaunchKernelGGL(k_maf_fuse16, dim3((unsigned)m.T), dim3(256), 0, st, m);
   return hipGetLastError();
 }
+// The compact fused image (sf_layout.h, packed16c) of every transform from the 16-row image, by the packer's table: runs behind
+// k_maf_fuse16 on the same stream, so W' is in it
+__global__ __launch_bounds__(256) void k_maf_compact16(SfDev m, const int32_t* __restrict__ tab, float* __restrict__ out) {
+  const float* tp = m.packed16 + (size_t)blockIdx.x * m.t16_stride;
+  float* op = out + (size_t)blockIdx.x * m.t16c_stride;
+  for (int i = threadIdx.x; i < m.t16c_stride; i += blockDim.x) {
+    const int s = tab[i];
+    op[i] = s >= 0 ? tp[s] : 0.f;
+  }
+}
+hipError_t sf_launch_maf_compact16(const SfDev& m, const int32_t* tab, float* out, hipStream_t st) {
+  hipLaunchKernelGGL(k_maf_compact16, dim3((unsigned)m.T), dim3(256), 0, st, m, tab, out);
+  return hipGetLastError();
+}
 hipError_t sf_launch_maf_ctab16(const SfDev& m, const float* x, long M, float* tab, hipStream_t st) {
   hipLaunchKernelGGL(k_maf_ctab16, dim3((unsigned)((M + 63) / 64), (unsigned)m.T), dim3(256), 0, st, m, x, M, tab);
   return hipGetLastError();
@@ -834,8 +895,7 @@ template <int NB, bool SPAN, bool HM, int DD, int PREC>
 static hipError_t sf_launch16q_p(const SfDev& m, const SfSampleArgsHost& a, hipStream_t st) {
   static SfAttrCache attr;
   static SfResidentCache rcache;
-  const size_t sh = ((size_t)(m.ctab ? m.t16_a_tab : m.t16_a) + (size_t)SfHid16<PREC>::lds_floats(m, !SPAN)) * sizeof(float) +
-                    (SF_Q_WORDS(64 * SF_SAMP16_TPW) + 96) * sizeof(unsigned int);
+  const size_t sh = (size_t)sf_lds_floats16<PREC>(m, !SPAN) * sizeof(float) + (SF_Q_WORDS(64 * SF_SAMP16_TPW) + 96) * sizeof(unsigned int);
   if (sh > 160 * 1024) return hipErrorInvalidValue;
   if (hipError_t e = sf_lds_optin16(k_maf_samp16<NB, SPAN, HM, DD, PREC>, attr); e != hipSuccess) return e;
   int resident = 0, cur_dev = 0;

@@ -767,10 +767,7 @@ __device__ __forceinline__ void sf_transform16g(const SfDev& m, const float* tp,
 }
 template <> struct SfHid16<2> {
   using State = SfPass16G;
-  // LDS floats behind part A: the SECOND block's fragments on and below the diagonal (the first block lives in W'), then the
-  // draw-state scratch of the four waves
-  static __host__ __device__ int blk_floats(const SfDev& m) { return m.NB >= 2 ? m.nT16 * (m.nT16 + 1) / 2 * 256 : 0; }
-  static __host__ __device__ int lds_floats(const SfDev& m, bool /*cp*/) { return blk_floats(m) + 4 * SF_G16_SCR; }
+  // (no part A, no blocks behind it: these kernels stage the compact fused image, sf_stage16c in sf_maf16.hip)
 };
 
 // Direct global -> LDS copy (global_load_lds_dwordx4: no staging registers, no ds_write) of one 4 KiB group by one wave: the LDS
@@ -806,10 +803,9 @@ __device__ __forceinline__ void sf_stage16(const SfDev& m, int t, int a_floats, 
     }
     const int NT = m.nT16, nb = m.NB < 2 ? m.NB : 2;
     const int per = CP ? NT * (NT + 1) / 2 : NT * NT;
-    constexpr int K0 = PREC == 2 ? 1 : 0;   // (fused first layer: the first block is not staged)
     float4* __restrict__ dF = d4 + (a_floats >> 2);
-    for (int e = __builtin_amdgcn_readfirstlane(wave); e < (nb - K0) * per; e += 4) {
-      const int k = K0 + (e >= per ? 1 : 0), ee = e - (k - K0) * per;
+    for (int e = __builtin_amdgcn_readfirstlane(wave); e < nb * per; e += 4) {
+      const int k = e >= per ? 1 : 0, ee = e - k * per;
       int src_blk = ee;
       if (CP) {  // entry ot (ot + 1) / 2 + it  ->  block ot * NT + it   (NT <= 4)
         const int ot = ee >= 6 ? 3 : (ee >= 3 ? 2 : (ee >= 1 ? 1 : 0));

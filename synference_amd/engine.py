@@ -107,6 +107,15 @@ class HipFlow:
             _lib.check(self.lib.sf_flow_pack_table16b(self.handle, s.ctypes.data_as(_lib.c_i32p), n))
         return s
 
+    def pack_table16c(self) -> np.ndarray:
+        """Gather table of the compact fused image, one transform (empty when the flow has none): entry i = offset of the float
+        inside that transform of the 16-row image; -1 = padding."""
+        n = int(self.lib.sf_flow_packed16c_size(self.handle))
+        s = np.empty(n, np.int32)
+        if n:
+            _lib.check(self.lib.sf_flow_pack_table16c(self.handle, s.ctypes.data_as(_lib.c_i32p), n))
+        return s
+
     TRC_FIELDS = ("ok NT NI t_stride g_stride o_win o_b0 o_w1 o_b1 o_w2 o_b2 o_wf o_bf o_wfT o_w2T o_w1T o_winT "
                   "g_win g_b0 g_w1 g_b1 g_w2 g_b2 g_wf g_bf kend0 kend1 kend2 kend3 kbeg0 kbeg1 kbeg2 kbeg3 c_insrc c_jobs "
                   "n_jobs").split()
@@ -141,6 +150,13 @@ class HipFlow:
             _lib.check(self.lib.sf_flow_describe(self.handle, buf, len(buf)))
             d = self._describe = json.loads(buf.value.decode())
         return dict(d)
+
+    def sampler_fused(self) -> bool:
+        """Whether a sampling launch over the rows of the context table prepared last (prepare_context) would run the fused
+        fp32 16-row kernels on the compact image right now; False without a prepared table.  (Run-time state: not cached.)"""
+        buf = C.create_string_buffer(1 << 16)
+        _lib.check(self.lib.sf_flow_describe(self.handle, buf, len(buf)))
+        return bool(json.loads(buf.value.decode()).get("sampler_fused", 0))
 
     # ---- device calls -----------------------------------------------------------------------
     def _dev(self):
