@@ -410,7 +410,11 @@ int sf_mlp_backward(sf_mlp* m, const float* flat, const float* x, const float* d
 /* ---- posterior summaries on the device ---------------------------------------------------
  * out[g,d,k] = quantile q[k] (numpy 'linear' rule) of samples[g,:,d], NaN draws ignored (all NaN -> NaN).
  * Replaces np.quantile(samples_i, quantiles, axis=1) of fit_catalogue (ref: sbi_runner.py:3270-3282)
- * without moving the (N,S,D) draws to the host.  q: DEVICE [Q]; 1 <= S <= 8192. */
+ * without moving the (N,S,D) draws to the host.  q: DEVICE [Q]; 1 <= S <= 8192.
+ * n counts every non-NaN draw, +-inf included (ordered values); the position (n - 1) q and the interpolation are formed in
+ * fp64 from the float32 q as given; at an integer position the result is that order statistic bit for bit (also beside an
+ * infinite draw).  q is not validated here: for q outside [0, 1] the lower rank is clamped to [0, n - 1] and the end segment
+ * extrapolated (defined, not meaningful), a NaN q gives NaN; the Python wrappers refuse both.  sf_quantiles_large: the same. */
 int sf_quantiles(const float* samples /*[N,S,D]*/, int64_t N, int64_t S, int32_t D,
                  const float* q /*[Q]*/, int32_t Q, float* out /*[N,D,Q]*/, void* stream);
 /* The same contract for long rows, 1 <= S <= 2^24 (the pooled nmc x nposterior draws of the missing-band path, ref:
@@ -574,7 +578,8 @@ typedef struct sf_spectra_desc {
 } sf_spectra_desc;
 int sf_spectra_transform(const sf_spectra_desc* desc, void* stream);
 
-/* PIT ranks of the truths among the posterior draws: out[g,d] = #{draws < truth} / #{finite draws}.
+/* PIT ranks of the truths among the posterior draws: out[g,d] = #{draws < truth} / #{non-NaN draws}
+ * (NaN when there are none; +-inf draws are ordered values and count on both sides; a NaN truth gives 0).
  * Replaces the host pass at ref: sbi_runner.py:7153-7158. */
 int sf_pit_ranks(const float* samples /*[N,S,D]*/, const float* truth /*[N,D]*/, int64_t N, int64_t S, int32_t D,
                  float* out /*[N,D]*/, void* stream);

@@ -26,23 +26,30 @@ def flux_to_asinh(flux_njy, f_b_njy, err_njy=None):
     return mag, K * np.asarray(err_njy, dtype=np.float64) / np.sqrt(f ** 2 + (2 * fb) ** 2)
 
 
-def scatter_depths(flux, depths, n_scatters=5, depth_sigma=5.0, min_flux_pc_error=0.0, seed=0):
+def scatter_depths(flux, depths, n_scatters=5, depth_sigma=5.0, min_flux_pc_error=0.0, seed=0, rows=None):
+    """``rows``: the output rows to evaluate (all N * n_scatters when None); the Philox counter is the output row, so any
+    subset costs only itself."""
     f = np.asarray(flux, dtype=np.float64)
     N, C = f.shape
     sg = np.asarray(depths, dtype=np.float64) / depth_sigma
     # sigma rows: one for all scatter copies, or one per scatter copy ([n_scatters, C], the 2-D depths case after the
     # caller has drawn a depth set per band and scatter)
     sg = np.broadcast_to(sg, (C,))[None, :] if sg.ndim < 2 else sg
-    rep = np.repeat(f, n_scatters, axis=0)
-    sigma = np.maximum(np.tile(sg, (N, 1)) if sg.shape[0] == n_scatters and n_scatters > 1 else sg[:1], np.abs(rep) * min_flux_pc_error / 100.0)
-    z = philox.normal(seed, np.arange(N * n_scatters, dtype=np.uint64), 0, C, stream=2).astype(np.float64)
+    if not (sg.shape[0] == n_scatters and n_scatters > 1):
+        sg = sg[:1]
+    orow = np.arange(N * n_scatters, dtype=np.int64) if rows is None else np.asarray(rows, dtype=np.int64)
+    rep = f[orow // n_scatters]
+    sigma = np.maximum(sg[(orow % n_scatters) % sg.shape[0]], np.abs(rep) * min_flux_pc_error / 100.0)
+    z = philox.normal(seed, orow.astype(np.uint64), 0, C, stream=2).astype(np.float64)
     return rep + sigma * z, sigma
 
 
 def pit_ranks(samples, truth):
+    """#{draws < truth} / #{non-NaN draws} per (row, dim); NaN where every draw is NaN.  +-inf draws are ordered values: they
+    count in the denominator and, where below the truth, in the numerator.  A NaN truth is above nothing: 0."""
     s = np.asarray(samples, dtype=np.float64)
     t = np.asarray(truth, dtype=np.float64)[:, None, :]
-    valid = np.isfinite(s).sum(1)
+    valid = (~np.isnan(s)).sum(1)
     with np.errstate(invalid="ignore", divide="ignore"):
         return np.where(valid > 0, (s < t).sum(1) / valid, np.nan)
 

@@ -9,7 +9,17 @@
 #include "sf_internal.h"
 #include "sf_rng.h"
 
-// one 256-thread workgroup per (galaxy, dim); P = S padded to a power of two (<= 8192), bitonic sort in LDS
+// lower rank of the position (n - 1) q, clamped to [0, n - 1]; defined for every pos (negative, infinite, NaN -> 0 or n - 1)
+__device__ __forceinline__ long sf_q_lo(double pos, int n) {
+  if (!(pos > 0.0)) return 0;
+  if (pos >= (double)(n - 1)) return n - 1;
+  return (long)floor(pos);
+}
+
+// one 256-thread workgroup per (galaxy, dim); P = S padded to a power of two (<= 8192), bitonic sort in LDS.
+// The rule (tests/post_model.py): n = the non-NaN draws, +-inf are ordered values; pos = (n - 1) q in fp64,
+// lo = floor(pos), f = pos - lo; v[lo] where f == 0, else v[lo] + f (v[lo + 1] - v[lo]).  For q outside [0, 1] lo is clamped to
+// [0, n - 1] and the end segment extrapolated: defined, not meaningful (the Python wrappers refuse such q, as numpy does).
 __global__ __launch_bounds__(256) void k_quantiles(const float* __restrict__ samples, long S, int D, int P,
                                                    const float* __restrict__ q, int Q, float* __restrict__ out) {
   extern __shared__ float v[];
@@ -17,15 +27,15 @@ __global__ __launch_bounds__(256) void k_quantiles(const float* __restrict__ sam
   const int d = blockIdx.x % D;
   const float* src = samples + g * S * D + d;
   const float INF = __builtin_inff();
-  for (int i = threadIdx.x; i < P; i += blockDim.x) {
-    float x = i < S ? src[(long)i * D] : INF;
-    v[i] = (x == x) ? x : INF;  // NaN -> +inf: sorted to the end and not counted
-  }
   __shared__ int n_valid;
   if (threadIdx.x == 0) n_valid = 0;
   __syncthreads();
   int cnt = 0;
-  for (int i = threadIdx.x; i < S; i += blockDim.x) cnt += (v[i] < INF) ? 1 : 0;
+  for (int i = threadIdx.x; i < P; i += blockDim.x) {
+    float x = i < S ? src[(long)i * D] : INF;
+    cnt += (i < S && x == x) ? 1 : 0;  // every non-NaN draw counts, +-inf included (as in k_quantiles_large)
+    v[i] = (x == x) ? x : INF;         // NaN -> +inf: sorted to the end, behind (or among) the genuine +inf draws
+  }
   atomicAdd(&n_valid, cnt);
   for (int k = 2; k <= P; k <<= 1) {
     for (int j = k >> 1; j > 0; j >>= 1) {
@@ -45,11 +55,14 @@ __global__ __launch_bounds__(256) void k_quantiles(const float* __restrict__ sam
   for (int t = threadIdx.x; t < Q; t += blockDim.x) {
     float r = __builtin_nanf("");
     if (n > 0) {
-      const float hpos = (float)(n - 1) * q[t];
-      int lo = (int)floorf(hpos);
-      lo = lo < 0 ? 0 : (lo > n - 1 ? n - 1 : lo);
+      // position and interpolation in fp64, as in k_quantiles_large: in fp32 the position error times the gap between
+      // two modes is thousands of ulp at n = 8192; f == 0 returns the order statistic (no 0 * inf beside an infinite draw)
+      const double pos = (double)(n - 1) * (double)q[t];
+      const int lo = (int)sf_q_lo(pos, n);
       const int hi = lo + 1 < n ? lo + 1 : n - 1;
-      r = v[lo] + (hpos - (float)lo) * (v[hi] - v[lo]);
+      const double vlo = (double)v[lo], vhi = (double)v[hi], f = pos - (double)lo;
+      r = (float)(f > 0.0 ? vlo + f * (vhi - vlo) : vlo);
+      if (pos != pos) r = __builtin_nanf("");  // a NaN q
     }
     out[(g * D + d) * Q + t] = r;
   }
@@ -121,8 +134,7 @@ __global__ __launch_bounds__(256) void k_quantiles_large(const float* __restrict
     if (tid < nr) {
       const int t = (r0 + tid) >> 1;
       const double pos = (double)(n - 1) * (double)q[t];
-      long lo = (long)floor(pos);
-      lo = lo < 0 ? 0 : (lo > n - 1 ? n - 1 : lo);
+      const long lo = sf_q_lo(pos, n);
       const long hi = lo + 1 < n ? lo + 1 : n - 1;
       int k = (int)(((r0 + tid) & 1) ? hi : lo), b = 0;
       while (b < 255 && k >= s_h0[b]) { k -= s_h0[b]; ++b; }
@@ -166,24 +178,23 @@ __global__ __launch_bounds__(256) void k_quantiles_large(const float* __restrict
     if (tid < nr && !(tid & 1)) {           // (nr is even: the two ranks of a quantile are in one batch)
       const int t = (r0 + tid) >> 1;
       const double pos = (double)(n - 1) * (double)q[t];
-      long lo = (long)floor(pos);
-      lo = lo < 0 ? 0 : (lo > n - 1 ? n - 1 : lo);
+      const long lo = sf_q_lo(pos, n);
       const double vlo = (double)sf_ql_val(s_pre[tid]), vhi = (double)sf_ql_val(s_pre[tid + 1]);
       const double f = pos - (double)lo;
-      dst[t] = (float)(f > 0.0 ? vlo + f * (vhi - vlo) : vlo);
+      dst[t] = pos != pos ? __builtin_nanf("") : (float)(f > 0.0 ? vlo + f * (vhi - vlo) : vlo);  // (a NaN q -> NaN)
     }
   }
 }
 
 extern "C" int sf_quantiles_large(const float* samples, int64_t N, int64_t S, int32_t D, const float* q_dev, int32_t Q,
                                   float* out, void* stream) {
-  if (!samples || !q_dev || !out) { sf_set_error("sf_quantiles_large: null argument"); return SF_ERR_INVALID; }
   if (S < 1 || S > (1ll << 24) || D < 1 || Q < 1 || Q > 256 || N < 0) {
     sf_set_error("sf_quantiles_large: need 1 <= S <= 2^24, D >= 1, 1 <= Q <= 256, N >= 0");
     return SF_ERR_INVALID;
   }
+  if (N == 0) return SF_OK;  // (an empty catalogue's buffers may be null, as for sf_quantiles)
+  if (!samples || !q_dev || !out) { sf_set_error("sf_quantiles_large: null argument"); return SF_ERR_INVALID; }
   if ((uint64_t)N * (uint64_t)D > 0x7fffffffull) { sf_set_error("sf_quantiles_large: N*D too large for one launch"); return SF_ERR_INVALID; }
-  if (N == 0) return SF_OK;
   hipLaunchKernelGGL(k_quantiles_large, dim3((unsigned)(N * D)), dim3(256), 0, (hipStream_t)stream, samples, (long)S, (int)D,
                      q_dev, (int)Q, out);
   hipError_t e = hipGetLastError();
@@ -289,6 +300,7 @@ __global__ void k_scatter_depths(const float* __restrict__ flux, long N, int C, 
   const int CB = (C + 3) / 4;
   const long total = N * n_scatters * CB;
   const long stride = (long)gridDim.x * blockDim.x;
+  const double pc = (double)min_pc * 0.01;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
     const long orow = i / CB;
     const int cb = (int)(i % CB);
@@ -301,7 +313,8 @@ __global__ void k_scatter_depths(const float* __restrict__ flux, long N, int C, 
       const int c = cb * 4 + j;
       if (c < C) {
         const float f = flux[row * C + c];
-        const float s = fmaxf(sg[c], fabsf(f) * min_pc * 0.01f);
+        // |f| min_pc / 100 in fp64, rounded once (two fp32 products and the rounded 0.01f were up to 1.5 ulp off the formula)
+        const float s = fmaxf(sg[c], (float)((double)fabsf(f) * pc));
         out[orow * C + c] = f + s * z[j];
         if (err_out) err_out[orow * C + c] = s;
       }
@@ -330,8 +343,9 @@ extern "C" int sf_scatter_depths(const float* flux, int64_t N, int32_t C, const 
 }
 
 // ---------------------------------------------------------------------------------------------
-// PIT ranks (ref: sbi_runner.py:7153-7158): rank[g,d] = #{ s : draw[g,s,d] < truth[g,d] } / #{finite draws}
-// one wave per (galaxy, dim); NaN draws ignored (all-NaN -> NaN).
+// PIT ranks (ref: sbi_runner.py:7153-7158): rank[g,d] = #{ s : draw[g,s,d] < truth[g,d] } / #{non-NaN draws}
+// one wave per (galaxy, dim); NaN draws ignored (all-NaN -> NaN); +-inf draws are ordered values and count in both the
+// numerator and the denominator; a NaN truth is below nothing and gives 0.
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_pit_ranks(const float* __restrict__ samples, const float* __restrict__ truth, long N,
                                                    long S, int D, float* __restrict__ out) {

@@ -67,14 +67,16 @@ def scatter_depths(flux: torch.Tensor, depths, n_scatters: int = 5, depth_sigma:
     f = flux.contiguous().float()
     N, Cb = f.shape
     dep = torch.as_tensor(depths, dtype=torch.float32, device=f.device)
+    # a device divisor: torch divides by a Python scalar as a product with its rounded reciprocal, up to 1.5 ulp off depth / depth_sigma
+    ds = torch.tensor(float(depth_sigma), dtype=torch.float32, device=f.device)
     if dep.dim() == 2:  # (k, C) depth sets: depths[idx[c, s], c] per band and scatter (sbi_runner.py:636-649)
         if dep.shape[1] != Cb:
             raise ValueError(f"Mismatch in dimensions: photometry has {Cb} bands but depths has {dep.shape[1]} columns")
         g = torch.Generator().manual_seed(int(seed) & 0x7FFFFFFF)
         idx = torch.randint(0, dep.shape[0], (n_scatters, Cb), generator=g).to(f.device)
-        sg = dep.gather(0, idx) / float(depth_sigma)                       # [n_scatters, C]
+        sg = dep.gather(0, idx) / ds                                       # [n_scatters, C]
     else:
-        sg = dep.reshape(-1) / float(depth_sigma)
+        sg = dep.reshape(-1) / ds
         if sg.numel() == 1:
             sg = sg.expand(Cb)
         if sg.numel() != Cb:
@@ -137,7 +139,8 @@ def apply_scalings(flux: torch.Tensor, error: torch.Tensor, models, flux_units: 
 
 
 def pit_ranks(samples: torch.Tensor, truth: torch.Tensor) -> torch.Tensor:
-    """(N,S,D) draws and (N,D) truths on the GPU -> (N,D) fraction of finite draws below the truth."""
+    """(N,S,D) draws and (N,D) truths on the GPU -> (N,D) #{draws < truth} / #{non-NaN draws}: NaN draws are ignored (none left ->
+    NaN), +-inf draws are ordered values and count in numerator and denominator, a NaN truth gives 0."""
     if samples.device.type != "cuda":
         raise RuntimeError("pit_ranks runs on the GPU (no CPU fallback)")
     s = samples.contiguous().float()

@@ -382,15 +382,26 @@ class EnsemblePosterior:
                        show_progress_bars, force_update, seed)
 
 
+def _checked_q(quantiles) -> np.ndarray:
+    """The requested quantiles as the float32 vector the ABI carries; numpy's refusal (and message) for any outside [0, 1] or
+    NaN, before any device work."""
+    q = np.array(quantiles, dtype=np.float32).reshape(-1)          # (a copy: the caller's array may be read-only)
+    if not np.all((q >= 0.0) & (q <= 1.0)):
+        raise ValueError("Quantiles must be in the range [0, 1]")
+    return q
+
+
 def device_quantiles(samples: torch.Tensor, quantiles) -> torch.Tensor:
     """(N,S,D) float32 device draws -> (N,D,Q) quantiles on the device (sf_quantiles; numpy 'linear' rule,
-    NaN draws ignored).  Counterpart of the host pass at ref: sbi_runner.py:3270-3282."""
+    NaN draws ignored, +-inf draws ordered values; the position (n - 1) q in float64 from the float32 q).  Counterpart of the
+    host pass at ref: sbi_runner.py:3270-3282.  ``quantiles`` outside [0, 1] or NaN: ValueError, as numpy."""
     from . import _lib
+    q = _checked_q(quantiles)
     if samples.device.type != "cuda":
         raise RuntimeError("device_quantiles needs the draws on the GPU")
     samples = samples.contiguous().float()
     N, S, D = samples.shape
-    q = torch.as_tensor(np.asarray(quantiles, dtype=np.float32), device=samples.device)
+    q = torch.as_tensor(q, device=samples.device)
     out = torch.empty((N, D, q.numel()), dtype=torch.float32, device=samples.device)
     st = _lib.stream_ptr(samples.device)
     _lib.check(_lib.load().sf_quantiles(_lib.ptr(samples), N, S, D, _lib.ptr(q), q.numel(), _lib.ptr(out), st))
@@ -402,11 +413,12 @@ def device_quantiles_large(samples: torch.Tensor, quantiles) -> torch.Tensor:
     LDS, the position (n - 1) q in float64) -- the pooled nmc x nposterior draws of the missing-band path
     (ref: sbi_runner.py:3292-3297)."""
     from . import _lib
+    q = _checked_q(quantiles)
     if samples.device.type != "cuda":
         raise RuntimeError("device_quantiles_large needs the draws on the GPU")
     samples = samples.contiguous().float()
     N, S, D = samples.shape
-    q = torch.as_tensor(np.asarray(quantiles, dtype=np.float32), device=samples.device)
+    q = torch.as_tensor(q, device=samples.device)
     out = torch.empty((N, D, q.numel()), dtype=torch.float32, device=samples.device)
     st = _lib.stream_ptr(samples.device)
     with torch.cuda.device(samples.device):

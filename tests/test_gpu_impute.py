@@ -233,9 +233,14 @@ def test_quantiles_large_integer_positions_are_order_statistics():
 
 def test_quantiles_large_agrees_with_the_lds_sort():
     from synference_amd.posterior import device_quantiles
+    import post_model as PM
     x = torch.tensor(np.random.default_rng(2).normal(size=(5, 4096, 5)).astype(np.float32)).cuda()
     a, b = device_quantiles(x, [0.16, 0.5, 0.84]).cpu().numpy(), _ql(x.cpu().numpy(), [0.16, 0.5, 0.84])
-    assert np.abs(a - b).max() < 1e-5                                 # (the fp32 position of the LDS kernel: a few ulp)
+    assert np.abs(a - b).max() < 1e-5
+    # both kernels form the position and the interpolation in fp64 and round once: one fp32 ulp of the larger knot (the bar of
+    # tests/test_gpu_post.py, with the other kernel's result in the model's place)
+    det = PM.quantiles_detail(x.cpu().numpy(), [0.16, 0.5, 0.84])
+    PM.check_quantiles("sort against select", a, det._replace(value=b.astype(np.float64)))
 
 
 # ---- the Python surface ---------------------------------------------------------------------------------------------------------
