@@ -260,7 +260,7 @@ int sf_flow_describe(const sf_flow* f, char* buf, size_t buflen) {
   // the one run-time entry: would a sampling launch over the rows of the prepared context table take the fused kernels NOW
   // (table attached, W' and the compact image fresh)?  0 without a prepared table.
   add("sampler_fused", (f->dev_ready && f->ctab_x) ? (sf_maf16_plan(sampler_dev(f, f->ctab_x)).fused ? 1 : 0) : 0);
-  add("m16_ok", v.m16_ok); add("m16_span", v.m16_span); add("nT16", v.nT16); add("nC16", v.nC16); add("t16_stride", v.t16_stride);
+  add("m16_ok", v.m16_ok); add("m16_span", v.m16_span); add("m16_k3", v.m16_k3); add("nT16", v.nT16); add("nC16", v.nC16); add("t16_stride", v.t16_stride);
   s += "\"g16_tile\": [";
   for (int i = 0; i < SF_DMAX; ++i) s += std::to_string(v.g16_tile[i]) + (i + 1 < SF_DMAX ? ", " : "], ");
   s += "\"g16_lo\": [";

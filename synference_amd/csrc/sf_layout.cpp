@@ -110,8 +110,10 @@ bool sf_build_layout(const sf_flow_desc& d, SfLayout& L) {
   // units and the autoregressive inverse can be evaluated incrementally).
   std::vector<int> hrow_full(4 * 32, -1);
   std::vector<int> h16row(4 * 16, -1);
+  std::vector<int> h16row_trc;  // rows of the cooperative training image: the placement without the skipped register (below)
   v.inc_ok = 0;
   v.m16_ok = 0;
+  v.m16_k3 = 0;
   if (d.kind == SF_MAF) {
     const int mx = std::max(1, D - 1), mn = std::min(1, D - 1);
     const int G = mx;  // degree values mn .. mn+G-1
@@ -181,6 +183,31 @@ bool sf_build_layout(const sf_flow_desc& d, SfLayout& L) {
         v.g16_tile[g + mn] = tile16;
       }
       for (int g = 0; g < G; ++g) v.g16_lo[g + mn] = v.g16_tile[g + mn];
+      // One degree group per tile with D = 3..5 (the shapes of the unrolled kernels, sf_maf16_seq_d): a group of n <= 12 units
+      // leaves register 3 of every row group empty -- unit q sits in row 4 (q / KS) + q % KS, KS = max(3, ceil(n / 4)) -- so
+      // that the fourth k-step of every MFMA that reads the tile (rows 3, 7, 11, 15: sf_mma16) and the fourth tanh register
+      // are structural zeros, which the fused passes skip (sf_pass16g).  Groups of 13..16 units keep their rows (KS = 4).
+      // Every block of the sampler's 16-row images is laid out through h16row -- part A, the fp32 and split-bf16 hidden blocks,
+      // the head tile, W' (k_maf_fuse16 reads the image), the compact image, the context-table weights -- so they all follow;
+      // kernels that keep four k-steps multiply zeros as before.  The cooperative training image (sf_trainc.hip) keeps the rows
+      // 0 .. n - 1 (h16row_trc): another placement would reorder the sums of its MFMAs, and a fit of thousands of steps
+      // amplifies that rounding into other weights -- training must not depend on a sampler optimisation.
+      // m16_k3 = trailing tiles with KS = 3 (degrees are dealt as j % (D - 1): the larger groups come first).
+      h16row_trc = h16row;
+      if (ok16 && D >= 3 && D <= 5 && tile16 + 1 == D - 1) {
+        bool one_per_tile = true;
+        for (int g = 0; g < G; ++g) one_per_tile = one_per_tile && v.g16_tile[g + mn] == g;
+        if (one_per_tile) {
+          std::vector<int> ks(G);
+          for (int g = 0; g < G; ++g) {
+            const int n = (int)grp[g].size();
+            ks[g] = std::max(3, ceil_div(n, 4));
+            for (int r = 0; r < 16; ++r) h16row[g * 16 + r] = -1;
+            for (int q = 0; q < n; ++q) h16row[g * 16 + 4 * (q / ks[g]) + q % ks[g]] = grp[g][q];
+          }
+          while (v.m16_k3 < G && ks[G - 1 - v.m16_k3] == 3) ++v.m16_k3;
+        }
+      }
       if (!ok16 && D >= 2 && NB <= 2 && H <= 64) {
         // whole groups do not fit four tiles: pack the degree-sorted units contiguously; a group may then straddle
         // tiles and its pass recomputes every tile it touches (sf_pass16_span)
@@ -191,6 +218,7 @@ bool sf_build_layout(const sf_flow_desc& d, SfLayout& L) {
           for (int j : grp[g]) h16row[r++] = j;
           v.g16_tile[g + mn] = (r - 1) / 16;
         }
+        h16row_trc = h16row;
         tile16 = (H - 1) / 16;
         ok16 = true;
         v.m16_span = 1;
@@ -548,7 +576,7 @@ bool sf_build_layout(const sf_flow_desc& d, SfLayout& L) {
               bool any = false;
               for (int ro = 0; ro < 16 && !any; ++ro)
                 for (int ri = 0; ri < 16 && !any; ++ri) {
-                  const int oo = h16row[ot * 16 + ro], ii = h16row[it * 16 + ri];
+                  const int oo = h16row_trc[ot * 16 + ro], ii = h16row_trc[it * 16 + ri];
                   any = oo >= 0 && ii >= 0 && deg_h(oo) >= deg_h(ii);
                 }
               if (any) {
@@ -571,7 +599,7 @@ bool sf_build_layout(const sf_flow_desc& d, SfLayout& L) {
         const int64_t gbase_t = (int64_t)t * c.g_stride;   // (g_stride is known from t = 0 on)
         // logical index of W[(to, ro)][(ti, ri)] for every layer, -1 = structural zero
         auto w_in = [&](int to, int ro, int ti, int ri) -> int64_t {
-          const int oo = h16row[to * 16 + ro];
+          const int oo = h16row_trc[to * 16 + ro];
           if (oo < 0) return -1;
           if (ti == 0 && (ri & 3) < 2) {
             const int p = 2 * (ri >> 2) + (ri & 3);
@@ -582,7 +610,7 @@ bool sf_build_layout(const sf_flow_desc& d, SfLayout& L) {
         };
         auto w_hid = [&](int64_t base) {
           return [&, base](int to, int ro, int ti, int ri) -> int64_t {
-            const int oo = h16row[to * 16 + ro], ii = h16row[ti * 16 + ri];
+            const int oo = h16row_trc[to * 16 + ro], ii = h16row_trc[ti * 16 + ri];
             return (oo >= 0 && ii >= 0 && deg_h(oo) >= deg_h(ii)) ? base + (int64_t)oo * H + ii : -1;
           };
         };
@@ -592,7 +620,7 @@ bool sf_build_layout(const sf_flow_desc& d, SfLayout& L) {
           return 2 * sinv[p] + ((ro & 3) >= 2 ? 1 : 0);
         };
         auto w_head = [&](int /*to*/, int ro, int ti, int ri) -> int64_t {
-          const int orow_l = head_row(ro), ii = h16row[ti * 16 + ri];
+          const int orow_l = head_row(ro), ii = h16row_trc[ti * 16 + ri];
           return (orow_l >= 0 && ii >= 0 && (orow_l / 2 + 1) > deg_h(ii)) ? lWf + (int64_t)orow_l * H + ii : -1;
         };
         using WFn = std::function<int64_t(int, int, int, int)>;
@@ -625,7 +653,7 @@ bool sf_build_layout(const sf_flow_desc& d, SfLayout& L) {
             }
         };
         auto hid_bias = [&](int64_t base) {
-          return [&, base](int ot, int ro) -> int64_t { const int oo = h16row[ot * 16 + ro]; return oo >= 0 ? base + oo : -1; };
+          return [&, base](int ot, int ro) -> int64_t { const int oo = h16row_trc[ot * 16 + ro]; return oo >= 0 ? base + oo : -1; };
         };
         if (t == 0) L.gdstC.assign((size_t)0, -1);
         if (L.gdstC.size() < (size_t)P) L.gdstC.resize((size_t)P, -1);   // P = end of this transform's logical block

@@ -97,6 +97,8 @@ struct SfDev {
   const uint32_t* packed16B;
   int t16B_stride, nP16, o16B_wk[2];  // words per transform, in-tile pairs, block offsets in words
   int m16_span;  // 1: contiguous packing, degree groups may straddle tiles (g16_lo < g16_tile)
+  int m16_k3;    // one degree group per tile, D = 3..5: trailing hidden tiles whose rows 3, 7, 11, 15 are empty (groups of <= 12
+                 // units, sf_layout.cpp) -- the fused passes skip the fourth k-step and tanh register of those tiles
   int o16_w0, o16_wc, o16_b0, o16_wk[2], o16_bk[2], o16_hv, o16_hvb;
   int g16_tile[SF_DMAX];  // LAST tile that holds hidden units of MADE degree g ...
   int g16_lo[SF_DMAX];    // ... and the FIRST one (== g16_tile when every degree group sits inside one tile)

@@ -241,8 +241,9 @@ __device__ __forceinline__ void sf_stage16c(const float* src, int wave) {
 #ifndef SF_SAMP16_WG_FUSED
 #define SF_SAMP16_WG_FUSED 4
 #endif
-template <int NB, bool SPAN, bool HM, int DD = 0, int PREC = 0>
+template <int NB, bool SPAN, bool HM, int DD = 0, int PREC = 0, int K3 = 0>
 __global__ __launch_bounds__(256, (SPAN ? 3 : (PREC == 2 ? SF_SAMP16_WG_FUSED : 4))) void k_maf_samp16(SfSamp16Args args_in) {
+  static_assert(K3 == 0 || (PREC == 2 && K3 <= DD - 1), "skipped k-steps: the fused passes only, at most every hidden tile");
   static_assert(DD == 0 || (HM && !SPAN && DD >= 2 && DD <= 5), "unrolled passes: head tile, aligned placement, D <= 5");
   static_assert(PREC != 2 || DD >= 3, "fused first layer: unrolled kernels only (m_fix and the compact image's offsets)");
   using HID = SfHid16<PREC>;
@@ -367,7 +368,7 @@ __global__ __launch_bounds__(256, (SPAN ? 3 : (PREC == 2 ? SF_SAMP16_WG_FUSED : 
           if (HM) S.hdone = sf_ld4(tp + m.o16_bh + g4 * 4);
           if constexpr (PREC == 2) {
             float* scr = sf_lds16 + FC::size + wave * SF_G16_SCR + s * SF_G16_ROW;
-            sf_transform16g<NB, DD>(m, tp, static_cast<const float*>(tpB), S, dsl, u_cur, scr, lane, g4);
+            sf_transform16g<NB, DD, K3>(m, tp, static_cast<const float*>(tpB), S, dsl, u_cur, scr, lane, g4);
           } else {
             S.xr = a.x + gal_cur * m.C;
             if constexpr (DD > 0) {
@@ -525,8 +526,9 @@ __global__ __launch_bounds__(256, (SPAN ? 3 : (PREC == 2 ? SF_SAMP16_WG_FUSED : 
 // A catalogue of 1e5 galaxies spends two thirds of its evaluations here (a few galaxies of acceptance ~1e-4 x 1 000 slots x
 // ~1e4 attempts); on the fp32 kernel k_maf_inv16 those ran at 0.6 of the sampler's rate.  Table path, aligned placement with
 // one degree group per tile (the shapes of the unrolled sampler); two tiles of 16 items per wave and staged transform.
-template <int NB, int DD, int PREC = 0>
+template <int NB, int DD, int PREC = 0, int K3 = 0>
 __global__ __launch_bounds__(256, 4) void k_maf_find16s(SfDev m, SfSampleArgsHost a) {
+  static_assert(K3 == 0 || (PREC == 2 && K3 <= DD - 1), "skipped k-steps: the fused passes only");
   using HID = SfHid16<PREC>;
   using FC = SfFixC16<NB, DD>;   // (PREC 2 only: the compact image)
   SfFix16<NB, DD>::apply(m);  // (the launcher only picks this kernel when the packer's offsets are these)
@@ -572,7 +574,7 @@ __global__ __launch_bounds__(256, 4) void k_maf_find16s(SfDev m, SfSampleArgsHos
         S.hdone = sf_ld4(tp + m.o16_bh + g4 * 4);
         if constexpr (PREC == 2) {
           float* scr = sf_lds16 + FC::size + wave * SF_G16_SCR + s * SF_G16_ROW;
-          sf_transform16g<NB, DD>(m, tp, static_cast<const float*>(tpB), S, dsl, u_cur, scr, lane, g4);
+          sf_transform16g<NB, DD, K3>(m, tp, static_cast<const float*>(tpB), S, dsl, u_cur, scr, lane, g4);
         } else {
           sf_transform16s<HID, NB, DD>(m, tp, tpB, S, NT, dsl, u_cur, lane, g4);
         }
@@ -693,12 +695,26 @@ SfMaf16Plan sf_maf16_plan(const SfDev& m) {
   return pl;
 }
 
-template <int NB, int DD, int PREC>
+// The fused kernels' skipped k-steps as a template argument: f(K3) for K3 = m16_k3 in 0 .. DD - 1 (the packer's count of trailing
+// hidden tiles with empty rows 3, 7, 11, 15); anything else is an error -- a kernel that skipped a row that holds a unit would be wrong
+template <int DD, typename F>
+static hipError_t sf_visit_k3(int k3, F&& f) {
+  switch (k3) {
+    case 0: return f(std::integral_constant<int, 0>{});
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: if constexpr (DD >= 4) return f(std::integral_constant<int, 3>{}); else return hipErrorInvalidValue;
+    case 4: if constexpr (DD >= 5) return f(std::integral_constant<int, 4>{}); else return hipErrorInvalidValue;
+    default: return hipErrorInvalidValue;
+  }
+}
+
+template <int NB, int DD, int PREC, int K3 = 0>
 static hipError_t sf_launch_find16s(const SfDev& m, const SfSampleArgsHost& a, hipStream_t st) {
   static SfAttrCache attr;
   const size_t sh = (size_t)sf_lds_floats16<PREC>(m, true) * sizeof(float) + 80 * sizeof(float);
-  if (hipError_t e = sf_lds_optin16(k_maf_find16s<NB, DD, PREC>, attr); e != hipSuccess) return e;
-  hipLaunchKernelGGL((k_maf_find16s<NB, DD, PREC>), dim3((unsigned)((a.n_items + 127) / 128)), dim3(256), sh, st, m, a);
+  if (hipError_t e = sf_lds_optin16(k_maf_find16s<NB, DD, PREC, K3>, attr); e != hipSuccess) return e;
+  hipLaunchKernelGGL((k_maf_find16s<NB, DD, PREC, K3>), dim3((unsigned)((a.n_items + 127) / 128)), dim3(256), sh, st, m, a);
   return hipGetLastError();
 }
 
@@ -891,17 +907,17 @@ static int sf_resident_blocks16(const void* fn, size_t sh, int cap) {
 }
 
 // persistent sampler: no more workgroups than the chip holds (more would only queue behind the spinning ones)
-template <int NB, bool SPAN, bool HM, int DD, int PREC>
+template <int NB, bool SPAN, bool HM, int DD, int PREC, int K3 = 0>
 static hipError_t sf_launch16q_p(const SfDev& m, const SfSampleArgsHost& a, hipStream_t st) {
   static SfAttrCache attr;
   static SfResidentCache rcache;
   const size_t sh = (size_t)sf_lds_floats16<PREC>(m, !SPAN) * sizeof(float) + (SF_Q_WORDS(64 * SF_SAMP16_TPW) + 96) * sizeof(unsigned int);
   if (sh > 160 * 1024) return hipErrorInvalidValue;
-  if (hipError_t e = sf_lds_optin16(k_maf_samp16<NB, SPAN, HM, DD, PREC>, attr); e != hipSuccess) return e;
+  if (hipError_t e = sf_lds_optin16(k_maf_samp16<NB, SPAN, HM, DD, PREC, K3>, attr); e != hipSuccess) return e;
   int resident = 0, cur_dev = 0;
   (void)hipGetDevice(&cur_dev);
   if (!rcache.get(cur_dev, sh, resident)) {
-    resident = sf_resident_blocks16((const void*)k_maf_samp16<NB, SPAN, HM, DD, PREC>, sh, SPAN ? 3 : (PREC == 2 ? SF_SAMP16_WG_FUSED : 4));
+    resident = sf_resident_blocks16((const void*)k_maf_samp16<NB, SPAN, HM, DD, PREC, K3>, sh, SPAN ? 3 : (PREC == 2 ? SF_SAMP16_WG_FUSED : 4));
     rcache.put(cur_dev, sh, resident);
   }
   long grid = (a.n_items + 64 * SF_SAMP16_TPW - 1) / (64 * SF_SAMP16_TPW);
@@ -909,7 +925,7 @@ static hipError_t sf_launch16q_p(const SfDev& m, const SfSampleArgsHost& a, hipS
   SfSamp16Args args;
   args.m = m;
   args.a = a;
-  hipLaunchKernelGGL((k_maf_samp16<NB, SPAN, HM, DD, PREC>), dim3((unsigned)grid), dim3(256), sh, st, args);
+  hipLaunchKernelGGL((k_maf_samp16<NB, SPAN, HM, DD, PREC, K3>), dim3((unsigned)grid), dim3(256), sh, st, args);
   return hipGetLastError();
 }
 // ... in the plan's arithmetic: the fused first layer (unrolled kernels only), fp32, or split bf16 where the flow has that image
@@ -918,7 +934,7 @@ static hipError_t sf_launch16q_p(const SfDev& m, const SfSampleArgsHost& a, hipS
 template <int NB, bool SPAN, bool HM, int DD>
 static hipError_t sf_launch16q(const SfDev& m, const SfSampleArgsHost& a, const SfMaf16Plan& pl, hipStream_t st) {
   if constexpr (DD > 0) {
-    if (pl.fused) return sf_launch16q_p<NB, SPAN, HM, DD, 2>(m, a, st);
+    if (pl.fused) return sf_visit_k3<DD>(m.m16_k3, [&](auto k3) { return sf_launch16q_p<NB, SPAN, HM, DD, 2, k3()>(m, a, st); });
   }
   if (pl.fp32) return sf_launch16q_p<NB, SPAN, HM, DD, 1>(m, a, st);
   if (!m.packed16B) return hipErrorInvalidValue;
@@ -936,8 +952,9 @@ static hipError_t sf_launch16(const SfDev& m, const SfSampleArgsHost& a, hipStre
 // find / resolve / count launches and the given-noise hook on the unrolled kernels' pass functions, in the plan's arithmetic
 static hipError_t sf_launch_find16(const SfDev& m, const SfSampleArgsHost& a, const SfMaf16Plan& pl, hipStream_t st) {
   return sf_visit_unrolled16(m.NB, pl.dd, [&](auto nb, auto dd) {
-    return pl.fused ? sf_launch_find16s<nb(), dd(), 2>(m, a, st)
-                    : (pl.fp32 ? sf_launch_find16s<nb(), dd(), 1>(m, a, st) : sf_launch_find16s<nb(), dd(), 0>(m, a, st));
+    constexpr int NB_ = decltype(nb)::value, DD_ = decltype(dd)::value;
+    if (pl.fused) return sf_visit_k3<DD_>(m.m16_k3, [&](auto k3) { return sf_launch_find16s<NB_, DD_, 2, k3()>(m, a, st); });
+    return (pl.fp32 ? sf_launch_find16s<nb(), dd(), 1>(m, a, st) : sf_launch_find16s<nb(), dd(), 0>(m, a, st));
   });
 }
 // parity hook of the fused pass functions: theta = inverse(z | x) through k_maf_find16s<.., PREC = 2> in its given-noise mode (the

@@ -695,11 +695,37 @@ struct SfWpCols {
     for (int q = 0; q <= NT - K; ++q) S.pre[K - 1 + q] = sf_rank1(S.pre[K - 1 + q], w[q], wv);
   }
 };
+// Tiles whose rows 3, 7, 11, 15 are empty (SfDev::m16_k3: groups of <= 12 units, the trailing K3 tiles): register 3 of the tile
+// is a structural zero in every lane, so the k-step that reads it (sf_mma16: register j is the B operand of step j) and its
+// tanh are not issued.  SKIP = false is sf_mma16 / sf_tanh4, bit for bit.
+template <bool SKIP>
+__device__ __forceinline__ f32x4 sf_mma16k(float4 w, const f32x4& in, f32x4 acc) {
+  acc = SF_MFMA16(w.x, in[0], acc);
+  acc = SF_MFMA16(w.y, in[1], acc);
+  acc = SF_MFMA16(w.z, in[2], acc);
+  if constexpr (!SKIP) acc = SF_MFMA16(w.w, in[3], acc);
+  return acc;
+}
+template <bool SKIP>
+__device__ __forceinline__ f32x4 sf_tanh4k(const f32x4& b) {
+  if constexpr (!SKIP) {
+    return sf_tanh4(b);
+  } else {
+    const f32x2 one = {1.0f, 1.0f}, m2 = {-2.0f, -2.0f};
+    const f32x2 e01 = f32x2{__builtin_amdgcn_exp2f(b[0]), __builtin_amdgcn_exp2f(b[1])} + one;
+    const float e2 = __builtin_amdgcn_exp2f(b[2]) + 1.0f;
+    const f32x2 r01 = {__builtin_amdgcn_rcpf(e01[0]), __builtin_amdgcn_rcpf(e01[1])};
+    const f32x2 o01 = __builtin_elementwise_fma(r01, m2, one);
+    return f32x4{o01[0], o01[1], __builtin_fmaf(__builtin_amdgcn_rcpf(e2), -2.0f, 1.0f), 0.f};
+  }
+}
 // One pass of the fused kernels: degree group in tile OT (degree OT + 1), new dimension = degree OT + 2 in physical slot sl.
 // Returns the finished value (every row group of the sample holds it) after adding it into the later tiles.
-template <int OT, int NB, int NT>
+// K3: the flow's m16_k3 -- tile it >= NT - K3 is read with three k-steps (second block and head tile alike).
+template <int OT, int NB, int NT, int K3 = 0>
 __device__ __forceinline__ float sf_pass16g(const SfDev& m, const float* tp, const float* tpF, SfPass16G& S, int sl, float u_in,
                                             int lane, int g4) {
+  constexpr bool SK = OT >= NT - K3;   // this pass's own tile
   const float4 wh = sf_w16(tp + m.o16_wh, NT, 0, OT, lane);
   float4 fw[OT + 1];
   f32x4 b1;
@@ -712,16 +738,17 @@ __device__ __forceinline__ float sf_pass16g(const SfDev& m, const float* tp, con
   if constexpr (OT + 2 <= NT) wu.load(tp, m.o16_wp, g4);
   __builtin_amdgcn_sched_barrier(0);
   if (NB == 2) {
+    // tiles finished in earlier passes: not on the chain   (`it` is static after unrolling: one of the two forms remains)
 #pragma unroll
-    for (int it = 0; it < OT; ++it) b1 = sf_mma16(fw[it], S.act[it], b1);   // tiles finished in earlier passes: not on the chain
+    for (int it = 0; it < OT; ++it) b1 = it >= NT - K3 ? sf_mma16k<true>(fw[it], S.act[it], b1) : sf_mma16k<false>(fw[it], S.act[it], b1);
   }
-  f32x4 last = sf_tanh4(S.pre[OT]);
+  f32x4 last = sf_tanh4k<SK>(S.pre[OT]);
   if (NB == 2) {
     S.act[OT] = last;
-    b1 = sf_mma16(fw[OT], last, b1);
-    last = sf_tanh4(b1);
+    b1 = sf_mma16k<SK>(fw[OT], last, b1);
+    last = sf_tanh4k<SK>(b1);
   }
-  S.hdone = sf_mma16(wh, last, S.hdone);
+  S.hdone = sf_mma16k<SK>(wh, last, S.hdone);
   const bool odd = (sl & 1) != 0;
   const int src = (lane & 15) + 16 * (sl >> 1);
   const float av = __shfl(odd ? S.hdone[2] : S.hdone[0], src, 64);
@@ -733,7 +760,7 @@ __device__ __forceinline__ float sf_pass16g(const SfDev& m, const float* tp, con
 // One transform of one tile of 16 draws (k_maf_samp16 / k_maf_find16s, PREC 2).  u: the draw in tile layout (lane (s, g4) holds
 // physical slots 4 g4 .. 4 g4 + 3), in and out; scr: the sample's row of the wave's scratch; S.pre: c0' of the transform,
 // S.hdone: the head biases.
-template <int NB, int DD>
+template <int NB, int DD, int K3 = 0>
 __device__ __forceinline__ void sf_transform16g(const SfDev& m, const float* tp, const float* tpF, SfPass16G& S, int dsl, f32x4& u,
                                                 float* scr, int lane, int g4) {
   constexpr int NT = DD - 1;
@@ -757,7 +784,7 @@ __device__ __forceinline__ void sf_transform16g(const SfDev& m, const float* tp,
   }
   auto pass = [&](auto otc) {
     constexpr int OT = decltype(otc)::value;
-    scr[sl[OT + 1]] = sf_pass16g<OT, NB, NT>(m, tp, tpF, S, sl[OT + 1], ud[OT + 1], lane, g4);
+    scr[sl[OT + 1]] = sf_pass16g<OT, NB, NT, K3>(m, tp, tpF, S, sl[OT + 1], ud[OT + 1], lane, g4);
   };
   pass(std::integral_constant<int, 0>{});
   if constexpr (DD >= 3) pass(std::integral_constant<int, 1>{});
