@@ -126,6 +126,10 @@ int sf_flow_pack_table16b(const sf_flow* f, int32_t* src, int64_t n);
  * and, for ONE transform, src[i] = offset of float i inside that transform of the 16-row image, -1 = padding */
 int64_t sf_flow_packed16c_size(const sf_flow* f);
 int sf_flow_pack_table16c(const sf_flow* f, int32_t* src, int64_t n);
+/* head rows behind the compact image (csrc/sf_layout.h, t16h_stride): T x t16h_stride entries (0 when the flow has none),
+ * src[t * t16h_stride + i] = offset of float i inside transform t of the 16-row image, -1 = padding */
+int64_t sf_flow_packed16h_size(const sf_flow* f);
+int sf_flow_pack_table16h(const sf_flow* f, int32_t* src, int64_t n);
 /* cooperative 16-row training image (MAF, num_blocks 2, D <= 8; csrc/sf_layout.h SfTrcDev): sizes (0 when the flow has
  * none), gather table, logical parameter -> gradient-partial index, and the descriptor as int32 words in declaration order */
 int64_t sf_flow_trainc_size(const sf_flow* f);

@@ -118,6 +118,8 @@ PROTOTYPES = {
     "sf_flow_pack_table16b": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "sf_flow_packed16c_size": (C.c_int64, [C.c_void_p]),
     "sf_flow_pack_table16c": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "sf_flow_packed16h_size": (C.c_int64, [C.c_void_p]),
+    "sf_flow_pack_table16h": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "sf_flow_get_params": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "sf_flow_prepare_context": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "sf_flow_release_context": (C.c_int, [C.c_void_p]),

@@ -55,8 +55,14 @@ static int ensure_device(sf_flow* f) {
     SF_TRY_SET(hipMemcpy(d.d_s16b, f->L.src16b.data(), n16 * sizeof(int32_t), hipMemcpyHostToDevice));
   }
   if (f->L.dev.m16_ok && f->L.n_packed16 > 0 && sf_maf16_compact_fix(f->L.dev) == 1) {   // (only where a kernel reads it)
-    SF_TRY_SET(d.d_packed16c.alloc((size_t)f->L.dev.t16c_stride * f->L.dev.T));
-    SF_TRY_SET(d.d_s16c.upload(f->L.src16c));
+    const SfDev& v = f->L.dev;
+    SF_TRY_SET(d.d_packed16c.alloc((size_t)(v.t16c_stride + v.t16h_stride) * v.T));
+    std::vector<int32_t> tab;   // per transform: the compact image's table (the same for all), then that transform's head rows
+    for (int t = 0; t < v.T; ++t) {
+      tab.insert(tab.end(), f->L.src16c.begin(), f->L.src16c.end());
+      tab.insert(tab.end(), f->L.src16h.begin() + (size_t)t * v.t16h_stride, f->L.src16h.begin() + (size_t)(t + 1) * v.t16h_stride);
+    }
+    SF_TRY_SET(d.d_s16c.upload(tab));
   }
   if ((f->L.dev.m16_ok || f->L.nsfS.ok) && f->L.n_packed16B > 0) {
     const size_t nB = (size_t)f->L.n_packed16B;
@@ -184,6 +190,15 @@ int sf_flow_pack_table16c(const sf_flow* f, int32_t* src, int64_t n) {
   return SF_OK;
 }
 
+int64_t sf_flow_packed16h_size(const sf_flow* f) { return (f && f->L.dev.m16_ok) ? (int64_t)f->L.src16h.size() : 0; }
+
+int sf_flow_pack_table16h(const sf_flow* f, int32_t* src, int64_t n) {
+  if (!f || !src) return sf_fail(SF_ERR_INVALID, "null argument");
+  if (!f->L.dev.m16_ok || n == 0 || n != (int64_t)f->L.src16h.size()) return sf_fail(SF_ERR_INVALID, "no head-row region or size mismatch");
+  std::memcpy(src, f->L.src16h.data(), (size_t)n * sizeof(int32_t));
+  return SF_OK;
+}
+
 int64_t sf_flow_trainc_size(const sf_flow* f) { return (f && (f->L.trc.ok || f->L.nsc.ok)) ? f->L.n_imgC : 0; }
 int64_t sf_flow_trainc_grad_size(const sf_flow* f) { return (f && (f->L.trc.ok || f->L.nsc.ok)) ? f->L.n_gradC : 0; }
 int64_t sf_flow_cst_size(const sf_flow* f) { return f ? (int64_t)f->L.cst.size() : 0; }
@@ -257,6 +272,7 @@ int sf_flow_describe(const sf_flow* f, char* buf, size_t buflen) {
   add("t16_a", v.t16_a); add("t16B_stride", v.t16B_stride); add("nP16", v.nP16); add("o16B_wk0", v.o16B_wk[0]); add("o16B_wk1", v.o16B_wk[1]);
   add("t16c_stride", v.t16c_stride); add("o16c_bk1", v.o16c_bk1); add("o16c_hvb", v.o16c_hvb); add("o16c_bh", v.o16c_bh);
   add("o16c_wh", v.o16c_wh); add("o16c_wp", v.o16c_wp); add("o16c_blk", v.o16c_blk); add("c16_fix", sf_maf16_compact_fix(v));
+  add("t16h_stride", v.t16h_stride);
   // the one run-time entry: would a sampling launch over the rows of the prepared context table take the fused kernels NOW
   // (table attached, W' and the compact image fresh)?  0 without a prepared table.
   add("sampler_fused", (f->dev_ready && f->ctab_x) ? (sf_maf16_plan(sampler_dev(f, f->ctab_x)).fused ? 1 : 0) : 0);

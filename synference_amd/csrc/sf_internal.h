@@ -88,7 +88,8 @@ void sf_ctab_shape(const SfDev& m, int& R, int& NV);
 hipError_t sf_launch_ctab(const SfDev& m, const float* x, long M, float* tab, hipStream_t st);
 hipError_t sf_launch_maf_ctab16(const SfDev& m, const float* x, long M, float* tab, hipStream_t st);
 hipError_t sf_launch_maf_fuse16(const SfDev& m, hipStream_t st);   // W' = (W1 o M)(W0 o M0) into o16_wp of every transform
-// the compact fused image of every transform from the 16-row image (after sf_launch_maf_fuse16: it carries W'); tab: SfLayout::src16c
+// the compact fused image of every transform from the 16-row image (after sf_launch_maf_fuse16: it carries W'); tab: per transform SfLayout::src16c, then that
+// transform's part of src16h
 hipError_t sf_launch_maf_compact16(const SfDev& m, const int32_t* tab, float* out, hipStream_t st);
 // the compact image's offsets against the compile-time ones of the unrolled fused kernels: 1 equal, 0 not, -1 no such kernel for the shape
 int sf_maf16_compact_fix(const SfDev& m);
@@ -189,7 +190,7 @@ struct SfFlowDev {   // ensure_device (sf_api.hip)
   SfBuf<float> d_packed16;      // 16-row image of the incremental MAF inverse (sf_maf16.hip)
   SfBuf<int32_t> d_s16a, d_s16b;
   SfBuf<float> d_packed16c;     // compact fused image (sf_layout.h: packed16c), rebuilt with W' (wp_stale)
-  SfBuf<int32_t> d_s16c;        // its gather table, one transform
+  SfBuf<int32_t> d_s16c;        // its gather table and the head rows' behind it, [T][t16c_stride + t16h_stride]
   SfBuf<unsigned short> d_packed16B;  // split-bf16 hidden blocks of the 16-row sampler (sf_layout.h)
   SfBuf<int32_t> d_s16B;
   SfBuf<unsigned short> d_packedB;    // bf16 hidden operand image (hidden_bf16)

@@ -1119,6 +1119,20 @@ bool sf_build_layout(const sf_flow_desc& d, SfLayout& L) {
         for (int it = 0; it <= ot; ++it) run(v.o16_wk[1] + (ot * NT + it) * 256, 256);
     align(256);
     v.t16c_stride = here();
+    // ---- head rows of the per-lane form (sf_pass16g), behind the compact image of each transform: one entry of 32 floats
+    // [g4][r][a|m] per (hidden tile ot, degree k >= ot + 2), tiles in order and each with its degrees in order (sf_hr16_entry), from
+    // the o16_hv rows of the slot that holds degree k IN THAT TRANSFORM -- hence one table per transform
+    const int NE = D * (D - 1) / 2;
+    v.t16h_stride = (NE * 32 + 255) / 256 * 256;
+    L.src16h.assign((size_t)T * v.t16h_stride, -1);
+    for (int t = 0; t < T; ++t) {
+      int32_t* th = L.src16h.data() + (size_t)t * v.t16h_stride;
+      int e = 0;
+      for (int ot = 0; ot < NT; ++ot)
+        for (int k = ot + 2; k <= D; ++k, ++e)
+          for (int g4 = 0; g4 < 4; ++g4)
+            for (int i = 0; i < 8; ++i) th[e * 32 + g4 * 8 + i] = v.o16_hv + sigma[t][k - 1] * 128 + g4 * 32 + ot * 8 + i;
+    }
   }
   L.n_packedB = (int64_t)L.srcB.size();
   // ---- LDS staging plan (budget: 152 KiB of the 160 KiB LDS; the rest holds the persistent sampler's control block) ---------------------------------

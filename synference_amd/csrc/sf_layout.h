@@ -93,6 +93,13 @@ struct SfDev {
   const float* packed16c;
   int t16c_stride;
   int o16c_bk1, o16c_hvb, o16c_bh, o16c_wh, o16c_wp, o16c_blk;
+  // Behind the compact image of each transform (same buffer: transform t starts at t * (t16c_stride + t16h_stride)), the head rows
+  // as the fused passes read them since they left the matrix pipe: per (hidden tile ot, degree k >= ot + 2) one entry of 32 floats
+  // [g4][r][a|m], entries in tile order and per tile in DEGREE order (sf_hr16_entry, sf_maf16_pass.h), so that every offset in a
+  // pass is a compile-time immediate.  The slot that holds a degree differs from transform to transform: SfLayout::src16h is a
+  // [T][t16h_stride] table.  t16h_stride floats (a multiple of 256; 0 without a compact image).  The head tile and its biases
+  // (o16c_wh, o16c_bh) stay in the compact image but are neither copied to LDS nor read by these kernels.
+  int t16h_stride;
   // split-bf16 hidden blocks of the 16-row sampler: 32-bit words (2 bf16 each), [ot][pair][hi|lo][64 lanes][4 words]
   const uint32_t* packed16B;
   int t16B_stride, nP16, o16B_wk[2];  // words per transform, in-tile pairs, block offsets in words
@@ -215,6 +222,7 @@ struct SfLayout {
   int64_t n_packed16 = 0;
   std::vector<int32_t> src16c;          // compact fused image, ONE transform (dev.t16c_stride entries, the same for every transform):
                                         // offset of the float inside the transform's 16-row image, -1 = padding (zero)
+  std::vector<int32_t> src16h;          // head rows behind it (dev.t16h_stride): [T][t16h_stride], offsets inside THAT transform's image
   int64_t n_packedB = 0;
   std::vector<float> cst;             // constants image
   std::string error;

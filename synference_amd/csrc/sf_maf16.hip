@@ -204,29 +204,39 @@ struct SfFixC16 {
   static constexpr int o_bk1 = 0, o_hvb = NB == 2 ? NT * 16 : 0, o_bh = o_hvb + (2 * DD + 3) / 4 * 4, o_wh = o_bh + 16;
   static constexpr int o_wp = o_wh + NT * 256, o_blk = o_wp + ENT * 16;
   static constexpr int size = (o_blk + (NB == 2 ? ENT * 256 : 0) + 255) / 256 * 256;
-  static constexpr int groups = size / 256;   // 1 KiB wave-instructions per transform
+  // behind it, the head rows of the per-lane form (sf_pass16g): sf_hr16_entries(DD) entries of 32 floats, padded to whole groups
+  static constexpr int o_hr = size, hr_size = (sf_hr16_entries(DD) * 32 + 255) / 256 * 256, total = size + hr_size;
+  // 1 KiB wave-instructions per transform; the groups that hold nothing but the head TILE (o_bh .. o_wp: the matrix-pipe form that
+  // these passes no longer read) are not copied
+  static constexpr int lds = total + 4 * SF_G16_SCR;   // sf_lds_floats16<2>: then the draw-state scratch of the four waves
+  static constexpr int groups = total / 256, dead_lo = (o_bh + 255) / 256, dead_hi = o_wp / 256;
   static bool matches(const SfDev& m) {
     return m.nT16 == NT && m.o16c_bk1 == o_bk1 && m.o16c_hvb == o_hvb && m.o16c_bh == o_bh && m.o16c_wh == o_wh && m.o16c_wp == o_wp &&
-           m.o16c_blk == o_blk && m.t16c_stride == size;
+           m.o16c_blk == o_blk && m.t16c_stride == size && m.t16h_stride == hr_size;
   }
   static __device__ __forceinline__ void apply(SfDev& m) {
-    m.o16_bk[1] = o_bk1; m.o16_hvb = o_hvb; m.o16_bh = o_bh; m.o16_wh = o_wh; m.o16_wp = o_wp;
+    m.o16_bk[1] = o_bk1; m.o16_hvb = o_hvb; m.o16_wp = o_wp;
   }
 };
 // LDS floats in front of a sampler kernel's control words / epilogue constants: the staged operands (+ the draw-state scratch)
 template <int PREC>
 static __host__ __device__ __forceinline__ int sf_lds_floats16(const SfDev& m, bool cp) {
-  if constexpr (PREC == 2) return m.t16c_stride + 4 * SF_G16_SCR;   // (then the draw-state scratch of the four waves)
+  if constexpr (PREC == 2) return m.t16c_stride + m.t16h_stride + 4 * SF_G16_SCR;   // (then the draw-state scratch of the four waves)
   else return (m.ctab ? m.t16_a_tab : m.t16_a) + SfHid16<PREC>::lds_floats(m, cp);
 }
 // Staging of one transform's compact image (G KiB; all four waves, the caller brackets it with barriers): direct global -> LDS
-// copies, 1 KiB wave-instructions dealt to the four waves.
-template <int G>
+// copies, 1 KiB wave-instructions dealt to the four waves.  Groups DEAD_LO .. DEAD_HI - 1 hold only blocks that no PREC 2 kernel
+// reads (the head tile and its biases, SfFixC16::dead_lo / dead_hi): they are not copied and their part of the LDS block stays
+// UNWRITTEN, while the offsets still span it.  This goes once those blocks leave the image.
+template <int G, int DEAD_LO = 0, int DEAD_HI = 0>
 __device__ __forceinline__ void sf_stage16c(const float* src, int wave) {
   const float4* __restrict__ g = reinterpret_cast<const float4*>(src) + (threadIdx.x & 63);
   float4* __restrict__ l = reinterpret_cast<float4*>(sf_lds16);
-  for (int gi = __builtin_amdgcn_readfirstlane(wave); gi < G; gi += 4)
+  constexpr int ND = DEAD_HI > DEAD_LO ? DEAD_HI - DEAD_LO : 0;   // groups DEAD_LO .. DEAD_HI - 1 are skipped
+  for (int q = __builtin_amdgcn_readfirstlane(wave); q < G - ND; q += 4) {
+    const int gi = q < DEAD_LO ? q : q + ND;
     __builtin_amdgcn_global_load_lds((const void*)(g + gi * 64), (void __attribute__((address_space(3)))*)(l + gi * 64), 16, 0, 0);
+  }
   __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0): the copies have landed
 }
 
@@ -252,7 +262,9 @@ __global__ __launch_bounds__(256, (SPAN ? 3 : (PREC == 2 ? SF_SAMP16_WG_FUSED : 
   const int wave = threadIdx.x >> 6;
   using FC = SfFixC16<NB, (PREC == 2 ? DD : 2)>;   // (PREC 2 only: the compact image)
   // with the per-galaxy context table the context block Wc is never read: only the prefix of part A before it is staged
-  unsigned int* ctrl = reinterpret_cast<unsigned int*>(sf_lds16 + sf_lds_floats16<PREC>(args_in.m, !SPAN));
+  // (PREC 2: the host launches these kernels only when the packer's sizes are FC's, so the offset is a compile-time one and the
+  //  queue's addresses behind it cost no registers)
+  unsigned int* ctrl = reinterpret_cast<unsigned int*>(sf_lds16 + (PREC == 2 ? FC::lds : sf_lds_floats16<PREC>(args_in.m, !SPAN)));
   unsigned int pf;
   sf_q_begin<IPW>(args_in.a, ctrl, pf);
   // per-slot constants of the epilogue, once per workgroup, behind the queue's control words
@@ -346,7 +358,7 @@ __global__ __launch_bounds__(256, (SPAN ? 3 : (PREC == 2 ? SF_SAMP16_WG_FUSED : 
 #endif
       __syncthreads();
       // PREC 2: the compact image; else part A of the fp32 image and the hidden blocks, one behind the other in LDS
-      if constexpr (PREC == 2) sf_stage16c<FC::groups>(m.packed16c + (size_t)t * FC::size, wave);
+      if constexpr (PREC == 2) sf_stage16c<FC::groups, FC::dead_lo, FC::dead_hi>(m.packed16c + (size_t)t * FC::total, wave);
       else sf_stage16<PREC, !SPAN>(m, t, S.tab ? m.t16_a_tab : m.t16_a, wave);
       __syncthreads();
 #ifdef SF_Q_STATS
@@ -365,10 +377,10 @@ __global__ __launch_bounds__(256, (SPAN ? 3 : (PREC == 2 ? SF_SAMP16_WG_FUSED : 
             if constexpr (PREC == 2) sf_pre16g_load<DD - 1>(S, g4);
             else if (HM && S.tab) sf_c0_prefetch(S, tiles.tile(2), g4);
           }
-          if (HM) S.hdone = sf_ld4(tp + m.o16_bh + g4 * 4);
+          if constexpr (PREC != 2) { if (HM) S.hdone = sf_ld4(tp + m.o16_bh + g4 * 4); }
           if constexpr (PREC == 2) {
-            float* scr = sf_lds16 + FC::size + wave * SF_G16_SCR + s * SF_G16_ROW;
-            sf_transform16g<NB, DD, K3>(m, tp, static_cast<const float*>(tpB), S, dsl, u_cur, scr, lane, g4);
+            float* scr = sf_lds16 + FC::total + wave * SF_G16_SCR + s * SF_G16_ROW;
+            sf_transform16g<NB, DD, K3>(m, tp, static_cast<const float*>(tpB), tp + FC::o_hr, S, dsl, u_cur, scr, lane, g4);
           } else {
             S.xr = a.x + gal_cur * m.C;
             if constexpr (DD > 0) {
@@ -534,7 +546,7 @@ __global__ __launch_bounds__(256, 4) void k_maf_find16s(SfDev m, SfSampleArgsHos
   SfFix16<NB, DD>::apply(m);  // (the launcher only picks this kernel when the packer's offsets are these)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int s = lane & 15, g4 = lane >> 4;
-  float* ecb = sf_lds16 + sf_lds_floats16<PREC>(m, true);
+  float* ecb = sf_lds16 + (PREC == 2 ? FC::lds : sf_lds_floats16<PREC>(m, true));
   sf_ecb16_build<false>(ecb, m, a);  // (80 words: the launcher adds no room for the column -> slot table)
   if constexpr (PREC == 2) FC::apply(m);   // (the fused passes read the compact image)
   const int NT = m.nT16;
@@ -558,7 +570,7 @@ __global__ __launch_bounds__(256, 4) void k_maf_find16s(SfDev m, SfSampleArgsHos
     if constexpr (PREC == 2) sf_pre16g_load<DD - 1>(S, g4);
     else sf_c0_prefetch(S, 0, g4);
     __syncthreads();
-    if constexpr (PREC == 2) sf_stage16c<FC::groups>(m.packed16c + (size_t)t * FC::size, wave);
+    if constexpr (PREC == 2) sf_stage16c<FC::groups, FC::dead_lo, FC::dead_hi>(m.packed16c + (size_t)t * FC::total, wave);
     else sf_stage16<PREC, true>(m, t, m.t16_a_tab, wave);
     __syncthreads();
     const float* tp = sf_lds16;
@@ -571,10 +583,10 @@ __global__ __launch_bounds__(256, 4) void k_maf_find16s(SfDev m, SfSampleArgsHos
           if constexpr (PREC == 2) sf_pre16g_load<DD - 1>(S, g4);
           else sf_c0_prefetch(S, 0, g4);
         }
-        S.hdone = sf_ld4(tp + m.o16_bh + g4 * 4);
+        if constexpr (PREC != 2) S.hdone = sf_ld4(tp + m.o16_bh + g4 * 4);
         if constexpr (PREC == 2) {
-          float* scr = sf_lds16 + FC::size + wave * SF_G16_SCR + s * SF_G16_ROW;
-          sf_transform16g<NB, DD, K3>(m, tp, static_cast<const float*>(tpB), S, dsl, u_cur, scr, lane, g4);
+          float* scr = sf_lds16 + FC::total + wave * SF_G16_SCR + s * SF_G16_ROW;
+          sf_transform16g<NB, DD, K3>(m, tp, static_cast<const float*>(tpB), tp + FC::o_hr, S, dsl, u_cur, scr, lane, g4);
         } else {
           sf_transform16s<HID, NB, DD>(m, tp, tpB, S, NT, dsl, u_cur, lane, g4);
         }
@@ -869,13 +881,16 @@ hipError_t sf_launch_maf_fuse16(const SfDev& m, hipStream_t st) {
   hipLaunchKernelGGL(k_maf_fuse16, dim3((unsigned)m.T), dim3(256), 0, st, m);
   return hipGetLastError();
 }
-// The compact fused image (sf_layout.h, packed16c) of every transform from the 16-row image, by the packer's table: runs behind
-// k_maf_fuse16 on the same stream, so W' is in it
+// The compact fused image (sf_layout.h, packed16c) of every transform and the head rows behind it from the 16-row image, by the
+// packer's tables: runs behind k_maf_fuse16 on the same stream, so W' is in it.  tab: [T][t16c_stride + t16h_stride] -- the head
+// rows of a degree come from the slot that holds it in THAT transform, so every transform has its own table.
 __global__ __launch_bounds__(256) void k_maf_compact16(SfDev m, const int32_t* __restrict__ tab, float* __restrict__ out) {
+  const int n = m.t16c_stride + m.t16h_stride;
   const float* tp = m.packed16 + (size_t)blockIdx.x * m.t16_stride;
-  float* op = out + (size_t)blockIdx.x * m.t16c_stride;
-  for (int i = threadIdx.x; i < m.t16c_stride; i += blockDim.x) {
-    const int s = tab[i];
+  const int32_t* tt = tab + (size_t)blockIdx.x * n;
+  float* op = out + (size_t)blockIdx.x * n;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    const int s = tt[i];
     op[i] = s >= 0 ? tp[s] : 0.f;
   }
 }

@@ -649,20 +649,47 @@ template <> struct SfHid16<1> {
 // the table), and whenever the dimension of degree k is finished every lane adds W'[rows of tile ot, slot of degree k] . w_k
 // into each tile ot >= k - 1 (one LDS fragment and two v_pk_fma_f32 per tile; only the update of tile k - 1, the next pass's,
 // is on the dependent chain).  k_maf_fuse16 stores exactly those columns, in degree order, as one float4 per row group:
-// entry sf_wp16_entry(NT, k, ot).  A pass then costs 4 (OT + 1) + 4 fp32 MFMAs (56 per tile and transform for cfg1, against
+// entry sf_wp16_entry(NT, k, ot).  A pass then cost 4 (OT + 1) + 4 fp32 MFMAs with the head tile (56 per tile and transform for cfg1, against
 // 72 with the first layer on the matrix pipe and 112 unfused), and its chain is tanh -> W1[OT, OT] -> tanh -> head -> w.
 // The draw state is handed to the passes in the transform's DEGREE order (sf_transform16g): written once per transform to the
 // sample's row in LDS in physical slot order and read back by degree, every finished dimension written to its slot there --
 // the passes themselves carry no runtime slot select and no write-back into a tile-layout quad.  Same function of the same
 // parameters as the two-layer form to fp32 rounding (parity rows: given noise, draw for draw).
+// Head rows: per-lane packed FMAs, not the matrix pipe.  The head TILE of the two-layer passes (o16_wh: the rows of all slots as
+// one 16-row MFMA output) spends 4 MFMAs = 128 cycles per pass on a tile of which 10 of 16 output rows exist and a row of degree
+// d reads only the tiles below d - 1; on gfx950 an fp32 MFMA holds the SIMD like the same FLOPs of v_pk_fma_f32 and nothing
+// overlaps it.  Here the state carries one (a, m) accumulator per degree 2 .. D (SfPass16G::ham, zero at the start of a
+// transform), and pass OT adds the tile it has just finished into the accumulator of EVERY degree >= OT + 2: its own first (four
+// packed FMAs, rows r = 0 .. 3 in order; three where the tile's row 3 is empty), then the sum over the four row groups
+// (xor 16, xor 32) and the head bias last -- the order of sf_head_acc + sf_sum4groups in the per-lane passes -- and the later
+// degrees' in the shadow of the cross-lane sums.  At D = 5 that is 74 MACs = 37 v_pk_fma_f32 per lane and transform in place of
+// 14 MFMAs.  Operands: 32 floats [g4][r][a|m] per (tile, degree) behind the compact image (sf_hr16_entry; SfDev::t16h_stride),
+// every offset an immediate.  Registers: the accumulators of the later degrees and the rank-1 updates of the later tiles are
+// PINNED in the pass that computes them (an empty asm statement on the value): their first reader is a later pass behind the
+// branch of the finish, and the compiler otherwise sinks the FMAs there and keeps the fragments, and a broadcast copy of the
+// tile, alive until then (128 VGPRs and 100 - 140 B of scratch instead of 127 / 0 in the flagship).
 // ---------------------------------------------------------------------------------------------------------------
 struct SfPass16G {
   f32x4 act[4];        // output of block 0 = input of block 1; [tile]
   f32x4 pre[4];        // block 0's pre-activation of tile ot: c0' + the rank-1 updates of the dimensions finished so far
-  f32x4 hdone;
+  f32x2 ham[4];        // [q]: head rows (a, m) of degree q + 2: this lane's products with the tiles finished so far (its row group's share)
   const float* c0p;    // this draw's c0' rows of the transform
   bool tab;
 };
+// Head-row entry of (hidden tile ot, degree k >= ot + 2) in the fused kernels' head-row region: tiles in order, each with its
+// degrees ot + 2 .. D; 32 floats [g4][r][a|m] (a lane reads its row group's two float4; the four groups of a sample read 128
+// contiguous bytes, and every lane of a group the same address: a broadcast)
+__host__ __device__ constexpr int sf_hr16_entry(int D, int ot, int k) { return ot * (D - 1) - ot * (ot - 1) / 2 + (k - ot - 2); }
+__host__ __device__ constexpr int sf_hr16_entries(int D) { return D * (D - 1) / 2; }
+// acc += (a_r, m_r) v_r, r = 0 .. 3 in order, as packed FMAs (sf_head_acc's order); SKIP: row 3 is a structural zero (sf_mma16k)
+template <bool SKIP>
+__device__ __forceinline__ f32x2 sf_head_acck(f32x2 acc, const float4& h01, const float4& h23, const f32x4& v) {
+  acc = __builtin_elementwise_fma(f32x2{h01.x, h01.y}, f32x2{v[0], v[0]}, acc);
+  acc = __builtin_elementwise_fma(f32x2{h01.z, h01.w}, f32x2{v[1], v[1]}, acc);
+  acc = __builtin_elementwise_fma(f32x2{h23.x, h23.y}, f32x2{v[2], v[2]}, acc);
+  if constexpr (!SKIP) acc = __builtin_elementwise_fma(f32x2{h23.z, h23.w}, f32x2{v[3], v[3]}, acc);
+  return acc;
+}
 // W' fragment entry of (input degree k, hidden tile ot >= k - 1): degrees in order, each with its tiles k - 1 .. NT - 1
 __host__ __device__ constexpr int sf_wp16_entry(int NT, int k, int ot) { return (k - 1) * NT - (k - 1) * (k - 2) / 2 + ot - (k - 1); }
 // the sample's row of the draw-state scratch (floats; 20, not 16: the per-degree reads of 16 samples hit 16 different banks)
@@ -692,7 +719,12 @@ struct SfWpCols {
   // the finished dimension w_K into every tile that sees it: tile K - 1 first (the next pass starts from it)
   __device__ __forceinline__ void apply(SfPass16G& S, float wv) const {
 #pragma unroll
-    for (int q = 0; q <= NT - K; ++q) S.pre[K - 1 + q] = sf_rank1(S.pre[K - 1 + q], w[q], wv);
+    for (int q = 0; q <= NT - K; ++q) {
+      S.pre[K - 1 + q] = sf_rank1(S.pre[K - 1 + q], w[q], wv);
+      // (pinned here: the compiler otherwise sinks the update of a later tile into the pass that reads it, across the branch of
+      //  the finish, and holds the fragment and the value until then)
+      if (q > 0) asm volatile("" : "+v"(S.pre[K - 1 + q]));
+    }
   }
 };
 // Tiles whose rows 3, 7, 11, 15 are empty (SfDev::m16_k3: groups of <= 12 units, the trailing K3 tiles): register 3 of the tile
@@ -721,12 +753,23 @@ __device__ __forceinline__ f32x4 sf_tanh4k(const f32x4& b) {
 }
 // One pass of the fused kernels: degree group in tile OT (degree OT + 1), new dimension = degree OT + 2 in physical slot sl.
 // Returns the finished value (every row group of the sample holds it) after adding it into the later tiles.
-// K3: the flow's m16_k3 -- tile it >= NT - K3 is read with three k-steps (second block and head tile alike).
+// K3: the flow's m16_k3 -- tile it >= NT - K3 is read with three k-steps (second block and head rows alike).
 template <int OT, int NB, int NT, int K3 = 0>
-__device__ __forceinline__ float sf_pass16g(const SfDev& m, const float* tp, const float* tpF, SfPass16G& S, int sl, float u_in,
-                                            int lane, int g4) {
+__device__ __forceinline__ float sf_pass16g(const SfDev& m, const float* tp, const float* tpF, const float* hr, SfPass16G& S, int sl,
+                                            const float* scr, int lane, int g4) {
   constexpr bool SK = OT >= NT - K3;   // this pass's own tile
-  const float4 wh = sf_w16(tp + m.o16_wh, NT, 0, OT, lane);
+  constexpr int D = NT + 1, NH = D - (OT + 1);   // head-row entries of tile OT: degrees OT + 2 .. D, this pass's own first
+  // this row group's head rows of (tile OT, degree OT + 2 + q); a tile with an empty row 3 needs three of the four (a, m) pairs
+  float4 h01[NH], h23[NH];
+#pragma unroll
+  for (int q = 0; q < NH; ++q) {
+    const float* p = hr + sf_hr16_entry(D, OT, OT + 2 + q) * 32 + g4 * 8;
+    h01[q] = *reinterpret_cast<const float4*>(p);
+    if constexpr (SK) { const float2 t = *reinterpret_cast<const float2*>(p + 4); h23[q] = float4{t.x, t.y, 0.f, 0.f}; }
+    else h23[q] = *reinterpret_cast<const float4*>(p + 4);
+  }
+  const float ba = tp[m.o16_hvb + 2 * sl], bm = tp[m.o16_hvb + 2 * sl + 1];
+  const float u_in = scr[sl];   // the draw's value of this degree: still in its slot of the sample's row (no pass before this one wrote it)
   float4 fw[OT + 1];
   f32x4 b1;
   if (NB == 2) {
@@ -748,43 +791,51 @@ __device__ __forceinline__ float sf_pass16g(const SfDev& m, const float* tp, con
     b1 = sf_mma16k<SK>(fw[OT], last, b1);
     last = sf_tanh4k<SK>(b1);
   }
-  S.hdone = sf_mma16k<SK>(wh, last, S.hdone);
-  const bool odd = (sl & 1) != 0;
-  const int src = (lane & 15) + 16 * (sl >> 1);
-  const float av = __shfl(odd ? S.hdone[2] : S.hdone[0], src, 64);
-  const float mv = __shfl(odd ? S.hdone[3] : S.hdone[1], src, 64);
+  // head rows of this pass's degree: the finished tile into its accumulator, then the four row groups and the bias -- the order
+  // of sf_head_acc + sf_sum4groups in the per-lane passes (tile ascending, r ascending, xor-16 then xor-32, bias last)
+  const f32x2 pam = sf_head_acck<SK>(S.ham[OT], h01[0], h23[0], last);
+  const float sa = sf_sum4groups(pam[0]), sm = sf_sum4groups(pam[1]);
+  // off the chain, in the shadow of the cross-lane sums: the same tile into the accumulators of the later degrees
+#pragma unroll
+  for (int q = 1; q < NH; ++q) {
+    S.ham[OT + q] = sf_head_acck<SK>(S.ham[OT + q], h01[q], h23[q], last);
+    // (pinned here: left to itself the compiler sinks these FMAs into the pass that first reads the accumulator, across the
+    //  branch of the finish, and keeps this tile's fragments and a broadcast copy of `last` in registers until then)
+    asm volatile("" : "+v"(S.ham[OT + q]));
+  }
+  const float av = ba + sa, mv = bm + sm;
   const float wv = sf_div(u_in - mv, sf_scale16(m, av));
   if constexpr (OT + 2 <= NT) wu.apply(S, wv);
   return wv;
 }
 // One transform of one tile of 16 draws (k_maf_samp16 / k_maf_find16s, PREC 2).  u: the draw in tile layout (lane (s, g4) holds
-// physical slots 4 g4 .. 4 g4 + 3), in and out; scr: the sample's row of the wave's scratch; S.pre: c0' of the transform,
-// S.hdone: the head biases.
+// physical slots 4 g4 .. 4 g4 + 3), in and out; scr: the sample's row of the wave's scratch; S.pre: c0' of the transform; hr: the
+// transform's head-row region.
 template <int NB, int DD, int K3 = 0>
-__device__ __forceinline__ void sf_transform16g(const SfDev& m, const float* tp, const float* tpF, SfPass16G& S, int dsl, f32x4& u,
-                                                float* scr, int lane, int g4) {
+__device__ __forceinline__ void sf_transform16g(const SfDev& m, const float* tp, const float* tpF, const float* hr, SfPass16G& S,
+                                                int dsl, f32x4& u, float* scr, int lane, int g4) {
   constexpr int NT = DD - 1;
+#pragma unroll
+  for (int q = 0; q < NT; ++q) S.ham[q] = f32x2{0.f, 0.f};
   // the 4 row groups write the same row: afterwards every lane reads any slot of its sample (one per degree, slots in SGPRs)
   *reinterpret_cast<f32x4*>(scr + 4 * g4) = u;
   int sl[DD];
-  float ud[DD];
 #pragma unroll
-  for (int q = 0; q < DD; ++q) {
-    sl[q] = __builtin_amdgcn_readlane(dsl, q);
-    ud[q] = scr[sl[q]];
-  }
+  for (int q = 0; q < DD; ++q) sl[q] = __builtin_amdgcn_readlane(dsl, q);
   {
     // degree 1 depends on the context only (head bias)
     SfWpCols<NT, 1> wu;
     wu.load(tp, m.o16_wp, g4);
     const float av = tp[m.o16_hvb + 2 * sl[0]], mv = tp[m.o16_hvb + 2 * sl[0] + 1];
-    const float wv = sf_div(ud[0] - mv, sf_scale16(m, av));
+    const float wv = sf_div(scr[sl[0]] - mv, sf_scale16(m, av));
     wu.apply(S, wv);
     scr[sl[0]] = wv;
   }
+  __builtin_amdgcn_sched_barrier(0);   // (the first pass's operands are requested once the degree-1 columns are spent: registers)
   auto pass = [&](auto otc) {
     constexpr int OT = decltype(otc)::value;
-    scr[sl[OT + 1]] = sf_pass16g<OT, NB, NT, K3>(m, tp, tpF, S, sl[OT + 1], ud[OT + 1], lane, g4);
+    // every degree's incoming value is read from the row in the pass that needs it, not held from the transform's start
+    scr[sl[OT + 1]] = sf_pass16g<OT, NB, NT, K3>(m, tp, tpF, hr, S, sl[OT + 1], scr, lane, g4);
   };
   pass(std::integral_constant<int, 0>{});
   if constexpr (DD >= 3) pass(std::integral_constant<int, 1>{});

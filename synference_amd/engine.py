@@ -116,6 +116,15 @@ class HipFlow:
             _lib.check(self.lib.sf_flow_pack_table16c(self.handle, s.ctypes.data_as(_lib.c_i32p), n))
         return s
 
+    def pack_table16h(self) -> np.ndarray:
+        """Gather table of the head rows behind the compact fused image, [T, t16h_stride] (empty when the flow has none): entry
+        [t, i] = offset of the float inside transform t of the 16-row image; -1 = padding."""
+        n = int(self.lib.sf_flow_packed16h_size(self.handle))
+        s = np.empty(n, np.int32)
+        if n:
+            _lib.check(self.lib.sf_flow_pack_table16h(self.handle, s.ctypes.data_as(_lib.c_i32p), n))
+        return s.reshape(-1, self.describe()["t16h_stride"]) if n else s.reshape(0, 0)
+
     TRC_FIELDS = ("ok NT NI t_stride g_stride o_win o_b0 o_w1 o_b1 o_w2 o_b2 o_wf o_bf o_wfT o_w2T o_w1T o_winT "
                   "g_win g_b0 g_w1 g_b1 g_w2 g_b2 g_wf g_bf kend0 kend1 kend2 kend3 kbeg0 kbeg1 kbeg2 kbeg3 c_insrc c_jobs "
                   "n_jobs").split()
