@@ -7,7 +7,8 @@
 // must return SF_OK even then.)  Needs no GPU; never run on one.
 //   san_handles_host            the whole check
 //   san_handles_host success    the success paths only; with SF_FAKE_HIP_LOG=<file>: one "function bytes" line per runtime call
-//                               (frees of one destroy sorted, frees of null left out) -- equal logs = equal call sequences
+//                               (frees of one destroy sorted, frees of null left out; a launch carries its kernel's mangled name)
+//                               -- equal logs = equal call sequences
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -32,13 +33,12 @@ static FILE* g_log = nullptr;
 static bool g_in_destroy = false;
 static std::vector<std::string> g_destroy_frees;
 
-static void hit(const char* fn, size_t bytes = 0, bool is_free = false) {
+static void hit(const char* fn, size_t bytes = 0, bool is_free = false, const char* detail = "") {
   ++g_hits[fn];
   if (!g_log) return;
-  char line[96];
-  std::snprintf(line, sizeof line, "%s %zu\n", fn, bytes);
+  const std::string line = std::string(fn) + detail + " " + std::to_string(bytes) + "\n";
   if (is_free && g_in_destroy) g_destroy_frees.push_back(line);
-  else std::fputs(line, g_log);
+  else std::fputs(line.c_str(), g_log);
 }
 static bool acquire() { return ++g_acq != g_fail_at; }
 static hipError_t release(std::map<void*, size_t>& live, void* p, const char* fn) {
@@ -112,14 +112,17 @@ hipError_t hipStreamSynchronize(hipStream_t) { hit("hipStreamSynchronize"); retu
 hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { hit("hipStreamCreateWithFlags"); *s = nullptr; return hipSuccess; }
 hipError_t hipStreamDestroy(hipStream_t) { hit("hipStreamDestroy"); return hipSuccess; }
 hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { hit("hipStreamWaitEvent"); return hipSuccess; }
-hipError_t hipLaunchKernel(const void*, dim3 g, dim3 b, void**, size_t sh, hipStream_t) {
-  hit("hipLaunchKernel", (size_t)g.x * g.y * g.z * b.x * b.y * b.z + sh);   // (threads + dynamic LDS: the launch shape)
+// host stub -> mangled kernel name.  (Function-local: the library's module constructors register their kernels before this
+// program's own globals are constructed.)
+static std::map<const void*, std::string>& kernel_names() { static auto* m = new std::map<const void*, std::string>(); return *m; }
+hipError_t hipLaunchKernel(const void* fn, dim3 g, dim3 b, void**, size_t sh, hipStream_t) {
+  hit("hipLaunchKernel", (size_t)g.x * g.y * g.z * b.x * b.y * b.z + sh, false, (" " + kernel_names()[fn]).c_str());   // (threads + dynamic LDS: the launch shape)
   return hipSuccess;
 }
 hipError_t __hipPushCallConfiguration(dim3 g, dim3 b, size_t sh, hipStream_t st) { g_grid = g; g_block = b; g_shmem = sh; g_stream = st; return hipSuccess; }
 hipError_t __hipPopCallConfiguration(dim3* g, dim3* b, size_t* sh, hipStream_t* st) { *g = g_grid; *b = g_block; *sh = g_shmem; *st = g_stream; return hipSuccess; }
 void** __hipRegisterFatBinary(const void*) { static void* h[1]; return h; }
-void __hipRegisterFunction(void**, const void*, char*, const char*, unsigned, void*, void*, void*, void*, int*) {}
+void __hipRegisterFunction(void**, const void* stub, char*, const char* name, unsigned, void*, void*, void*, void*, int*) { kernel_names()[stub] = name; }
 void __hipUnregisterFatBinary(void**) {}
 }  // extern "C"
 
@@ -134,6 +137,7 @@ static std::vector<float> g_flat(1 << 20, 0.01f), g_theta(256 * 16, 0.1f), g_x(2
 static std::vector<float> g_m(1 << 20), g_v(1 << 20);
 static std::vector<int64_t> g_rows(256);
 static std::vector<int32_t> g_drawn(64);
+static const std::vector<uint32_t> g_slots = {0, 3, 4, 9, 14};   // (of the 3 x 5 output slots, sorted)
 
 struct Scenario {
   std::string name;
@@ -195,7 +199,7 @@ static long run_injected(const Scenario& sc, const std::vector<long>& acq) {
   return cases;
 }
 
-static Scenario flow_scenario(const std::string& name, int kind, int D, int C, int NB) {
+static Scenario flow_scenario(const std::string& name, int kind, int D, int C, int NB, bool profiling = true) {
   Scenario sc;
   sc.name = name;
   sc.create = [=]() -> void* {
@@ -208,17 +212,17 @@ static Scenario flow_scenario(const std::string& name, int kind, int D, int C, i
     d.theta_mean = zero.data(); d.theta_std = one.data(); d.x_mean = zero.data(); d.x_std = one.data();
     sf_flow* f = nullptr;
     if (sf_flow_create(&d, &f) != SF_OK || !f) { std::printf("FAILED: sf_flow_create(%s): %s\n", name.c_str(), sf_last_error()); std::exit(1); }
-    sf_flow_set_profiling(f, 1);   // (so that the training events are created too)
+    sf_flow_set_profiling(f, profiling);   // (on: the training events are created too)
     return f;
   };
   sc.destroy = [](void* h) { sf_flow_destroy((sf_flow*)h); };
   const bool plain = kind == SF_MAF || (kind == SF_NSF && D > 1);
   auto F = [](void* h) { return (sf_flow*)h; };
   auto set_params = [=](void* h) { return sf_flow_set_params(F(h), g_flat.data(), sf_flow_num_params(F(h)), 0, nullptr); };
-  auto sample = [=](int64_t M, int64_t S) {
+  auto sample = [=](int64_t M, int64_t S, int32_t max_attempts = 0) {
     return [=](void* h) {
       int64_t unfilled = -1;
-      return sf_flow_sample(F(h), g_x.data(), M, S, g_lo.data(), g_hi.data(), 7, 0, g_out.data(), g_drawn.data(), &unfilled, nullptr);
+      return sf_flow_sample(F(h), g_x.data(), M, S, g_lo.data(), g_hi.data(), 7, max_attempts, g_out.data(), g_drawn.data(), &unfilled, nullptr);
     };
   };
   auto loss_grad = [=](int64_t B, bool dctx, bool rows) {
@@ -237,6 +241,23 @@ static Scenario flow_scenario(const std::string& name, int kind, int D, int C, i
   sc.steps.push_back({"log_prob", [=](void* h) { return sf_flow_log_prob(F(h), g_theta.data(), g_x.data(), 100, g_loss.data(), nullptr); }});
   sc.steps.push_back({"sample 3x5", sample(3, 5)});
   sc.steps.push_back({"sample 40x2000", sample(40, 2000)});   // (more than 2^16 slots: the retry ring grows too)
+  if (plain) sc.steps.push_back({"sample 3x5, at most 2048 attempts", sample(3, 5, 2048)});   // (the capped schedule)
+  sc.steps.push_back({"sample_slots 5 of 3x5", [=](void* h) {
+                        int64_t unfilled = -1;
+                        return sf_flow_sample_slots(F(h), g_x.data(), 3, 5, g_slots.data(), (int64_t)g_slots.size(), g_lo.data(), g_hi.data(), 7, 0,
+                                                    g_out.data(), &unfilled, nullptr);
+                      }});
+  sc.steps.push_back({"acceptance 3x100", [=](void* h) {
+                        return sf_flow_acceptance(F(h), g_x.data(), 3, 100, g_lo.data(), g_hi.data(), 7, g_drawn.data(), nullptr);
+                      }});
+  sc.steps.push_back({"inverse_from_noise 100", [=](void* h) {
+                        return sf_flow_inverse_from_noise(F(h), g_theta.data(), g_x.data(), 100, g_out.data(), g_loss.data(), nullptr);
+                      }});
+  sc.steps.push_back({"inverse_from_noise_sampler 100", [=](void* h) {   // (positive: which arithmetic ran, not an error)
+                        const int rc = sf_flow_inverse_from_noise_sampler(F(h), g_theta.data(), g_x.data(), 100, g_out.data(), nullptr);
+                        return rc > 0 ? (int)SF_OK : rc;
+                      }});
+  sc.steps.push_back({"get_params", [=](void* h) { return sf_flow_get_params(F(h), g_grad.data(), sf_flow_num_params(F(h)), 0, nullptr); }});
   if (plain) {
     sc.steps.push_back({"prepare_context 3", [=](void* h) { return sf_flow_prepare_context(F(h), g_x.data(), 3, nullptr); }});
     sc.steps.push_back({"prepare_context 200", [=](void* h) { return sf_flow_prepare_context(F(h), g_x.data(), 200, nullptr); }});
@@ -258,7 +279,7 @@ static Scenario flow_scenario(const std::string& name, int kind, int D, int C, i
                         return sf_flow_train_epoch(F(h), g_flat.data(), g_theta.data(), g_x.data(), g_rows.data(), 2, 32, 1.f, g_m.data(), g_v.data(), &ad,
                                                    0, 1.f, scratch, g_grad.data(), &loss_sum, nullptr);
                       }, SF_OK});
-  if (!(kind == SF_NSF && D == 1))   // (the one-parameter NSF brackets nothing)
+  if (profiling && !(kind == SF_NSF && D == 1))   // (the one-parameter NSF brackets nothing)
     sc.steps.push_back({"train_stats", [=](void* h) { float ms; return sf_flow_train_stats(F(h), &ms); }});
   return sc;
 }
@@ -275,6 +296,8 @@ int main(int argc, char** argv) {
   all.push_back(flow_scenario("nsf D=1", SF_NSF, 1, 10, 2));
   all.push_back(flow_scenario("nsf_ar D=3", SF_NSF_AR, 3, 10, 2));
   all.push_back(flow_scenario("maf_ar D=3", SF_MAF_AR, 3, 10, 2));
+  all.push_back(flow_scenario("maf D=5, profiling off", SF_MAF, 5, 20, 2, false));   // (the training launches without their event bracket)
+  all.push_back(flow_scenario("nsf D=4, profiling off", SF_NSF, 4, 10, 2, false));
   {
     Scenario sc;
     sc.name = "mlp";
@@ -315,7 +338,7 @@ int main(int argc, char** argv) {
     const std::vector<long> acq = run_success(sc);
     long tot = 0;
     for (long a : acq) tot += a;
-    std::printf("%-12s success path: %ld acquisitions over %zu steps\n", sc.name.c_str(), tot, sc.steps.size());
+    std::printf("%-24s success path: %ld acquisitions over %zu steps\n", sc.name.c_str(), tot, sc.steps.size());
     if (!success_only) cases += run_injected(sc, acq);
   }
   // every fake the script is meant to reach was reached (a fake that is never called checks nothing)

@@ -22,6 +22,13 @@ thread_local std::string g_err;
 int hip_fail(hipError_t e, const char* what) {
   return sf_fail(SF_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
+
+// a developer knob of this file, from the environment (atol).  This reads it on every call: a user that wants it read once
+// keeps the result in a `static const long` of its own.
+long env_long(const char* name, long dflt) {
+  const char* e = std::getenv(name);
+  return e ? std::atol(e) : dflt;
+}
 }  // namespace
 
 // all or nothing: the buffers are built in a local group and moved into the handle at the end, so a failure part-way leaves
@@ -76,8 +83,6 @@ static int ensure_device(sf_flow* f) {
     SF_TRY_SET(hipMemcpy(d.d_bsrc, f->L.srcB.data(), (size_t)f->L.n_packedB * sizeof(int32_t), hipMemcpyHostToDevice));
   }
   SF_TRY_SET(d.d_flat.alloc((size_t)f->L.n_params));
-  SF_TRY_SET(d.d_cnt.alloc(SF_MAX_ROUNDS));
-  SF_TRY_SET(d.h_cnt.alloc(SF_MAX_ROUNDS));
   SF_TRY_SET(d.ev_dense[0].create());
   SF_TRY_SET(d.ev_dense[1].create());
   static_cast<SfFlowDev&>(*f) = std::move(d);
@@ -88,6 +93,26 @@ static int ensure_device(sf_flow* f) {
 sf_flow::~sf_flow() {
   sf_nsf1_destroy(nsf1);
   sf_nsfar_destroy(nsfar);
+}
+
+// a handle whose engine lives in a sub-handle (sf_nsf1.hip, sf_nsfar.hip): L carries the shape only (and, from the caller, n_params)
+static sf_flow* shape_only_handle(const sf_flow_desc& d) {
+  sf_flow* f = new sf_flow();
+  std::memset(&f->L.dev, 0, sizeof(f->L.dev));
+  std::memset(&f->L.trc, 0, sizeof(f->L.trc));
+  std::memset(&f->L.nsc, 0, sizeof(f->L.nsc));
+  std::memset(&f->L.nsfS, 0, sizeof(f->L.nsfS));
+  SfDev& v = f->L.dev;
+  v.kind = d.kind; v.D = d.D; v.C = d.C; v.H = d.H; v.T = d.T; v.K = d.K; v.NB = d.NB;
+  return f;
+}
+
+// one gather table of the 16-row images, to the caller
+static int copy_table16(const sf_flow* f, const std::vector<int32_t>& tab, int32_t* dst, int64_t n, bool empty_ok, const char* what) {
+  if (!f->L.dev.m16_ok || (n == 0 && !empty_ok) || n != (int64_t)tab.size())
+    return sf_fail(SF_ERR_INVALID, std::string("no ") + what + " or size mismatch");
+  std::memcpy(dst, tab.data(), (size_t)n * sizeof(int32_t));
+  return SF_OK;
 }
 
 extern "C" {
@@ -102,34 +127,14 @@ int sf_device_count(void) {
 
 int sf_flow_create(const sf_flow_desc* desc, sf_flow** out) {
   if (!desc || !out) return sf_fail(SF_ERR_INVALID, "null argument");
-  if (desc->kind == SF_NSF && desc->D == 1) {  // sbi's ContextSplineMap flow (sf_nsf1.hip)
-    sf_flow* f1 = new sf_flow();
-    std::string err;
-    int rc = sf_nsf1_create(*desc, &f1->nsf1, err);
-    if (rc) { delete f1; return sf_fail(rc, err); }
-    std::memset(&f1->L.dev, 0, sizeof(f1->L.dev));
-    std::memset(&f1->L.trc, 0, sizeof(f1->L.trc));
-    std::memset(&f1->L.nsc, 0, sizeof(f1->L.nsc));
-    std::memset(&f1->L.nsfS, 0, sizeof(f1->L.nsfS));
-    SfDev& v = f1->L.dev;
-    v.kind = SF_NSF; v.D = 1; v.C = desc->C; v.H = desc->H; v.T = desc->T; v.K = desc->K; v.NB = desc->NB;
-    f1->L.n_params = (int64_t)desc->T * f1->nsf1->P_mlp;
-    *out = f1;
-    return SF_OK;
-  }
-  if (desc->kind == SF_NSF_AR || desc->kind == SF_MAF_AR) {  // the autoregressive flows of the lampe / zuko backend (sf_nsfar.hip)
-    sf_flow* fa = new sf_flow();
-    std::string err;
-    int rc = sf_nsfar_create(*desc, &fa->nsfar, err);
-    if (rc) { delete fa; return sf_fail(rc, err); }
-    std::memset(&fa->L.dev, 0, sizeof(fa->L.dev));
-    std::memset(&fa->L.trc, 0, sizeof(fa->L.trc));
-    std::memset(&fa->L.nsc, 0, sizeof(fa->L.nsc));
-    std::memset(&fa->L.nsfS, 0, sizeof(fa->L.nsfS));
-    SfDev& v = fa->L.dev;
-    v.kind = desc->kind; v.D = desc->D; v.C = desc->C; v.H = desc->H; v.T = desc->T; v.K = desc->K; v.NB = desc->NB;
-    fa->L.n_params = fa->nsfar->n_params;
-    *out = fa;
+  const bool nsf1 = desc->kind == SF_NSF && desc->D == 1;                // sbi's ContextSplineMap flow (sf_nsf1.hip)
+  const bool nsfar = desc->kind == SF_NSF_AR || desc->kind == SF_MAF_AR;  // the autoregressive flows of the lampe / zuko backend (sf_nsfar.hip)
+  if (nsf1 || nsfar) {
+    sf_flow* fs = shape_only_handle(*desc);
+    const int rc = nsf1 ? sf_nsf1_create(*desc, &fs->nsf1) : sf_nsfar_create(*desc, &fs->nsfar);
+    if (rc) { delete fs; return rc; }
+    fs->L.n_params = nsf1 ? (int64_t)desc->T * fs->nsf1->P_mlp : fs->nsfar->n_params;
+    *out = fs;
     return SF_OK;
   }
   sf_flow* f = new sf_flow();
@@ -166,37 +171,29 @@ int64_t sf_flow_packed16_size(const sf_flow* f) { return (f && f->L.dev.m16_ok) 
 
 int sf_flow_pack_table16(const sf_flow* f, int32_t* src1, int32_t* src2, int64_t n_packed16) {
   if (!f || !src1 || !src2) return sf_fail(SF_ERR_INVALID, "null argument");
-  if (!f->L.dev.m16_ok || n_packed16 != f->L.n_packed16) return sf_fail(SF_ERR_INVALID, "no 16-row image or size mismatch");
-  std::memcpy(src1, f->L.src16a.data(), (size_t)n_packed16 * sizeof(int32_t));
-  std::memcpy(src2, f->L.src16b.data(), (size_t)n_packed16 * sizeof(int32_t));
-  return SF_OK;
+  const int rc = copy_table16(f, f->L.src16a, src1, n_packed16, true, "16-row image");
+  return rc ? rc : copy_table16(f, f->L.src16b, src2, n_packed16, true, "16-row image");
 }
 
 int64_t sf_flow_packed16b_size(const sf_flow* f) { return (f && f->L.dev.m16_ok) ? f->L.n_packed16B : 0; }
 
 int sf_flow_pack_table16b(const sf_flow* f, int32_t* src, int64_t n) {
   if (!f || !src) return sf_fail(SF_ERR_INVALID, "null argument");
-  if (!f->L.dev.m16_ok || n != f->L.n_packed16B) return sf_fail(SF_ERR_INVALID, "no split-bf16 image or size mismatch");
-  std::memcpy(src, f->L.src16B.data(), (size_t)n * sizeof(int32_t));
-  return SF_OK;
+  return copy_table16(f, f->L.src16B, src, n, true, "split-bf16 image");
 }
 
 int64_t sf_flow_packed16c_size(const sf_flow* f) { return (f && f->L.dev.m16_ok) ? (int64_t)f->L.src16c.size() : 0; }
 
 int sf_flow_pack_table16c(const sf_flow* f, int32_t* src, int64_t n) {
   if (!f || !src) return sf_fail(SF_ERR_INVALID, "null argument");
-  if (!f->L.dev.m16_ok || n == 0 || n != (int64_t)f->L.src16c.size()) return sf_fail(SF_ERR_INVALID, "no compact fused image or size mismatch");
-  std::memcpy(src, f->L.src16c.data(), (size_t)n * sizeof(int32_t));
-  return SF_OK;
+  return copy_table16(f, f->L.src16c, src, n, false, "compact fused image");
 }
 
 int64_t sf_flow_packed16h_size(const sf_flow* f) { return (f && f->L.dev.m16_ok) ? (int64_t)f->L.src16h.size() : 0; }
 
 int sf_flow_pack_table16h(const sf_flow* f, int32_t* src, int64_t n) {
   if (!f || !src) return sf_fail(SF_ERR_INVALID, "null argument");
-  if (!f->L.dev.m16_ok || n == 0 || n != (int64_t)f->L.src16h.size()) return sf_fail(SF_ERR_INVALID, "no head-row region or size mismatch");
-  std::memcpy(src, f->L.src16h.data(), (size_t)n * sizeof(int32_t));
-  return SF_OK;
+  return copy_table16(f, f->L.src16h, src, n, false, "head-row region");
 }
 
 int64_t sf_flow_trainc_size(const sf_flow* f) { return (f && (f->L.trc.ok || f->L.nsc.ok)) ? f->L.n_imgC : 0; }
@@ -218,12 +215,24 @@ int sf_flow_trainc_table(const sf_flow* f, int32_t* src1, int32_t* src2, int64_t
   return SF_OK;
 }
 
+static void nsf_sampler_view(const sf_flow* f, SfDev& m);
 static SfDev sampler_dev(const sf_flow* f, const float* x);
 int sf_flow_describe(const sf_flow* f, char* buf, size_t buflen) {
   if (!f || !buf) return sf_fail(SF_ERR_INVALID, "null argument");
   const SfDev& v = f->L.dev;
   std::string s = "{";
   auto add = [&](const char* k, long val) { s += "\"" + std::string(k) + "\": " + std::to_string(val) + ", "; };
+  auto arr = [&](const char* k, const auto* a, size_t n) {
+    s += "\"" + std::string(k) + "\": [";
+    for (size_t i = 0; i < n; ++i) s += std::to_string(a[i]) + (i + 1 < n ? ", " : "");
+    s += "], ";
+  };
+  auto finish = [&]() {   // (the ", " behind the last entry closes the object)
+    s.replace(s.size() - 2, 2, "}");
+    if (s.size() + 1 > buflen) return sf_fail(SF_ERR_INVALID, "buffer too small");
+    std::memcpy(buf, s.c_str(), s.size() + 1);
+    return (int)SF_OK;
+  };
   if (f->nsfar) {   // the autoregressive NSF has its own images (sf_nsfar.h)
     const SfNsfAr& n = *f->nsfar;
     add("kind", n.affine ? SF_MAF_AR : SF_NSF_AR); add("D", n.D); add("C", n.C); add("H", n.H); add("T", n.T); add("K", n.K); add("NB", 2);
@@ -232,15 +241,9 @@ int sf_flow_describe(const sf_flow* f, char* buf, size_t buflen) {
     add("o_L2t", n.o_L2t); add("o_b2", n.o_b2); add("o_L0m", n.o_L0m); add("o_L2m", n.o_L2m); add("lds_bytes_train", (long)sf_nsfar_lds_bytes(n, 3));
     add("sampler_tiles16", sf_nsfar16_eligible(n) ? 1 : 0); add("s16_nt", n.s16_nt); add("s16_ni", n.s16_ni); add("s16_ks", n.s16_ks); add("s16_tpt", n.s16_tpt);
     add("o_F0", n.o_F0); add("o_fb0", n.o_fb0); add("o_F1", n.o_F1); add("o_fb1", n.o_fb1); add("o_F2", n.o_F2);
-    auto arr = [&](const char* k, const std::vector<int32_t>& a, bool last) {
-      s += "\"" + std::string(k) + "\": [";
-      for (size_t i = 0; i < a.size(); ++i) s += std::to_string(a[i]) + (i + 1 < a.size() ? ", " : "");
-      s += last ? "]}" : "], ";
-    };
-    arr("perm", n.perm, false); arr("ptype", n.ptype, false); arr("tend", n.tend, false); arr("ord", n.ord, false); arr("dimof", n.dimof, true);
-    if (s.size() + 1 > buflen) return sf_fail(SF_ERR_INVALID, "buffer too small");
-    std::memcpy(buf, s.c_str(), s.size() + 1);
-    return SF_OK;
+    auto vec = [&](const char* k, const std::vector<int32_t>& a) { arr(k, a.data(), a.size()); };
+    vec("perm", n.perm); vec("ptype", n.ptype); vec("tend", n.tend); vec("ord", n.ord); vec("dimof", n.dimof);
+    return finish();
   }
   add("kind", v.kind); add("D", v.D); add("C", v.C); add("H", v.H); add("T", v.T); add("K", v.K);
   add("NB", v.NB); add("HT", v.HT); add("PT", v.PT); add("KMAX", v.KMAX); add("JP", v.JP);
@@ -277,28 +280,16 @@ int sf_flow_describe(const sf_flow* f, char* buf, size_t buflen) {
   // (table attached, W' and the compact image fresh)?  0 without a prepared table.
   add("sampler_fused", (f->dev_ready && f->ctab_x) ? (sf_maf16_plan(sampler_dev(f, f->ctab_x)).fused ? 1 : 0) : 0);
   add("m16_ok", v.m16_ok); add("m16_span", v.m16_span); add("m16_k3", v.m16_k3); add("nT16", v.nT16); add("nC16", v.nC16); add("t16_stride", v.t16_stride);
-  s += "\"g16_tile\": [";
-  for (int i = 0; i < SF_DMAX; ++i) s += std::to_string(v.g16_tile[i]) + (i + 1 < SF_DMAX ? ", " : "], ");
-  s += "\"g16_lo\": [";
-  for (int i = 0; i < SF_DMAX; ++i) s += std::to_string(v.g16_lo[i]) + (i + 1 < SF_DMAX ? ", " : "], ");
-  s += "\"g_kend\": [";
-  for (int i = 0; i < SF_DMAX; ++i) s += std::to_string(v.g_kend[i]) + (i + 1 < SF_DMAX ? ", " : "], ");
-  s += "\"g_lo\": [";
-  for (int i = 0; i < SF_DMAX; ++i) s += std::to_string(v.g_lo[i]) + (i + 1 < SF_DMAX ? ", " : "], ");
-  s += "\"g_tile\": [";
-  for (int i = 0; i < SF_DMAX; ++i) s += std::to_string(v.g_tile[i]) + (i + 1 < SF_DMAX ? ", " : "], ");
-  s += "\"mt_kend\": [";
-  for (int i = 0; i < 4; ++i) s += std::to_string(v.mt_kend[i]) + (i + 1 < 4 ? ", " : "], ");
+  arr("g16_tile", v.g16_tile, SF_DMAX); arr("g16_lo", v.g16_lo, SF_DMAX); arr("g_kend", v.g_kend, SF_DMAX); arr("g_lo", v.g_lo, SF_DMAX);
+  arr("g_tile", v.g_tile, SF_DMAX); arr("mt_kend", v.mt_kend, 4);
   s += "\"cst\": [";
   for (size_t i = 0; i < f->L.cst.size(); ++i) {
     char t[40];
     std::snprintf(t, sizeof(t), "%.9g%s", f->L.cst[i], i + 1 < f->L.cst.size() ? ", " : "");
     s += t;
   }
-  s += "]}";
-  if (s.size() + 1 > buflen) return sf_fail(SF_ERR_INVALID, "buffer too small");
-  std::memcpy(buf, s.c_str(), s.size() + 1);
-  return SF_OK;
+  s += "], ";
+  return finish();
 }
 
 int sf_flow_set_params(sf_flow* f, const float* flat, int64_t n, int is_device, void* stream) {
@@ -314,9 +305,8 @@ int sf_flow_set_params(sf_flow* f, const float* flat, int64_t n, int is_device, 
   f->gt_image_valid = false;  // (sf_flow_log_prob_grad rebuilds its transposed image on its next call)
   if (f->nsf1) { f->params_set = true; return SF_OK; }   // (the MLP engine re-tiles per call)
   if (f->nsfar) {
-    std::string err;
-    rc = sf_nsfar_pack(f->nsfar, src, st, err);
-    if (rc) return sf_fail(rc, err);
+    rc = sf_nsfar_pack(f->nsfar, src, st);
+    if (rc) return rc;
     f->params_set = true;
     return SF_OK;
   }
@@ -349,16 +339,8 @@ int sf_flow_log_prob(sf_flow* f, const float* theta, const float* x, int64_t B, 
   if (!theta || !x || !out) return sf_fail(SF_ERR_INVALID, "null argument");
   if (!f->params_set) return sf_fail(SF_ERR_STATE, "sf_flow_set_params has not been called");
   if (B < 0) return sf_fail(SF_ERR_INVALID, "B < 0");
-  if (f->nsf1) {
-    std::string err;
-    int rc = sf_nsf1_log_prob(f->nsf1, f->d_flat, theta, x, (long)B, out, (hipStream_t)stream, err);
-    return rc ? sf_fail(rc, err) : SF_OK;
-  }
-  if (f->nsfar) {
-    std::string err;
-    int rc = sf_nsfar_log_prob(f->nsfar, theta, x, (long)B, out, (hipStream_t)stream, err);
-    return rc ? sf_fail(rc, err) : SF_OK;
-  }
+  if (f->nsf1) return sf_nsf1_log_prob(f->nsf1, f->d_flat, theta, x, (long)B, out, (hipStream_t)stream);
+  if (f->nsfar) return sf_nsfar_log_prob(f->nsfar, theta, x, (long)B, out, (hipStream_t)stream);
   SF_TRY_SET(sf_launch_logprob(f->dev(), theta, x, (long)B, out, (hipStream_t)stream));
   return SF_OK;
 }
@@ -369,24 +351,14 @@ int sf_flow_inverse_from_noise(sf_flow* f, const float* z, const float* x, int64
   if (B == 0) return SF_OK;
   if (!z || !x || !theta) return sf_fail(SF_ERR_INVALID, "null argument");
   if (!f->params_set) return sf_fail(SF_ERR_STATE, "sf_flow_set_params has not been called");
-  if (f->nsf1) {
-    std::string err;
-    int rc = sf_nsf1_inverse(f->nsf1, f->d_flat, z, x, (long)B, theta, logdet, (hipStream_t)stream, err);
-    return rc ? sf_fail(rc, err) : SF_OK;
-  }
-  if (f->nsfar) {
-    std::string err;
-    int rc = sf_nsfar_inverse(f->nsfar, z, x, (long)B, theta, logdet, (hipStream_t)stream, err);
-    return rc ? sf_fail(rc, err) : SF_OK;
-  }
+  if (f->nsf1) return sf_nsf1_inverse(f->nsf1, f->d_flat, z, x, (long)B, theta, logdet, (hipStream_t)stream);
+  if (f->nsfar) return sf_nsfar_inverse(f->nsfar, z, x, (long)B, theta, logdet, (hipStream_t)stream);
   SfSampleArgsHost a;
   a.x = x; a.z_in = z; a.n_items = (long)B; a.out = theta; a.logdet_out = logdet;
   SF_TRY_SET(sf_launch_inverse(f->dev(), a, (hipStream_t)stream));
   return SF_OK;
 }
 
-static void nsf_sampler_view(const sf_flow* f, SfDev& m);
-static SfDev sampler_dev(const sf_flow* f, const float* x);
 int sf_flow_inverse_from_noise_sampler(sf_flow* f, const float* z, const float* x, int64_t B, float* theta, void* stream) {
   if (!f) return sf_fail(SF_ERR_INVALID, "null handle");
   if (B == 0) return SF_OK;
@@ -469,13 +441,14 @@ static void seed_keys(uint64_t seed, uint32_t stream_id, uint32_t& k0, uint32_t&
   k1 = (uint32_t)(seed >> 32) ^ stream_id;
 }
 
+// added to the slot id in the Philox counter (SfSampleArgsHost::rng_slot_offset): the rows before this call's in its catalogue
+static unsigned long long slot_offset(const sf_flow* f, int64_t S) {
+  return (unsigned long long)f->sample_row_offset * (unsigned long long)S;
+}
+
 // ---- per-galaxy context table ---------------------------------------------------------------
 static size_t ctab_limit_bytes() {
-  static long v = -1;
-  if (v < 0) {
-    const char* e = std::getenv("SF_CTAB_MAX_MB");  // 0 disables the table
-    v = e ? std::atol(e) : 4096;
-  }
+  static const long v = env_long("SF_CTAB_MAX_MB", 4096);  // 0 disables the table
   return (size_t)v << 20;
 }
 
@@ -563,7 +536,7 @@ int sf_flow_sample_round(sf_flow* f, const float* x, int64_t S, const uint32_t* 
   SfSampleArgsHost a;
   a.x = x; a.S = (long)S; a.slots = slots; a.slot_base = (long)slot_base; a.n_items = (long)n_slots * A;
   a.attempts_per_slot = A; a.attempt = attempt; seed_keys(seed, stream_id, a.k0, a.k1);
-  a.rng_slot_offset = (unsigned long long)f->sample_row_offset * (unsigned long long)S;
+  a.rng_slot_offset = slot_offset(f, S);
   a.lo = lo; a.hi = hi; a.out = out; a.rejected = rejected; a.n_rejected = n_rejected; a.n_drawn = n_drawn;
   if (f->ctab_x == x && (uint64_t)(slot_base + n_slots) > (uint64_t)f->ctab_M * (uint64_t)S && slots == nullptr)
     return sf_fail(SF_ERR_INVALID, "slots reach past the rows given to sf_flow_prepare_context");
@@ -604,6 +577,62 @@ static int ensure_queue(sf_flow* f, int64_t n_slots, int64_t M) {
   return SF_OK;
 }
 
+// The order in which a persistent launch walks its dense list (SfSampleArgsHost: dense_G, dense_run, list_mul): a function of the
+// list (cur: null = every slot), the stage, the open slots, the catalogue's shape and the kernel's tile
+static void dense_order(SfSampleArgsHost& a, const uint32_t* cur, int stage, int64_t pending, int64_t M, int64_t S, uint32_t tile) {
+  static const long env_il = env_long("SF_INTERLEAVE", 128);  // developer knob: SF_INTERLEAVE=<galaxies per block>, 0 = plain slot order (A-B runs)
+  a.dense_G = (!cur && env_il > 0 && pending == M * S && M > 1 && (int64_t)env_il * S < (int64_t)1 << 31) ? (uint32_t)env_il : 0u;
+  uint32_t run = tile;
+  // (S = 1000 does not divide into tiles of 16 / 32: the largest power of two that divides S -- 8 -- still gives every
+  //  tile runs of consecutive draws of few galaxies; round 4 fell back to draw-by-draw order there)
+  while (run > 1 && S % (int64_t)run != 0) run >>= 1;
+  a.dense_run = run;
+  a.list_mul = 0; a.list_log2 = 0;
+  if (cur && stage == 0 && env_il > 0 && pending >= 4096 && pending < (1ll << 31)) {  // the caller's list (sorted by slot): strided walk
+    uint32_t k = 12;
+    while ((1ull << k) < (uint64_t)pending) ++k;
+    a.list_log2 = k;
+    a.list_mul = (uint32_t)(((1ull << k) / 128u) | 1u);   // odd: a bijection of [0, 2^k)
+  }
+}
+
+// the queue words of the launches so far, on the host (h_queue); a queue error ends the call.  Only the persistent kernel writes
+// SfQueue::error, and the deep tail begins after a persistent stage that read back 0: in the tail loop the check never fires.
+static int read_queue(sf_flow* f, int64_t pending, hipStream_t st) {
+  SF_TRY_SET(hipMemcpyAsync(f->h_queue, f->d_queue, sizeof(SfQueue), hipMemcpyDeviceToHost, st));  // pinned
+  SF_TRY_SET(hipStreamSynchronize(st));
+  if (!f->h_queue->error) return SF_OK;
+  f->ctab_x = nullptr;
+  return sf_fail(SF_ERR_STATE, "persistent sampler: work queue inconsistent (code " + std::to_string(f->h_queue->error) +
+                                ": 1 = a device-side wait exceeded its bound, 2 = foreign ring entry, 3 = survivor "
+                                "list overflow, 4 = listed slot outside M*S, 5 = claimed entry never arrived, 6/7 = "
+                                "claim contention); head " + std::to_string(f->h_queue->head) + " reserve " +
+                                std::to_string(f->h_queue->reserve) + " resolved " + std::to_string(f->h_queue->resolved) +
+                                " of " + std::to_string((unsigned)pending) + " survivors " + std::to_string(f->h_queue->n_surv) +
+                                " dense_next " + std::to_string(f->h_queue->dense_next));
+}
+
+// drop the open slots of galaxies that made no progress (NaN rows), in place, and start their counters over
+static int drop_stalled(sf_flow* f, uint32_t* list, int64_t M, int64_t S, float* out, int out_f64, hipStream_t st) {
+  SF_TRY_SET(sf_launch_filter_survivors(list, &f->d_queue->n_surv, (long)S, f->d_galacc, out, f->L.dev.D, st, out_f64));
+  SF_TRY_SET(hipMemsetAsync(f->d_galacc, 0, (size_t)M * sizeof(int32_t), st));
+  return SF_OK;
+}
+
+static void print_queue_stats(const SfQueue& h, int stage, unsigned n_total) {   // SF_Q_STATS=1 (counters of a -DSF_Q_STATS build)
+  const unsigned long long* q = h.stats;
+  std::fprintf(stderr, "[sf_queue] stage %d: entry-barrier %.3e cyc, serial %.3e cyc, exit-barrier %.3e cyc, idle %.3e cyc in %llu "
+               "episodes, %llu donations, iterations dense %llu tail %llu, entries %llu, evals %llu, resolved %u/%u\n", stage,
+               (double)q[0], (double)q[1], (double)q[2], (double)q[3], q[4], q[5], q[6], q[7], q[8],
+               (unsigned long long)h.evals, h.resolved, n_total);
+  std::fprintf(stderr, "[sf_queue]   max iterations of a workgroup %llu; last flow evaluation ended %.1f us, last exit %.1f us after the first start\n",
+               q[11], ((double)q[12] - (double)q[10]) * 0.01, ((double)q[13] - (double)q[10]) * 0.01);
+  std::fprintf(stderr, "[sf_queue]   wave 0 of every workgroup, summed, dense mode (us): fetch %.0f, prologue %.0f, staging %.0f, passes %.0f, epilogue %.0f\n",
+               (double)q[14] * 0.01, (double)q[15] * 0.01, (double)q[16] * 0.01, (double)q[17] * 0.01, (double)q[18] * 0.01);
+  std::fprintf(stderr, "[sf_queue]   the same in tail mode (us): fetch %.0f, prologue %.0f, staging %.0f, passes %.0f, epilogue %.0f\n",
+               (double)q[19] * 0.01, (double)q[20] * 0.01, (double)q[21] * 0.01, (double)q[22] * 0.01, (double)q[23] * 0.01);
+}
+
 // x [M,C]; slots: device list of n_slots output slots (NULL = all of 0 .. M*S-1); see sf_flow_sample_slots
 static int sample_persistent(sf_flow* f, const float* x, int64_t M, int64_t S, const uint32_t* slots, int64_t n_slots,
                              const float* lo, const float* hi, uint64_t seed, int32_t max_attempts, float* out,
@@ -615,14 +644,12 @@ static int sample_persistent(sf_flow* f, const float* x, int64_t M, int64_t S, c
   if (rc) return rc;
   const bool capped = max_attempts > 0;
   const uint32_t ceiling = capped ? (uint32_t)max_attempts : 0x40000000u;
-  {
-    rc = sf_flow_prepare_context(f, x, M, (void*)st);
-    if (rc) return rc;
-  }
+  rc = sf_flow_prepare_context(f, x, M, (void*)st);
+  if (rc) return rc;
   const SfDev m = sampler_dev(f, x);
   SfSampleArgsHost a;
   a.x = x; a.S = (long)S; seed_keys(seed, 0, a.k0, a.k1);
-  a.rng_slot_offset = (unsigned long long)f->sample_row_offset * (unsigned long long)S;
+  a.rng_slot_offset = slot_offset(f, S);
   a.lo = lo; a.hi = hi; a.out = out; a.n_drawn = n_drawn; a.out_f64 = f->sample_out_f64 ? 1 : 0;
   a.q = f->d_queue; a.ring = f->d_ring; a.ring_mask = (uint32_t)(f->d_ring.cap() - 1);
   a.out_slots = (uint32_t)(M * S);
@@ -641,6 +668,8 @@ static int sample_persistent(sf_flow* f, const float* x, int64_t M, int64_t S, c
   //  slot that needs hundreds of attempts is cheaper side by side in a find launch than 32 at a time in the tail; the
   //  16-row MAF kernel, 35 us per sparse iteration and 64 attempts wide, is best left at 1 024)
   const uint32_t first_window = fast16 ? 1024u : 256u;
+  // the window after one that ended at `end`: sixteen times as deep, up to the ceiling
+  auto next_window = [&](uint32_t end) { return (end > ceiling / 16u) ? ceiling : end * 16u; };
   uint32_t attempt = 0, limit = ceiling < first_window ? ceiling : first_window;
   int buf = 0, stage = 0;
   double evals = 0.0;
@@ -663,12 +692,8 @@ static int sample_persistent(sf_flow* f, const float* x, int64_t M, int64_t S, c
   // with the windows [1 024, 16 384), [16 384, 262 144) ...: the queue keeps every lane busy with speculation 64 wide
   // at the sampler kernel's cost per evaluation.  (Chip-wide find / resolve launches, below, are for the FEW slots that
   // remain: they spread one slot's attempts over the whole chip, on the plain fp32 kernels.)
-  int64_t persist_min = 8192;
-  {
-    static long env_pm = -1;  // developer knob: SF_PERSIST_MIN=<slots> (1 = every window on the persistent kernel: tests)
-    if (env_pm < 0) { const char* e = std::getenv("SF_PERSIST_MIN"); env_pm = e ? std::atol(e) : 0; }
-    if (env_pm > 0) persist_min = env_pm;
-  }
+  static const long env_pm = env_long("SF_PERSIST_MIN", 0);  // developer knob: SF_PERSIST_MIN=<slots> (1 = every window on the persistent kernel: tests)
+  const int64_t persist_min = env_pm > 0 ? env_pm : 8192;
   for (;;) {
     // The retry ring stays all-zero only while every launch ends cleanly (consumers clear what they take).  A launch that
     // ended on a queue error, or never completed, may have left donated entries behind: clear the ring before it is reused.
@@ -680,25 +705,7 @@ static int sample_persistent(sf_flow* f, const float* x, int64_t M, int64_t S, c
 #endif
     if (progress_rule && stage == 0) SF_TRY_SET(hipMemsetAsync(f->d_galacc, 0, (size_t)M * sizeof(int32_t), st));  // (later: carried over)
     a.slots = cur; a.slot_base = 0; a.n_items = (long)pending; a.n_total = (uint32_t)pending;
-    {
-      static int env_il = -1;  // developer knob: SF_INTERLEAVE=<galaxies per block>, 0 = plain slot order (A-B runs)
-      if (env_il < 0) { const char* e = std::getenv("SF_INTERLEAVE"); env_il = e ? std::atoi(e) : 128; }
-      a.dense_G = (!cur && env_il > 0 && pending == M * S && M > 1 && (int64_t)env_il * S < (int64_t)1 << 31) ? (uint32_t)env_il : 0u;
-      {
-        uint32_t run = fast16 ? 16u : 32u;  // the kernel's tile
-        // (S = 1000 does not divide into tiles of 16 / 32: the largest power of two that divides S -- 8 -- still gives every
-        //  tile runs of consecutive draws of few galaxies; round 4 fell back to draw-by-draw order there)
-        while (run > 1 && S % (int64_t)run != 0) run >>= 1;
-        a.dense_run = run;
-      }
-      a.list_mul = 0; a.list_log2 = 0;
-      if (cur && stage == 0 && env_il > 0 && pending >= 4096 && pending < (1ll << 31)) {  // the caller's list (sorted by slot): strided walk
-        uint32_t k = 12;
-        while ((1ull << k) < (uint64_t)pending) ++k;
-        a.list_log2 = k;
-        a.list_mul = (uint32_t)(((1ull << k) / 128u) | 1u);   // odd: a bijection of [0, 2^k)
-      }
-    }
+    dense_order(a, cur, stage, pending, M, S, fast16 ? 16u : 32u);
     a.attempt = attempt; a.attempt_limit = limit; a.attempts_per_slot = 1;
     a.rejected = f->d_rej[buf];
     a.gal_acc = progress_rule ? f->d_galacc : nullptr;
@@ -715,23 +722,13 @@ static int sample_persistent(sf_flow* f, const float* x, int64_t M, int64_t S, c
     hipError_t e = sf_launch_inverse(m, a, st);
     if (e != hipSuccess) { f->ctab_x = nullptr; return hip_fail(e, "persistent sampler launch"); }
     if (stage == 0) SF_TRY_SET(hipEventRecord(f->ev_dense[1], st));
-    if (limit >= 1024u && rule_due(limit)) {  // drop the open slots of galaxies that made no progress (NaN rows), in place
-      SF_TRY_SET(sf_launch_filter_survivors(f->d_rej[buf], &f->d_queue->n_surv, (long)S, f->d_galacc, out, f->L.dev.D, st, a.out_f64));
-      SF_TRY_SET(hipMemsetAsync(f->d_galacc, 0, (size_t)M * sizeof(int32_t), st));
+    if (limit >= 1024u && rule_due(limit)) {
+      rc = drop_stalled(f, f->d_rej[buf], M, S, out, a.out_f64, st);
+      if (rc) return rc;
       acc_from = limit;
     }
-    SF_TRY_SET(hipMemcpyAsync(f->h_queue, f->d_queue, sizeof(SfQueue), hipMemcpyDeviceToHost, st));  // pinned
-    SF_TRY_SET(hipStreamSynchronize(st));
-    if (f->h_queue->error) {
-      f->ctab_x = nullptr;
-      return sf_fail(SF_ERR_STATE, "persistent sampler: work queue inconsistent (code " + std::to_string(f->h_queue->error) +
-                                    ": 1 = a device-side wait exceeded its bound, 2 = foreign ring entry, 3 = survivor "
-                                    "list overflow, 4 = listed slot outside M*S, 5 = claimed entry never arrived, 6/7 = "
-                                    "claim contention); head " + std::to_string(f->h_queue->head) + " reserve " +
-                                    std::to_string(f->h_queue->reserve) + " resolved " + std::to_string(f->h_queue->resolved) +
-                                    " of " + std::to_string((unsigned)pending) + " survivors " + std::to_string(f->h_queue->n_surv) +
-                                    " dense_next " + std::to_string(f->h_queue->dense_next));
-    }
+    rc = read_queue(f, pending, st);
+    if (rc) return rc;
     f->ring_dirty = false;  // clean end: every ring entry was consumed
     evals += (double)f->h_queue->evals;
     dropped += (int64_t)f->h_queue->dropped;
@@ -745,19 +742,7 @@ static int sample_persistent(sf_flow* f, const float* x, int64_t M, int64_t S, c
       a.qtrace = nullptr;
     }
 #endif
-    if (std::getenv("SF_Q_STATS")) {
-      const unsigned long long* q = f->h_queue->stats;
-      std::fprintf(stderr, "[sf_queue] stage %d: entry-barrier %.3e cyc, serial %.3e cyc, exit-barrier %.3e cyc, idle %.3e cyc in %llu "
-                   "episodes, %llu donations, iterations dense %llu tail %llu, entries %llu, evals %llu, resolved %u/%u\n", stage,
-                   (double)q[0], (double)q[1], (double)q[2], (double)q[3], q[4], q[5], q[6], q[7], q[8],
-                   (unsigned long long)f->h_queue->evals, f->h_queue->resolved, (unsigned)a.n_total);
-      std::fprintf(stderr, "[sf_queue]   max iterations of a workgroup %llu; last flow evaluation ended %.1f us, last exit %.1f us after the first start\n",
-                   q[11], ((double)q[12] - (double)q[10]) * 0.01, ((double)q[13] - (double)q[10]) * 0.01);
-      std::fprintf(stderr, "[sf_queue]   wave 0 of every workgroup, summed, dense mode (us): fetch %.0f, prologue %.0f, staging %.0f, passes %.0f, epilogue %.0f\n",
-                   (double)q[14] * 0.01, (double)q[15] * 0.01, (double)q[16] * 0.01, (double)q[17] * 0.01, (double)q[18] * 0.01);
-      std::fprintf(stderr, "[sf_queue]   the same in tail mode (us): fetch %.0f, prologue %.0f, staging %.0f, passes %.0f, epilogue %.0f\n",
-                   (double)q[19] * 0.01, (double)q[20] * 0.01, (double)q[21] * 0.01, (double)q[22] * 0.01, (double)q[23] * 0.01);
-    }
+    if (std::getenv("SF_Q_STATS")) print_queue_stats(*f->h_queue, stage, (unsigned)a.n_total);
     if (stage == 0) rej0 = (float)f->h_queue->rej0;
     pending = (int64_t)f->h_queue->n_surv;
     cur = f->d_rej[buf];
@@ -765,7 +750,7 @@ static int sample_persistent(sf_flow* f, const float* x, int64_t M, int64_t S, c
     ++stage;
     attempt = limit;
     if (pending < persist_min || attempt >= ceiling || out_of_time()) break;
-    limit = (attempt > ceiling / 16u) ? ceiling : attempt * 16u;
+    limit = next_window(attempt);
   }
   // ---- deep tail: the few slots that used up `limit` attempts (their galaxies accept less than ~1 draw in a
   // thousand).  One slot's attempts are now spread over the whole chip instead of over one workgroup: a FIND launch
@@ -776,7 +761,7 @@ static int sample_persistent(sf_flow* f, const float* x, int64_t M, int64_t S, c
     SF_TRY_SET(f->d_best.grow((size_t)pending));
     SfSampleArgsHost p = a;  // plain launches
     p.q = nullptr; p.ring = nullptr; p.gal_acc = nullptr; p.n_drawn = nullptr;
-    uint32_t window_end = attempt < 1024u ? 1024u : ((attempt > ceiling / 16u) ? ceiling : attempt * 16u);
+    uint32_t window_end = attempt < 1024u ? 1024u : next_window(attempt);
     if (window_end > ceiling) window_end = ceiling;
     while (pending > 0 && attempt < ceiling && !out_of_time()) {
       // as many new attempts per survivor as it has already failed (a slot that has failed n attempts needs ~n more on
@@ -803,14 +788,14 @@ static int sample_persistent(sf_flow* f, const float* x, int64_t M, int64_t S, c
       const bool window_done = attempt >= window_end || attempt >= ceiling;
       const bool look = window_done && rule_due(attempt);
       if (look) {
-        SF_TRY_SET(sf_launch_filter_survivors(f->d_rej[buf], &f->d_queue->n_surv, (long)S, f->d_galacc, out, f->L.dev.D, st, a.out_f64));
-        SF_TRY_SET(hipMemsetAsync(f->d_galacc, 0, (size_t)M * sizeof(int32_t), st));
+        rc = drop_stalled(f, f->d_rej[buf], M, S, out, a.out_f64, st);
+        if (rc) return rc;
         acc_from = attempt;
       }
-      SF_TRY_SET(hipMemcpyAsync(f->h_queue, f->d_queue, sizeof(SfQueue), hipMemcpyDeviceToHost, st));
-      SF_TRY_SET(hipStreamSynchronize(st));
+      rc = read_queue(f, pending, st);
+      if (rc) return rc;
       if (look) dropped += (int64_t)f->h_queue->dropped;
-      if (window_done) window_end = (window_end > ceiling / 16u) ? ceiling : window_end * 16u;
+      if (window_done) window_end = next_window(window_end);
       pending = (int64_t)f->h_queue->n_surv;
       cur = f->d_rej[buf];
       buf ^= 1;
@@ -828,6 +813,34 @@ static int sample_persistent(sf_flow* f, const float* x, int64_t M, int64_t S, c
   return SF_OK;
 }
 
+// Sampling on a sub-engine (sf_nsf1.hip / sf_nsfar.hip): the draws of the listed slots (null: all M * S), or -- count != null -- the
+// acceptance count of S attempts per row.  timed (sf_flow_sample): the launch between the handle's events, for sf_flow_sample_stats.
+static int sub_engine_sample(sf_flow* f, const float* x, int64_t M, int64_t S, const uint32_t* slots, int64_t n_slots, const float* lo,
+                             const float* hi, uint64_t seed, int32_t max_attempts, float* out, int32_t* n_drawn, int32_t* count,
+                             int64_t* n_unfilled, bool timed, hipStream_t st) {
+  uint32_t k0, k1;
+  seed_keys(seed, count ? 1u : 0u, k0, k1);
+  const unsigned long long off = slot_offset(f, S);
+  if (f->nsf1) {
+    if (count) return sf_nsf1_acceptance(f->nsf1, f->d_flat, x, (long)M, (long)S, lo, hi, k0, k1, off, count, st);
+    return sf_nsf1_sample(f->nsf1, f->d_flat, x, (long)M, (long)S, slots, (long)n_slots, lo, hi, k0, k1, off, max_attempts, out, n_drawn,
+                          n_unfilled, st);
+  }
+  if (!timed)
+    return sf_nsfar_sample(f->nsfar, x, (long)M, (long)S, slots, (long)n_slots, lo, hi, k0, k1, off, max_attempts, out, n_drawn, count,
+                           n_unfilled, st);
+  SF_TRY_SET(f->ev_dense[0].create()); SF_TRY_SET(f->ev_dense[1].create());
+  int64_t unf = 0;
+  int rc = sf_nsfar_sample(f->nsfar, x, (long)M, (long)S, slots, (long)n_slots, lo, hi, k0, k1, off, max_attempts, out, n_drawn, count, &unf,
+                           st, f->ev_dense[0], f->ev_dense[1]);
+  if (rc) return rc;
+  if (n_unfilled) *n_unfilled = unf;
+  float ms = 0.f;   // (the counters' read-back has synchronised the stream)
+  SF_TRY_SET(hipEventElapsedTime(&ms, f->ev_dense[0], f->ev_dense[1]));
+  f->last_stats[0] = ms; f->last_stats[1] = 1.f; f->last_stats[2] = (float)f->nsfar->last_rej0; f->last_stats[3] = (float)f->nsfar->last_evals;
+  return SF_OK;
+}
+
 int sf_flow_sample(sf_flow* f, const float* x, int64_t M, int64_t S, const float* lo, const float* hi,
                    uint64_t seed, int32_t max_attempts, float* out, int32_t* n_drawn, int64_t* n_unfilled,
                    void* stream) {
@@ -839,31 +852,9 @@ int sf_flow_sample(sf_flow* f, const float* x, int64_t M, int64_t S, const float
   if (M < 0 || S < 1) return sf_fail(SF_ERR_INVALID, "bad M or S");
   if ((lo == nullptr) != (hi == nullptr)) return sf_fail(SF_ERR_INVALID, "lo and hi must be given together");
   hipStream_t st = (hipStream_t)stream;
-  if (f->nsf1) {
+  if (f->nsf1 || f->nsfar) {
     if (n_drawn) SF_TRY_SET(sf_launch_fill_i32(n_drawn, (long)M, 0, st));
-    uint32_t k0, k1;
-    seed_keys(seed, 0u, k0, k1);
-    std::string err;
-    int rc = sf_nsf1_sample(f->nsf1, f->d_flat, x, (long)M, (long)S, nullptr, (long)(M * S), lo, hi, k0, k1,
-                            (unsigned long long)f->sample_row_offset * (unsigned long long)S, max_attempts, out, n_drawn, n_unfilled, st, err);
-    return rc ? sf_fail(rc, err) : SF_OK;
-  }
-  if (f->nsfar) {
-    if (n_drawn) SF_TRY_SET(sf_launch_fill_i32(n_drawn, (long)M, 0, st));
-    uint32_t k0, k1;
-    seed_keys(seed, 0u, k0, k1);
-    std::string err;
-    SF_TRY_SET(f->ev_dense[0].create()); SF_TRY_SET(f->ev_dense[1].create());
-    int64_t unf = 0;
-    int rc = sf_nsfar_sample(f->nsfar, x, (long)M, (long)S, nullptr, (long)(M * S), lo, hi, k0, k1,
-                             (unsigned long long)f->sample_row_offset * (unsigned long long)S, max_attempts, out, n_drawn, nullptr, &unf, st, err,
-                             f->ev_dense[0], f->ev_dense[1]);
-    if (rc) return sf_fail(rc, err);
-    if (n_unfilled) *n_unfilled = unf;
-    float ms = 0.f;   // (the counters' read-back has synchronised the stream)
-    SF_TRY_SET(hipEventElapsedTime(&ms, f->ev_dense[0], f->ev_dense[1]));
-    f->last_stats[0] = ms; f->last_stats[1] = 1.f; f->last_stats[2] = (float)f->nsfar->last_rej0; f->last_stats[3] = (float)f->nsfar->last_evals;
-    return SF_OK;
+    return sub_engine_sample(f, x, M, S, nullptr, M * S, lo, hi, seed, max_attempts, out, n_drawn, nullptr, n_unfilled, true, st);
   }
   if (n_drawn) SF_TRY_SET(sf_launch_fill_i32(n_drawn, (long)M, (int32_t)S, st));
   return sample_persistent(f, x, M, S, nullptr, M * S, lo, hi, seed, max_attempts, out, n_drawn, n_unfilled, st);
@@ -879,24 +870,9 @@ int sf_flow_sample_slots(sf_flow* f, const float* x, int64_t M, int64_t S, const
   if (!f->params_set) return sf_fail(SF_ERR_STATE, "sf_flow_set_params has not been called");
   if (M < 1 || S < 1 || n_slots < 0 || n_slots > M * S) return sf_fail(SF_ERR_INVALID, "bad M, S or n_slots");
   if ((lo == nullptr) != (hi == nullptr)) return sf_fail(SF_ERR_INVALID, "lo and hi must be given together");
-  if (f->nsf1) {
-    uint32_t k0, k1;
-    seed_keys(seed, 0u, k0, k1);
-    std::string err;
-    int rc = sf_nsf1_sample(f->nsf1, f->d_flat, x, (long)M, (long)S, slots, (long)n_slots, lo, hi, k0, k1,
-                            (unsigned long long)f->sample_row_offset * (unsigned long long)S, max_attempts, out, nullptr, n_unfilled,
-                            (hipStream_t)stream, err);
-    return rc ? sf_fail(rc, err) : SF_OK;
-  }
-  if (f->nsfar) {
-    uint32_t k0, k1;
-    seed_keys(seed, 0u, k0, k1);
-    std::string err;
-    int rc = sf_nsfar_sample(f->nsfar, x, (long)M, (long)S, slots, (long)n_slots, lo, hi, k0, k1,
-                             (unsigned long long)f->sample_row_offset * (unsigned long long)S, max_attempts, out, nullptr, nullptr, n_unfilled,
-                             (hipStream_t)stream, err);
-    return rc ? sf_fail(rc, err) : SF_OK;
-  }
+  if (f->nsf1 || f->nsfar)
+    return sub_engine_sample(f, x, M, S, slots, n_slots, lo, hi, seed, max_attempts, out, nullptr, nullptr, n_unfilled, false,
+                             (hipStream_t)stream);
   return sample_persistent(f, x, M, S, slots, n_slots, lo, hi, seed, max_attempts, out, nullptr, n_unfilled,
                            (hipStream_t)stream);
 }
@@ -915,30 +891,14 @@ int sf_flow_acceptance(sf_flow* f, const float* x, int64_t M, int64_t n, const f
   if ((uint64_t)(M * n) > 0xffffffffull) return sf_fail(SF_ERR_INVALID, "M*n must fit 32 bits");
   hipStream_t st = (hipStream_t)stream;
   SF_TRY_SET(sf_launch_fill_i32(count, (long)M, 0, st));
-  if (f->nsf1) {
-    uint32_t k0, k1;
-    seed_keys(seed, 1u, k0, k1);
-    std::string err;
-    int rc = sf_nsf1_acceptance(f->nsf1, f->d_flat, x, (long)M, (long)n, lo, hi, k0, k1,
-                                (unsigned long long)f->sample_row_offset * (unsigned long long)n, count, st, err);
-    return rc ? sf_fail(rc, err) : SF_OK;
-  }
-  if (f->nsfar) {
-    uint32_t k0, k1;
-    seed_keys(seed, 1u, k0, k1);
-    std::string err;
-    int rc = sf_nsfar_sample(f->nsfar, x, (long)M, (long)n, nullptr, (long)(M * n), lo, hi, k0, k1,
-                             (unsigned long long)f->sample_row_offset * (unsigned long long)n, 1, nullptr, nullptr, count, nullptr, st, err);
-    return rc ? sf_fail(rc, err) : SF_OK;
-  }
+  if (f->nsf1 || f->nsfar)   // (one attempt per slot)
+    return sub_engine_sample(f, x, M, n, nullptr, M * n, lo, hi, seed, 1, nullptr, nullptr, count, nullptr, false, st);
   SfSampleArgsHost a;
   a.x = x; a.S = (long)n; a.n_items = (long)(M * n); seed_keys(seed, 1u, a.k0, a.k1);
-  a.rng_slot_offset = (unsigned long long)f->sample_row_offset * (unsigned long long)n;
+  a.rng_slot_offset = slot_offset(f, n);
   a.lo = lo; a.hi = hi; a.count = count;
-  {
-    int rc = sf_flow_prepare_context(f, x, M, stream);
-    if (rc) return rc;
-  }
+  int rc = sf_flow_prepare_context(f, x, M, stream);
+  if (rc) return rc;
   const SfDev m = sampler_dev(f, x);
   f->ctab_x = nullptr;
   SF_TRY_SET(sf_launch_inverse(m, a, st));
@@ -948,26 +908,23 @@ int sf_flow_acceptance(sf_flow* f, const float* x, int64_t M, int64_t n, const f
 int sf_copy_to_host_f64(const float* dev_src, double* host_dst, int64_t n, void* stream) {
   if (n == 0) return SF_OK;
   if (!dev_src || !host_dst || n < 0) return sf_fail(SF_ERR_INVALID, "null argument or n < 0");
-  std::string err;
-  int rc = sf_hostio_copy_f64(dev_src, host_dst, n, (hipStream_t)stream, err);
-  return rc ? sf_fail(rc, err) : SF_OK;
+  return sf_hostio_copy_f64(dev_src, host_dst, n, (hipStream_t)stream);
 }
 
 // ---- training ------------------------------------------------------------------------------
-int sf_flow_loss_grad_weighted(sf_flow* f, const float* flat, const float* theta, const float* x, int64_t B,
-                               float grad_scale, const float* weights, float* loss, float* grad,
-                               float* dctx, void* stream) {
+// the one body behind sf_flow_loss_grad_weighted (no rows) and sf_flow_loss_grad_rows (need_rows: a batch must come with its rows)
+static int loss_grad(sf_flow* f, const float* flat, const float* theta, const float* x, const int64_t* rows, bool need_rows, int64_t B,
+                     float grad_scale, const float* weights, float* loss, double* loss_sum, float* grad, float* dctx, void* stream) {
   if (!f || !flat || !grad) return sf_fail(SF_ERR_INVALID, "null argument");
-  if (B > 0 && (!theta || !x)) return sf_fail(SF_ERR_INVALID, "null argument");
+  if (B > 0 && (!theta || !x || (need_rows && !rows))) return sf_fail(SF_ERR_INVALID, "null argument");
   if (B < 0) return sf_fail(SF_ERR_INVALID, "B < 0");
   int rc = ensure_device(f);
   if (rc) return rc;
-  std::string err;
-  rc = sf_train_loss_grad(f, flat, theta, x, nullptr, (long)B, grad_scale, weights, loss, nullptr, grad, dctx,
-                          (hipStream_t)stream, err);
+  rc = sf_train_loss_grad(f, flat, theta, x, reinterpret_cast<const long long*>(rows), (long)B, grad_scale, weights, loss, loss_sum, grad,
+                          dctx, (hipStream_t)stream);
   if (rc) {
     if (rc == SF_ERR_HIP) f->flat_valid = false;  // failed part-way: the forward image may already hold the caller's vector
-    return sf_fail(rc, err);
+    return rc;
   }
   f->params_set = true;  // the forward image now holds `flat`
   f->flat_valid = false; // ... but the handle's own copy of the logical vector does not
@@ -975,25 +932,16 @@ int sf_flow_loss_grad_weighted(sf_flow* f, const float* flat, const float* theta
   return SF_OK;
 }
 
+int sf_flow_loss_grad_weighted(sf_flow* f, const float* flat, const float* theta, const float* x, int64_t B,
+                               float grad_scale, const float* weights, float* loss, float* grad,
+                               float* dctx, void* stream) {
+  return loss_grad(f, flat, theta, x, nullptr, false, B, grad_scale, weights, loss, nullptr, grad, dctx, stream);
+}
+
 int sf_flow_loss_grad_rows(sf_flow* f, const float* flat, const float* theta, const float* x, const int64_t* rows,
                            int64_t B, float grad_scale, const float* weights, float* loss, double* loss_sum,
                            float* grad, float* dctx, void* stream) {
-  if (!f || !flat || !grad) return sf_fail(SF_ERR_INVALID, "null argument");
-  if (B > 0 && (!theta || !x || !rows)) return sf_fail(SF_ERR_INVALID, "null argument");
-  if (B < 0) return sf_fail(SF_ERR_INVALID, "B < 0");
-  int rc = ensure_device(f);
-  if (rc) return rc;
-  std::string err;
-  rc = sf_train_loss_grad(f, flat, theta, x, reinterpret_cast<const long long*>(rows), (long)B, grad_scale, weights, loss,
-                          loss_sum, grad, dctx, (hipStream_t)stream, err);
-  if (rc) {
-    if (rc == SF_ERR_HIP) f->flat_valid = false;  // (as above)
-    return sf_fail(rc, err);
-  }
-  f->params_set = true;
-  f->flat_valid = false;
-  f->ctab_x = nullptr;
-  return SF_OK;
+  return loss_grad(f, flat, theta, x, rows, true, B, grad_scale, weights, loss, loss_sum, grad, dctx, stream);
 }
 
 int sf_flow_train_epoch(sf_flow* f, float* flat, const float* theta, const float* x, const int64_t* order,

@@ -129,10 +129,10 @@ void wait_slot(int b) {
 
 }  // namespace
 
-int sf_hostio_copy_f64(const float* dev_src, double* host_dst, int64_t n, hipStream_t stream, std::string& err) {
+int sf_hostio_copy_f64(const float* dev_src, double* host_dst, int64_t n, hipStream_t stream) {
   std::lock_guard<std::mutex> call(g.call);
   int dev = 0;
-  SF_TRY_ERR(hipGetDevice(&dev));
+  SF_TRY_SET(hipGetDevice(&dev));
   const size_t pb = piece_bytes();
   if (g.device != dev || g.stage_bytes != pb) {   // first call (or another device / piece size): build the pipeline
     for (int b = 0; b < NBUF; ++b) {
@@ -148,11 +148,11 @@ int sf_hostio_copy_f64(const float* dev_src, double* host_dst, int64_t n, hipStr
     g.ev_src = nullptr;
     g.stage_bytes = 0;
     for (int b = 0; b < NBUF; ++b) {
-      SF_TRY_ERR(hipHostMalloc((void**)&g.stage[b], pb, hipHostMallocDefault));
-      SF_TRY_ERR(hipEventCreateWithFlags(&g.ev[b], hipEventDisableTiming));
+      SF_TRY_SET(hipHostMalloc((void**)&g.stage[b], pb, hipHostMallocDefault));
+      SF_TRY_SET(hipEventCreateWithFlags(&g.ev[b], hipEventDisableTiming));
     }
-    SF_TRY_ERR(hipStreamCreateWithFlags(&g.cs, hipStreamNonBlocking));
-    SF_TRY_ERR(hipEventCreateWithFlags(&g.ev_src, hipEventDisableTiming));
+    SF_TRY_SET(hipStreamCreateWithFlags(&g.cs, hipStreamNonBlocking));
+    SF_TRY_SET(hipEventCreateWithFlags(&g.ev_src, hipEventDisableTiming));
     g.device = dev;
     g.stage_bytes = pb;
   }
@@ -164,8 +164,8 @@ int sf_hostio_copy_f64(const float* dev_src, double* host_dst, int64_t n, hipStr
     g.workers = w;
   }
   // the draws were written on the caller's stream
-  SF_TRY_ERR(hipEventRecord(g.ev_src, stream));
-  SF_TRY_ERR(hipStreamWaitEvent(g.cs, g.ev_src, 0));
+  SF_TRY_SET(hipEventRecord(g.ev_src, stream));
+  SF_TRY_SET(hipStreamWaitEvent(g.cs, g.ev_src, 0));
   const size_t per = pb / sizeof(float);
   const int64_t n_pieces = (int64_t)(((size_t)n + per - 1) / per);
   auto issue = [&](int64_t k) -> hipError_t {
@@ -179,13 +179,13 @@ int sf_hostio_copy_f64(const float* dev_src, double* host_dst, int64_t n, hipStr
   int64_t issued = 0;
   for (; issued < n_pieces && issued < NBUF; ++issued) {
     hipError_t e = issue(issued);
-    if (e != hipSuccess) { err = std::string("hipMemcpyAsync(D2H piece): ") + hipGetErrorString(e); rc = SF_ERR_HIP; break; }
+    if (e != hipSuccess) { rc = sf_fail(SF_ERR_HIP, std::string("hipMemcpyAsync(D2H piece): ") + hipGetErrorString(e)); break; }
   }
   const int parts = g.workers;
   for (int64_t k = 0; rc == SF_OK && k < n_pieces; ++k) {
     const int b = (int)(k % NBUF);
     hipError_t e = hipEventSynchronize(g.ev[b]);
-    if (e != hipSuccess) { err = std::string("hipEventSynchronize(piece): ") + hipGetErrorString(e); rc = SF_ERR_HIP; break; }
+    if (e != hipSuccess) { rc = sf_fail(SF_ERR_HIP, std::string("hipEventSynchronize(piece): ") + hipGetErrorString(e)); break; }
     const size_t off = (size_t)k * per, cnt = (size_t)n - off < per ? (size_t)n - off : per;
     g.left[b].store(parts);
     for (int p = 0; p < parts; ++p) {
@@ -205,7 +205,7 @@ int sf_hostio_copy_f64(const float* dev_src, double* host_dst, int64_t n, hipStr
     if (k >= 1 && issued < n_pieces) {
       wait_slot((int)((k - 1) % NBUF));
       hipError_t e2 = issue(issued);
-      if (e2 != hipSuccess) { err = std::string("hipMemcpyAsync(D2H piece): ") + hipGetErrorString(e2); rc = SF_ERR_HIP; break; }
+      if (e2 != hipSuccess) { rc = sf_fail(SF_ERR_HIP, std::string("hipMemcpyAsync(D2H piece): ") + hipGetErrorString(e2)); break; }
       ++issued;
     }
   }

@@ -151,23 +151,14 @@ struct SfResidentCache {
 };
 void sf_set_error(const std::string& msg);          // thread-local message behind sf_last_error()
 int sf_fail(int code, const std::string& msg);      // sf_set_error(msg), then `code` for the caller to return
-// a HIP call that must succeed: on failure the message "<call>: <hip error>" and return SF_ERR_HIP.  _ERR writes the message
-// to the enclosing function's `std::string err` (helpers whose caller reports it), _SET makes it the thread's last error.
-// (An operation of an owner, sf_buf.h -- x.alloc(n), x.grow(n), x.upload(v), x.create() -- also names the runtime function that failed.)
+// a HIP call that must succeed: on failure the message "<call>: <hip error>" becomes the thread's last error and the enclosing
+// function returns SF_ERR_HIP.  (An operation of an owner, sf_buf.h -- x.alloc(n), x.grow(n), x.upload(v), x.create() -- also names the runtime function that failed.)
 inline std::string sf_hip_message(const char* call, hipError_t e) {
   std::string s = std::string(call) + ": ";
   for (const char* op : {".alloc(", ".grow(", ".upload(", ".create("})
     if (s.find(op) != std::string::npos) { s += std::string(sf_buf_last_call()) + ": "; break; }
   return s + hipGetErrorString(e);
 }
-#define SF_TRY_ERR(call)                                                     \
-  do {                                                                       \
-    hipError_t e_ = (call);                                                  \
-    if (e_ != hipSuccess) {                                                  \
-      err = sf_hip_message(#call, e_);                                       \
-      return SF_ERR_HIP;                                                     \
-    }                                                                        \
-  } while (0)
 #define SF_TRY_SET(call)                                                                                   \
   do {                                                                                                     \
     hipError_t e_ = (call);                                                                                \
@@ -181,7 +172,6 @@ int sf_comm_all_reduce_impl(sf_comm* c, float* buf, long n, hipStream_t st);  //
 // all or nothing, form a struct that the handle inherits (so that their names read as before): the builder fills a local one and
 // moves it in, and a group that has to grow is first assigned an empty one (free before malloc).
 #define SF_LOSS_PARTS 64
-#define SF_MAX_ROUNDS 80
 struct SfNsf1;
 struct SfFlowDev {   // ensure_device (sf_api.hip)
   SfBuf<float> d_packed;        // forward operand image
@@ -196,8 +186,6 @@ struct SfFlowDev {   // ensure_device (sf_api.hip)
   SfBuf<unsigned short> d_packedB;    // bf16 hidden operand image (hidden_bf16)
   SfBuf<int32_t> d_bsrc;
   SfBuf<float> d_flat;          // staging for host-sourced parameters
-  SfBuf<uint32_t> d_cnt;        // SF_MAX_ROUNDS rejected-slot counters (one per round of a sf_flow_sample call)
-  SfPinned<uint32_t> h_cnt;     // pinned host mirror for the per-round read-back
   SfEvent ev_dense[2];          // brackets round 0 of the last sf_flow_sample call
 };
 struct SfFlowTrain {   // the `train_ready` group (sf_train.hip)
@@ -281,4 +269,4 @@ struct sf_flow : SfFlowDev, SfFlowTrain, SfFlowTrainC, SfFlowGt, SfFlowRej {
 };
 
 // device fp32 -> host float64 hand-over (sf_hostio.hip)
-int sf_hostio_copy_f64(const float* dev_src, double* host_dst, int64_t n, hipStream_t stream, std::string& err);
+int sf_hostio_copy_f64(const float* dev_src, double* host_dst, int64_t n, hipStream_t stream);

@@ -5,6 +5,7 @@
 #include "sf_block.h"
 #include "sf_device.h"
 #include "sf_internal.h"
+#include "sf_pack.h"
 
 // ---------------------------------------------------------------------------------------------
 // small utility kernels
@@ -12,38 +13,20 @@
 __global__ void k_pack(const float* __restrict__ flat, const int32_t* __restrict__ s1,
                        const int32_t* __restrict__ s2, float* __restrict__ packed, long n) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const int a = s1[i], b = s2[i];
-  float v = 0.f;
-  if (a >= 0) v = flat[a];
-  if (b >= 0) v += flat[b];
-  else if (b == SF_PACK_TANH_SCALE) v *= SF_TANH_PRESCALE;
-  packed[i] = v;
+  if (i < n) packed[i] = sf_pack_f32(flat, s1[i], s2[i]);
 }
 
 __global__ void k_pack_bf16(const float* __restrict__ flat, const int32_t* __restrict__ src,
                             unsigned short* __restrict__ out, long n) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const int a = src[i];
-  const __bf16 v = (__bf16)(a >= 0 ? flat[a] : 0.f);  // round to nearest even
-  out[i] = __builtin_bit_cast(unsigned short, v);
+  if (i < n) out[i] = sf_pack_bf16(flat, src[i]);
 }
 
-// split-bf16 pack: src = logical index | (part << 30); part 0 -> hi = bf16(w) (round to nearest even), part 1 ->
-// lo = bf16(w - hi).  Two bf16 per 32-bit word of the image.
+// (two bf16 per 32-bit word of the image)
 __global__ void k_pack_bf16_split(const float* __restrict__ flat, const int32_t* __restrict__ src,
                                   unsigned short* __restrict__ out, long n) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const int a = src[i];
-  unsigned short r = 0;
-  if (a >= 0) {
-    const float w = flat[a & SF_PACK_SPLIT_INDEX] * ((a & SF_PACK_SPLIT_SCALED) ? SF_TANH_PRESCALE : 1.0f);
-    const __bf16 hi = (__bf16)w;
-    r = __builtin_bit_cast(unsigned short, (a >> 30) & 1 ? (__bf16)(w - (float)hi) : hi);
-  }
-  out[i] = r;
+  if (i < n) out[i] = sf_pack_bf16_split(flat, src[i]);
 }
 
 // exclusive scan of n counts by one workgroup: thread t owns the counts [t * chunk, (t + 1) * chunk)

@@ -23,15 +23,14 @@ struct SfNsf1 {
   SfBuf<unsigned int> d_cnt;
 };
 
-int sf_nsf1_create(const sf_flow_desc& d, SfNsf1** out, std::string& err);
+int sf_nsf1_create(const sf_flow_desc& d, SfNsf1** out);
 void sf_nsf1_destroy(SfNsf1* n);
-int sf_nsf1_log_prob(SfNsf1* n, const float* flat, const float* theta, const float* x, long B, float* out, hipStream_t st, std::string& err);
-int sf_nsf1_inverse(SfNsf1* n, const float* flat, const float* z, const float* x, long B, float* theta, float* logdet, hipStream_t st,
-                    std::string& err);
+int sf_nsf1_log_prob(SfNsf1* n, const float* flat, const float* theta, const float* x, long B, float* out, hipStream_t st);
+int sf_nsf1_inverse(SfNsf1* n, const float* flat, const float* z, const float* x, long B, float* theta, float* logdet, hipStream_t st);
 int sf_nsf1_loss_grad(SfNsf1* n, const float* flat, const float* theta, const float* x, const long long* idx, long B, float grad_scale,
-                      const float* weights, float* loss, double* loss_sum, float* grad, hipStream_t st, std::string& err);
+                      const float* weights, float* loss, double* loss_sum, float* grad, hipStream_t st);
 int sf_nsf1_sample(SfNsf1* n, const float* flat, const float* x, long M, long S, const uint32_t* slots, long n_slots, const float* lo,
                    const float* hi, uint32_t k0, uint32_t k1, unsigned long long slot_offset, int max_attempts, float* out,
-                   int32_t* n_drawn, int64_t* n_unfilled, hipStream_t st, std::string& err);
+                   int32_t* n_drawn, int64_t* n_unfilled, hipStream_t st);
 int sf_nsf1_acceptance(SfNsf1* n, const float* flat, const float* x, long M, long cnt, const float* lo, const float* hi, uint32_t k0,
-                       uint32_t k1, unsigned long long slot_offset, int32_t* count, hipStream_t st, std::string& err);
+                       uint32_t k1, unsigned long long slot_offset, int32_t* count, hipStream_t st);

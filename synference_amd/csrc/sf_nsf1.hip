@@ -208,14 +208,11 @@ Nsf1C consts_of(const SfNsf1& n) {
 #define N1_RC(call)                                                         \
   do {                                                                      \
     int rc_ = (call);                                                       \
-    if (rc_) {                                                              \
-      err = std::string(#call) + ": " + sf_last_error();                    \
-      return rc_;                                                           \
-    }                                                                       \
+    if (rc_) return sf_fail(rc_, std::string(#call) + ": " + sf_last_error()); \
   } while (0)
 
 // q[t][row][:] = MLP_t(x[row]) for every transform, with the parameters in `flat` (device)
-int conditioner(SfNsf1& n, const float* flat, const float* x, long rows, float* q, hipStream_t st, std::string& err) {
+int conditioner(SfNsf1& n, const float* flat, const float* x, long rows, float* q, hipStream_t st) {
   for (int t = 0; t < n.T; ++t)
     N1_RC(sf_mlp_forward(n.mlp, flat + (size_t)t * n.P_mlp, x, rows, q + (size_t)t * rows * n.NP, st));
   return SF_OK;
@@ -223,11 +220,11 @@ int conditioner(SfNsf1& n, const float* flat, const float* x, long rows, float* 
 
 }  // namespace
 
-int sf_nsf1_create(const sf_flow_desc& d, SfNsf1** out, std::string& err) {
-  if (d.T < 1 || d.T > SF_NSF1_TMAX) { err = "one-parameter NSF: T must be in 1.." + std::to_string(SF_NSF1_TMAX); return SF_ERR_INVALID; }
-  if (d.K < 2 || d.K > 16) { err = "K must be in 2..16"; return SF_ERR_INVALID; }
-  if (d.H < 1 || d.H > 128 || d.C < 1 || d.C > 512) { err = "H must be in 1..128, C in 1..512"; return SF_ERR_INVALID; }
-  if (!d.theta_mean || !d.theta_std || !d.x_mean || !d.x_std) { err = "z-score buffers must be given"; return SF_ERR_INVALID; }
+int sf_nsf1_create(const sf_flow_desc& d, SfNsf1** out) {
+  if (d.T < 1 || d.T > SF_NSF1_TMAX) return sf_fail(SF_ERR_INVALID, "one-parameter NSF: T must be in 1.." + std::to_string(SF_NSF1_TMAX));
+  if (d.K < 2 || d.K > 16) return sf_fail(SF_ERR_INVALID, "K must be in 2..16");
+  if (d.H < 1 || d.H > 128 || d.C < 1 || d.C > 512) return sf_fail(SF_ERR_INVALID, "H must be in 1..128, C in 1..512");
+  if (!d.theta_mean || !d.theta_std || !d.x_mean || !d.x_std) return sf_fail(SF_ERR_INVALID, "z-score buffers must be given");
   SfNsf1* n = new SfNsf1();
   n->T = d.T; n->C = d.C; n->H = d.H; n->K = d.K; n->NP = 3 * d.K - 1;
   n->tail_bound = d.tail_bound; n->min_w = d.min_bin_width; n->min_h = d.min_bin_height; n->min_d = d.min_derivative;
@@ -239,7 +236,7 @@ int sf_nsf1_create(const sf_flow_desc& d, SfNsf1** out, std::string& err) {
   md.n_in = d.C; md.n_layers = 3; md.widths[0] = d.H; md.widths[1] = d.H; md.widths[2] = n->NP; md.act = SF_ACT_RELU;
   md.x_mean = d.x_mean; md.x_std = d.x_std;
   int rc = sf_mlp_create(&md, &n->mlp);
-  if (rc) { err = sf_last_error(); delete n; return rc; }
+  if (rc) { delete n; return rc; }   // (sf_mlp_create has set the message)
   n->P_mlp = sf_mlp_num_params(n->mlp);
   *out = n;
   return SF_OK;
@@ -248,48 +245,46 @@ int sf_nsf1_create(const sf_flow_desc& d, SfNsf1** out, std::string& err) {
 SfNsf1::~SfNsf1() { sf_mlp_destroy(mlp); }
 void sf_nsf1_destroy(SfNsf1* n) { delete n; }
 
-int sf_nsf1_log_prob(SfNsf1* n, const float* flat, const float* theta, const float* x, long B, float* out, hipStream_t st,
-                     std::string& err) {
-  SF_TRY_ERR(n->d_q.grow((size_t)n->T * B * n->NP));
-  int rc = conditioner(*n, flat, x, B, n->d_q, st, err);
+int sf_nsf1_log_prob(SfNsf1* n, const float* flat, const float* theta, const float* x, long B, float* out, hipStream_t st) {
+  SF_TRY_SET(n->d_q.grow((size_t)n->T * B * n->NP));
+  int rc = conditioner(*n, flat, x, B, n->d_q, st);
   if (rc) return rc;
   hipLaunchKernelGGL(k_nsf1_logprob, dim3((unsigned)((B + 127) / 128)), dim3(128), 0, st, n->d_q, theta, B, consts_of(*n), out);
-  SF_TRY_ERR(hipGetLastError());
+  SF_TRY_SET(hipGetLastError());
   return SF_OK;
 }
 
 int sf_nsf1_inverse(SfNsf1* n, const float* flat, const float* z, const float* x, long B, float* theta, float* logdet,
-                    hipStream_t st, std::string& err) {
-  SF_TRY_ERR(n->d_q.grow((size_t)n->T * B * n->NP));
-  int rc = conditioner(*n, flat, x, B, n->d_q, st, err);
+                    hipStream_t st) {
+  SF_TRY_SET(n->d_q.grow((size_t)n->T * B * n->NP));
+  int rc = conditioner(*n, flat, x, B, n->d_q, st);
   if (rc) return rc;
   hipLaunchKernelGGL(k_nsf1_inverse, dim3((unsigned)((B + 127) / 128)), dim3(128), 0, st, n->d_q, z, B, consts_of(*n), theta, logdet);
-  SF_TRY_ERR(hipGetLastError());
+  SF_TRY_SET(hipGetLastError());
   return SF_OK;
 }
 
 int sf_nsf1_loss_grad(SfNsf1* n, const float* flat, const float* theta, const float* x, const long long* idx, long B,
-                      float grad_scale, const float* weights, float* loss, double* loss_sum, float* grad, hipStream_t st,
-                      std::string& err) {
+                      float grad_scale, const float* weights, float* loss, double* loss_sum, float* grad, hipStream_t st) {
   if (B == 0) {
-    SF_TRY_ERR(hipMemsetAsync(grad, 0, (size_t)n->T * n->P_mlp * sizeof(float), st));
+    SF_TRY_SET(hipMemsetAsync(grad, 0, (size_t)n->T * n->P_mlp * sizeof(float), st));
     return SF_OK;
   }
   int rc;
   if (idx) {  // the mini-batch gather (the MLP engine reads contiguous rows)
-    SF_TRY_ERR(n->d_xg.grow((size_t)B * n->C)); SF_TRY_ERR(n->d_thg.grow((size_t)B));
+    SF_TRY_SET(n->d_xg.grow((size_t)B * n->C)); SF_TRY_SET(n->d_thg.grow((size_t)B));
     const long tot = B * (n->C + 1);
     hipLaunchKernelGGL(k_nsf1_gather, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, theta, x, idx, B, n->C, n->d_thg, n->d_xg);
-    SF_TRY_ERR(hipGetLastError());
+    SF_TRY_SET(hipGetLastError());
     theta = n->d_thg;
     x = n->d_xg;
   }
-  SF_TRY_ERR(n->d_q.grow((size_t)n->T * B * n->NP)); SF_TRY_ERR(n->d_dq.grow((size_t)n->T * B * n->NP));
-  rc = conditioner(*n, flat, x, B, n->d_q, st, err);
+  SF_TRY_SET(n->d_q.grow((size_t)n->T * B * n->NP)); SF_TRY_SET(n->d_dq.grow((size_t)n->T * B * n->NP));
+  rc = conditioner(*n, flat, x, B, n->d_q, st);
   if (rc) return rc;
   hipLaunchKernelGGL(k_nsf1_train, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, n->d_q, theta, B, consts_of(*n), grad_scale, weights,
                      n->d_dq, loss, loss_sum);
-  SF_TRY_ERR(hipGetLastError());
+  SF_TRY_SET(hipGetLastError());
   for (int t = 0; t < n->T; ++t)
     N1_RC(sf_mlp_backward(n->mlp, flat + (size_t)t * n->P_mlp, x, n->d_dq + (size_t)t * B * n->NP, B, grad + (size_t)t * n->P_mlp, st));
   return SF_OK;
@@ -297,33 +292,33 @@ int sf_nsf1_loss_grad(SfNsf1* n, const float* flat, const float* theta, const fl
 
 int sf_nsf1_sample(SfNsf1* n, const float* flat, const float* x, long M, long S, const uint32_t* slots, long n_slots,
                    const float* lo, const float* hi, uint32_t k0, uint32_t k1, unsigned long long slot_offset, int max_attempts,
-                   float* out, int32_t* n_drawn, int64_t* n_unfilled, hipStream_t st, std::string& err) {
-  SF_TRY_ERR(n->d_q.grow((size_t)n->T * M * n->NP));
-  int rc = conditioner(*n, flat, x, M, n->d_q, st, err);
+                   float* out, int32_t* n_drawn, int64_t* n_unfilled, hipStream_t st) {
+  SF_TRY_SET(n->d_q.grow((size_t)n->T * M * n->NP));
+  int rc = conditioner(*n, flat, x, M, n->d_q, st);
   if (rc) return rc;
-  if (!n->d_cnt) SF_TRY_ERR(n->d_cnt.alloc(1));
-  SF_TRY_ERR(hipMemsetAsync(n->d_cnt, 0, sizeof(unsigned int), st));
+  if (!n->d_cnt) SF_TRY_SET(n->d_cnt.alloc(1));
+  SF_TRY_SET(hipMemsetAsync(n->d_cnt, 0, sizeof(unsigned int), st));
   // no ceiling asked for: 2^22 attempts per slot (the engine's other samplers give a galaxy up once 1e5 attempts of its open
   // slots brought no draw; a scalar slot that failed four million attempts is in the same state)
   const uint32_t cap = max_attempts > 0 ? (uint32_t)max_attempts : (1u << 22);
   hipLaunchKernelGGL(k_nsf1_sample, dim3((unsigned)((n_slots + 127) / 128)), dim3(128), 0, st, n->d_q, M, S, slots, n_slots, consts_of(*n),
                      lo, hi, k0, k1, slot_offset, cap, out, n_drawn, n->d_cnt);
-  SF_TRY_ERR(hipGetLastError());
+  SF_TRY_SET(hipGetLastError());
   unsigned int h = 0;
-  SF_TRY_ERR(hipMemcpyAsync(&h, n->d_cnt, sizeof(h), hipMemcpyDeviceToHost, st));
-  SF_TRY_ERR(hipStreamSynchronize(st));
+  SF_TRY_SET(hipMemcpyAsync(&h, n->d_cnt, sizeof(h), hipMemcpyDeviceToHost, st));
+  SF_TRY_SET(hipStreamSynchronize(st));
   if (n_unfilled) *n_unfilled = (int64_t)h;
   return SF_OK;
 }
 
 int sf_nsf1_acceptance(SfNsf1* n, const float* flat, const float* x, long M, long cnt, const float* lo, const float* hi, uint32_t k0,
-                       uint32_t k1, unsigned long long slot_offset, int32_t* count, hipStream_t st, std::string& err) {
-  SF_TRY_ERR(n->d_q.grow((size_t)n->T * M * n->NP));
-  int rc = conditioner(*n, flat, x, M, n->d_q, st, err);
+                       uint32_t k1, unsigned long long slot_offset, int32_t* count, hipStream_t st) {
+  SF_TRY_SET(n->d_q.grow((size_t)n->T * M * n->NP));
+  int rc = conditioner(*n, flat, x, M, n->d_q, st);
   if (rc) return rc;
   const long tot = M * cnt;
   hipLaunchKernelGGL(k_nsf1_accept, dim3((unsigned)((tot + 127) / 128)), dim3(128), 0, st, n->d_q, M, cnt, consts_of(*n), lo, hi, k0, k1,
                      slot_offset, count);
-  SF_TRY_ERR(hipGetLastError());
+  SF_TRY_SET(hipGetLastError());
   return SF_OK;
 }

@@ -45,17 +45,17 @@ struct SfNsfAr : SfNsfArDev, SfNsfArSurv {
   double last_evals = 0.0, last_rej0 = 0.0;   // of the last sampling call that read the counters back
 };
 
-int sf_nsfar_create(const sf_flow_desc& d, SfNsfAr** out, std::string& err);
+int sf_nsfar_create(const sf_flow_desc& d, SfNsfAr** out);
 void sf_nsfar_destroy(SfNsfAr* n);
 size_t sf_nsfar_lds_bytes(const SfNsfAr& n, int hidden_buffers, int waves = 1);
 // re-tiles the logical vector into the masked images (every entry point below reads the images of the LAST pack)
-int sf_nsfar_pack(SfNsfAr* n, const float* flat, hipStream_t st, std::string& err);
-int sf_nsfar_log_prob(SfNsfAr* n, const float* theta, const float* x, long B, float* out, hipStream_t st, std::string& err);
-int sf_nsfar_inverse(SfNsfAr* n, const float* z, const float* x, long B, float* theta, float* logdet, hipStream_t st, std::string& err);
+int sf_nsfar_pack(SfNsfAr* n, const float* flat, hipStream_t st);
+int sf_nsfar_log_prob(SfNsfAr* n, const float* theta, const float* x, long B, float* out, hipStream_t st);
+int sf_nsfar_inverse(SfNsfAr* n, const float* z, const float* x, long B, float* theta, float* logdet, hipStream_t st);
 // count != null: acceptance counting (one attempt per item, item i belongs to row i / S); else the rejection sampler
 int sf_nsfar_sample(SfNsfAr* n, const float* x, long M, long S, const uint32_t* slots, long n_slots, const float* lo, const float* hi,
                     uint32_t k0, uint32_t k1, unsigned long long slot_offset, int max_attempts, float* out, int32_t* n_drawn,
-                    int32_t* count, int64_t* n_unfilled, hipStream_t st, std::string& err, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+                    int32_t* count, int64_t* n_unfilled, hipStream_t st, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 // One sampling call as all six sampler kernels take it (sf_ar_sampler.h: the control flow; sf_nsfar.hip / sf_nsfar16.hip: the candidate routines and kernels).
 // cursor = d_ctr: [0] work cursor, [2] evaluations, [3] first attempts rejected.
 struct SfArLaunch {
@@ -75,5 +75,5 @@ hipError_t sf_nsfar16_launch(const SfNsfAr& n, const SfArLaunch& L, int cus, hip
 hipError_t sf_nsfar16_find(const SfNsfAr& n, const SfArLaunch& L, const SfArRound& R, hipStream_t st);
 hipError_t sf_nsfar16_resolve(const SfNsfAr& n, const SfArLaunch& L, const SfArRound& R, hipStream_t st);
 int sf_nsfar_loss_grad(SfNsfAr* n, const float* flat, const float* theta, const float* x, const long long* idx, long B, float grad_scale,
-                       const float* weights, float* loss, double* loss_sum, float* grad, hipStream_t st, std::string& err, hipEvent_t ev0 = nullptr,
+                       const float* weights, float* loss, double* loss_sum, float* grad, hipStream_t st, hipEvent_t ev0 = nullptr,
                        hipEvent_t ev1 = nullptr);

@@ -809,15 +809,15 @@ hipError_t set_lds(Kern k, size_t bytes) {
 
 }  // namespace
 
-int sf_nsfar_create(const sf_flow_desc& d, SfNsfAr** out, std::string& err) {
-  if (d.D < 1 || d.D > 16) { err = "autoregressive NSF: D must be in 1..16"; return SF_ERR_INVALID; }
+int sf_nsfar_create(const sf_flow_desc& d, SfNsfAr** out) {
+  if (d.D < 1 || d.D > 16) return sf_fail(SF_ERR_INVALID, "autoregressive NSF: D must be in 1..16");
   const bool affine = d.kind == SF_MAF_AR;
-  if (!affine && (d.K < 2 || d.K > ARK)) { err = "autoregressive NSF: K (bins) must be in 2..8"; return SF_ERR_INVALID; }
-  if (d.NB != 2) { err = "autoregressive NSF: two hidden layers (NB = 2: lampe / ltu-ili's hyper-network) are built"; return SF_ERR_INVALID; }
-  if (d.H < d.D || d.H > 192) { err = "autoregressive NSF: H must be in D..192"; return SF_ERR_INVALID; }
-  if (d.C < 1 || d.C > 256 || d.T < 1 || d.T > 64) { err = "autoregressive NSF: C in 1..256, T in 1..64"; return SF_ERR_INVALID; }
-  if (!d.theta_mean || !d.theta_std || !d.x_mean || !d.x_std) { err = "z-score buffers must be given"; return SF_ERR_INVALID; }
-  if (!(d.ar_slope > 0.f && d.ar_slope < 1.f)) { err = "ar_slope must be in (0, 1)"; return SF_ERR_INVALID; }
+  if (!affine && (d.K < 2 || d.K > ARK)) return sf_fail(SF_ERR_INVALID, "autoregressive NSF: K (bins) must be in 2..8");
+  if (d.NB != 2) return sf_fail(SF_ERR_INVALID, "autoregressive NSF: two hidden layers (NB = 2: lampe / ltu-ili's hyper-network) are built");
+  if (d.H < d.D || d.H > 192) return sf_fail(SF_ERR_INVALID, "autoregressive NSF: H must be in D..192");
+  if (d.C < 1 || d.C > 256 || d.T < 1 || d.T > 64) return sf_fail(SF_ERR_INVALID, "autoregressive NSF: C in 1..256, T in 1..64");
+  if (!d.theta_mean || !d.theta_std || !d.x_mean || !d.x_std) return sf_fail(SF_ERR_INVALID, "z-score buffers must be given");
+  if (!(d.ar_slope > 0.f && d.ar_slope < 1.f)) return sf_fail(SF_ERR_INVALID, "ar_slope must be in (0, 1)");
   SfNsfAr* n = new SfNsfAr();
   // (affine = zuko MAF: two parameters per dimension, carried in slots 0 and 1 of family 0 -- "K = 2, widths only")
   const int D = d.D, C = d.C, H = d.H, T = d.T, K = affine ? 2 : d.K, NP = affine ? 2 : 3 * K - 1;
@@ -886,9 +886,8 @@ int sf_nsfar_create(const sf_flow_desc& d, SfNsfAr** out, std::string& err) {
   }
   n->t_stride = (o + 63) / 64 * 64;
   if (std::max(sf_nsfar_lds_bytes(*n, 3, 1), sf_nsfar_lds_bytes(*n, 2, 1)) > (size_t)160 * 1024 - 1024) {
-    err = "autoregressive NSF: (3 D + C + 2 Hp + 32) x 260 bytes of LDS per wave (training: 24 head rows + 16 Hp bytes of tables) exceed the 160 KB of a CU (Hp = H with every type padded to a multiple of 8, in all a multiple of 16)";
     delete n;
-    return SF_ERR_INVALID;
+    return sf_fail(SF_ERR_INVALID, "autoregressive NSF: (3 D + C + 2 Hp + 32) x 260 bytes of LDS per wave (training: 24 head rows + 16 Hp bytes of tables) exceed the 160 KB of a CU (Hp = H with every type padded to a multiple of 8, in all a multiple of 16)");
   }
   n->src.assign((size_t)T * n->t_stride, -1);
   n->ord.assign((size_t)T * D, 0); n->dimof.assign((size_t)T * D, 0); n->dwave.assign((size_t)T * D, 0);
@@ -996,29 +995,29 @@ int sf_nsfar_create(const sf_flow_desc& d, SfNsfAr** out, std::string& err) {
 
 void sf_nsfar_destroy(SfNsfAr* n) { delete n; }
 
-static int ar_ensure(SfNsfAr* n, std::string& err) {
+static int ar_ensure(SfNsfAr* n) {
   if (n->dev_ready) return SF_OK;
   SfNsfArDev d;   // all or nothing
-  SF_TRY_ERR(d.d_img.alloc(n->src.size()));
-  SF_TRY_ERR(d.d_src.upload(n->src)); SF_TRY_ERR(d.d_perm.upload(n->perm)); SF_TRY_ERR(d.d_ptype.upload(n->ptype)); SF_TRY_ERR(d.d_tend.upload(n->tend));
-  SF_TRY_ERR(d.d_ord.upload(n->ord)); SF_TRY_ERR(d.d_dimof.upload(n->dimof)); SF_TRY_ERR(d.d_dwave.upload(n->dwave)); SF_TRY_ERR(d.d_xmean.upload(n->h_xmean)); SF_TRY_ERR(d.d_xstd.upload(n->h_xstd));
+  SF_TRY_SET(d.d_img.alloc(n->src.size()));
+  SF_TRY_SET(d.d_src.upload(n->src)); SF_TRY_SET(d.d_perm.upload(n->perm)); SF_TRY_SET(d.d_ptype.upload(n->ptype)); SF_TRY_SET(d.d_tend.upload(n->tend));
+  SF_TRY_SET(d.d_ord.upload(n->ord)); SF_TRY_SET(d.d_dimof.upload(n->dimof)); SF_TRY_SET(d.d_dwave.upload(n->dwave)); SF_TRY_SET(d.d_xmean.upload(n->h_xmean)); SF_TRY_SET(d.d_xstd.upload(n->h_xstd));
   {   // live[i] = 1 where logical parameter i appears in an image (an unmasked weight or a bias): the entries a training workgroup writes
     std::vector<unsigned char> live((size_t)n->n_params, 0);
     for (int32_t v : n->src)
       if (v >= 0) live[(size_t)v] = 1;
-    SF_TRY_ERR(d.d_live.upload(live));
+    SF_TRY_SET(d.d_live.upload(live));
   }
-  SF_TRY_ERR(d.d_ctr.alloc(8));
-  SF_TRY_ERR(d.h_ctr.alloc(8));   // [0] cursor [1] unfilled [2] evaluations [3] rejected first attempts [4], [5] survivor counts
+  SF_TRY_SET(d.d_ctr.alloc(8));
+  SF_TRY_SET(d.h_ctr.alloc(8));   // [0] cursor [1] unfilled [2] evaluations [3] rejected first attempts [4], [5] survivor counts
   {
     const std::vector<int32_t> none(n->src.size(), -1);
-    SF_TRY_ERR(d.d_none.upload(none));
+    SF_TRY_SET(d.d_none.upload(none));
   }
   const size_t lds = (size_t)160 * 1024 - 1024;   // (k_ar_sample also has 768 static bytes)
-  SF_TRY_ERR(set_lds(k_ar_logprob<1>, lds)); SF_TRY_ERR(set_lds(k_ar_logprob<4>, lds)); SF_TRY_ERR(set_lds(k_ar_inverse, lds)); SF_TRY_ERR(set_lds(k_ar_sample, lds));
-  SF_TRY_ERR(set_lds(k_ar_train<1, false>, lds)); SF_TRY_ERR(set_lds(k_ar_train<4, false>, lds));
-  SF_TRY_ERR(set_lds(k_ar_train<1, true>, lds)); SF_TRY_ERR(set_lds(k_ar_train<4, true>, lds));
-  SF_TRY_ERR(set_lds(k_ar_find, lds)); SF_TRY_ERR(set_lds(k_ar_resolve, lds));
+  SF_TRY_SET(set_lds(k_ar_logprob<1>, lds)); SF_TRY_SET(set_lds(k_ar_logprob<4>, lds)); SF_TRY_SET(set_lds(k_ar_inverse, lds)); SF_TRY_SET(set_lds(k_ar_sample, lds));
+  SF_TRY_SET(set_lds(k_ar_train<1, false>, lds)); SF_TRY_SET(set_lds(k_ar_train<4, false>, lds));
+  SF_TRY_SET(set_lds(k_ar_train<1, true>, lds)); SF_TRY_SET(set_lds(k_ar_train<4, true>, lds));
+  SF_TRY_SET(set_lds(k_ar_find, lds)); SF_TRY_SET(set_lds(k_ar_resolve, lds));
   static_cast<SfNsfArDev&>(*n) = std::move(d);
   n->dev_ready = true;
   return SF_OK;
@@ -1037,29 +1036,29 @@ static int ar_waves(const SfNsfAr& n, int hidden_buffers) {
   return sf_nsfar_lds_bytes(n, hidden_buffers, 4) <= (size_t)160 * 1024 - 1024 ? 4 : 1;
 }
 
-int sf_nsfar_pack(SfNsfAr* n, const float* flat, hipStream_t st, std::string& err) {
-  int rc = ar_ensure(n, err);
+int sf_nsfar_pack(SfNsfAr* n, const float* flat, hipStream_t st) {
+  int rc = ar_ensure(n);
   if (rc) return rc;
   // (k_pack sums two gather tables; the second is "none" everywhere)
-  SF_TRY_ERR(sf_launch_pack(flat, n->d_src, n->d_none, n->d_img, (long)n->src.size(), st));
+  SF_TRY_SET(sf_launch_pack(flat, n->d_src, n->d_none, n->d_img, (long)n->src.size(), st));
   return SF_OK;
 }
 
-int sf_nsfar_log_prob(SfNsfAr* n, const float* theta, const float* x, long B, float* out, hipStream_t st, std::string& err) {
+int sf_nsfar_log_prob(SfNsfAr* n, const float* theta, const float* x, long B, float* out, hipStream_t st) {
 #ifdef SF_AR_TRACE
   {
     static unsigned long long* d_tr = nullptr;
-    if (!d_tr) SF_TRY_ERR(hipMalloc(&d_tr, 256 * 8));
-    SF_TRY_ERR(hipMemsetAsync(d_tr, 0, 256 * 8, st));
+    if (!d_tr) SF_TRY_SET(hipMalloc(&d_tr, 256 * 8));
+    SF_TRY_SET(hipMemsetAsync(d_tr, 0, 256 * 8, st));
     ArArgs aa = args_of(*n);
     aa.trace = d_tr;
     if (ar_waves(*n, 2) == 4)
       hipLaunchKernelGGL(k_ar_logprob<4>, dim3((unsigned)((B + 63) / 64)), dim3(256), sf_nsfar_lds_bytes(*n, 2, 4), st, aa, theta, x, B, out);
     else
       hipLaunchKernelGGL(k_ar_logprob<1>, dim3((unsigned)((B + 63) / 64)), dim3(64), sf_nsfar_lds_bytes(*n, 2, 1), st, aa, theta, x, B, out);
-    SF_TRY_ERR(hipStreamSynchronize(st));
+    SF_TRY_SET(hipStreamSynchronize(st));
     unsigned long long h[256];
-    SF_TRY_ERR(hipMemcpy(h, d_tr, sizeof(h), hipMemcpyDeviceToHost));
+    SF_TRY_SET(hipMemcpy(h, d_tr, sizeof(h), hipMemcpyDeviceToHost));
     static int calls = 0;
     if (++calls % 8 == 0) {
       fprintf(stderr, "[nsfar trace] B=%ld (units of 100 cycles since stamp 0):", B);
@@ -1073,13 +1072,13 @@ int sf_nsfar_log_prob(SfNsfAr* n, const float* theta, const float* x, long B, fl
     hipLaunchKernelGGL(k_ar_logprob<4>, dim3((unsigned)((B + 63) / 64)), dim3(256), sf_nsfar_lds_bytes(*n, 2, 4), st, args_of(*n), theta, x, B, out);
   else
     hipLaunchKernelGGL(k_ar_logprob<1>, dim3((unsigned)((B + 63) / 64)), dim3(64), sf_nsfar_lds_bytes(*n, 2, 1), st, args_of(*n), theta, x, B, out);
-  SF_TRY_ERR(hipGetLastError());
+  SF_TRY_SET(hipGetLastError());
   return SF_OK;
 }
 
-int sf_nsfar_inverse(SfNsfAr* n, const float* z, const float* x, long B, float* theta, float* logdet, hipStream_t st, std::string& err) {
+int sf_nsfar_inverse(SfNsfAr* n, const float* z, const float* x, long B, float* theta, float* logdet, hipStream_t st) {
   hipLaunchKernelGGL(k_ar_inverse, dim3((unsigned)((B + 63) / 64)), dim3(64), sf_nsfar_lds_bytes(*n, 2, 1), st, args_of(*n), z, x, B, theta, logdet);
-  SF_TRY_ERR(hipGetLastError());
+  SF_TRY_SET(hipGetLastError());
   return SF_OK;
 }
 
@@ -1113,17 +1112,17 @@ static hipError_t ar_launch_resolve(const SfNsfAr& n, const SfArLaunch& L, const
 
 int sf_nsfar_sample(SfNsfAr* n, const float* x, long M, long S, const uint32_t* slots, long n_slots, const float* lo, const float* hi,
                     uint32_t k0, uint32_t k1, unsigned long long slot_offset, int max_attempts, float* out, int32_t* n_drawn,
-                    int32_t* count, int64_t* n_unfilled, hipStream_t st, std::string& err, hipEvent_t ev0, hipEvent_t ev1) {
-  SF_TRY_ERR(hipMemsetAsync(n->d_ctr, 0, 8 * sizeof(unsigned long long), st));
+                    int32_t* count, int64_t* n_unfilled, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
+  SF_TRY_SET(hipMemsetAsync(n->d_ctr, 0, 8 * sizeof(unsigned long long), st));
   // no ceiling asked for: the row-level progress rule of the kernel, and 2^20 attempts per slot at the very most
   const uint32_t cap = count ? 1u : (max_attempts > 0 ? (uint32_t)max_attempts : (1u << 20));
   int32_t* g_try = nullptr;
   if (!count && max_attempts <= 0 && lo) {
-    SF_TRY_ERR(n->d_gal.grow((size_t)(2 * M)));
-    SF_TRY_ERR(hipMemsetAsync(n->d_gal, 0, (size_t)(2 * M) * sizeof(int32_t), st));
+    SF_TRY_SET(n->d_gal.grow((size_t)(2 * M)));
+    SF_TRY_SET(hipMemsetAsync(n->d_gal, 0, (size_t)(2 * M) * sizeof(int32_t), st));
     g_try = n->d_gal;
   }
-  if (ev0) SF_TRY_ERR(hipEventRecord(ev0, st));
+  if (ev0) SF_TRY_SET(hipEventRecord(ev0, st));
   unsigned long long walk_R = 0, walk_C = 0;
   if (!count && n_slots >= 4096) {
     if (!slots && M > 1 && (long)(M * S) == n_slots) { walk_R = (unsigned long long)M; walk_C = (unsigned long long)S; }
@@ -1142,25 +1141,25 @@ int sf_nsfar_sample(SfNsfAr* n, const float* x, long M, long S, const uint32_t* 
     if ((size_t)n_slots > n->d_best.cap()) {   // all three or none: release, build, move in
       static_cast<SfNsfArSurv&>(*n) = SfNsfArSurv();
       SfNsfArSurv v;
-      SF_TRY_ERR(v.d_surv[0].alloc((size_t)n_slots));
-      SF_TRY_ERR(v.d_surv[1].alloc((size_t)n_slots));
-      SF_TRY_ERR(v.d_best.alloc((size_t)n_slots));
+      SF_TRY_SET(v.d_surv[0].alloc((size_t)n_slots));
+      SF_TRY_SET(v.d_surv[1].alloc((size_t)n_slots));
+      SF_TRY_SET(v.d_best.alloc((size_t)n_slots));
       static_cast<SfNsfArSurv&>(*n) = std::move(v);
     }
   }
   unsigned int* d_ns = reinterpret_cast<unsigned int*>(n->d_ctr + 4);   // [0], [1]: survivor counts of the two lists
   const SfArLaunch L = {x, S, slots, n_slots, lo, hi, k0, k1, slot_offset, cap, out, n_drawn, count, n->d_ctr,
                         reinterpret_cast<unsigned int*>(n->d_ctr + 1), g_try, g_try ? g_try + M : nullptr, walk_R, walk_C, window, n->d_surv[0], d_ns};
-  SF_TRY_ERR(ar_launch_persistent(*n, L, st));
-  if (ev1) SF_TRY_ERR(hipEventRecord(ev1, st));
+  SF_TRY_SET(ar_launch_persistent(*n, L, st));
+  if (ev1) SF_TRY_SET(hipEventRecord(ev1, st));
   unsigned long long* h = n->h_ctr;   // (pinned: a read-back into pageable memory is a staged, host-synchronous copy)
   for (int i = 0; i < 8; ++i) h[i] = 0;
   if (rounds) {
     int cur = 0;
     uint32_t base = window;
     for (;;) {
-      SF_TRY_ERR(hipMemcpyAsync(h, n->d_ctr, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-      SF_TRY_ERR(hipStreamSynchronize(st));
+      SF_TRY_SET(hipMemcpyAsync(h, n->d_ctr, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+      SF_TRY_SET(hipStreamSynchronize(st));
       const unsigned int ns = reinterpret_cast<const unsigned int*>(h + 4)[cur];
       if (ns == 0 || base >= cap) break;
       uint32_t A = 64;
@@ -1168,26 +1167,26 @@ int sf_nsfar_sample(SfNsfAr* n, const float* x, long M, long S, const uint32_t* 
       if ((uint64_t)base + A > cap) A = (uint32_t)(((uint64_t)cap - base + 63u) / 64u * 64u);
       const uint32_t att_end = (uint64_t)base + A > cap ? cap : base + A;
       const SfArRound R = {n->d_surv[cur], ns, n->d_best, base, A / 64u, att_end, n->d_surv[cur ^ 1], d_ns + (cur ^ 1)};   // (64 attempts per find workgroup)
-      SF_TRY_ERR(hipMemsetAsync(n->d_best, 0xff, (size_t)ns * sizeof(uint32_t), st));
-      SF_TRY_ERR(hipMemsetAsync(d_ns + (cur ^ 1), 0, sizeof(unsigned int), st));
-      SF_TRY_ERR(ar_launch_find(*n, L, R, st));
-      SF_TRY_ERR(ar_launch_resolve(*n, L, R, st));
+      SF_TRY_SET(hipMemsetAsync(n->d_best, 0xff, (size_t)ns * sizeof(uint32_t), st));
+      SF_TRY_SET(hipMemsetAsync(d_ns + (cur ^ 1), 0, sizeof(unsigned int), st));
+      SF_TRY_SET(ar_launch_find(*n, L, R, st));
+      SF_TRY_SET(ar_launch_resolve(*n, L, R, st));
       base = att_end;
       cur ^= 1;
     }
     const unsigned int left = reinterpret_cast<const unsigned int*>(h + 4)[cur];
     if (left > 0) {   // (the ceiling was reached with slots still open: NaN rows)
-      SF_TRY_ERR(hipMemsetAsync(n->d_best, 0xff, (size_t)left * sizeof(uint32_t), st));
+      SF_TRY_SET(hipMemsetAsync(n->d_best, 0xff, (size_t)left * sizeof(uint32_t), st));
       SfArLaunch Lf = L;
       Lf.g_try = nullptr; Lf.g_acc = nullptr;
       const SfArRound R = {n->d_surv[cur], left, n->d_best, cap, 0u, cap, n->d_surv[cur ^ 1], d_ns + (cur ^ 1)};   // (nothing tried: write-off only)
-      SF_TRY_ERR(ar_launch_resolve(*n, Lf, R, st));
+      SF_TRY_SET(ar_launch_resolve(*n, Lf, R, st));
     }
-    SF_TRY_ERR(hipMemcpyAsync(h, n->d_ctr, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    SF_TRY_ERR(hipStreamSynchronize(st));
+    SF_TRY_SET(hipMemcpyAsync(h, n->d_ctr, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    SF_TRY_SET(hipStreamSynchronize(st));
   } else if (n_unfilled) {
-    SF_TRY_ERR(hipMemcpyAsync(h, n->d_ctr, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    SF_TRY_ERR(hipStreamSynchronize(st));
+    SF_TRY_SET(hipMemcpyAsync(h, n->d_ctr, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    SF_TRY_SET(hipStreamSynchronize(st));
   }
   if (n_unfilled) *n_unfilled = (int64_t)(unsigned int)h[1];
   n->last_evals = (double)h[2];
@@ -1196,16 +1195,16 @@ int sf_nsfar_sample(SfNsfAr* n, const float* x, long M, long S, const uint32_t* 
 }
 
 int sf_nsfar_loss_grad(SfNsfAr* n, const float* flat, const float* theta, const float* x, const long long* idx, long B, float grad_scale,
-                       const float* weights, float* loss, double* loss_sum, float* grad, hipStream_t st, std::string& err, hipEvent_t ev0,
+                       const float* weights, float* loss, double* loss_sum, float* grad, hipStream_t st, hipEvent_t ev0,
                        hipEvent_t ev1) {
-  int rc = sf_nsfar_pack(n, flat, st, err);
+  int rc = sf_nsfar_pack(n, flat, st);
   if (rc) return rc;
   if (B == 0) {
-    SF_TRY_ERR(hipMemsetAsync(grad, 0, (size_t)n->n_params * sizeof(float), st));
+    SF_TRY_SET(hipMemsetAsync(grad, 0, (size_t)n->n_params * sizeof(float), st));
     return SF_OK;
   }
   const size_t need = (size_t)B * n->T * n->D;
-  SF_TRY_ERR(n->d_ustash.grow(need));
+  SF_TRY_SET(n->d_ustash.grow(need));
   // Gradient accumulation: one partial per 64-row chunk + k_ar_gather (plain stores, summed in chunk order) while the partials fit
   // 512 MiB -- cfg1 shape: up to 2 300 chunks = 147 000 rows; 16 384 rows: 0.57 -> 0.36 ms, 131 072 rows: 3.0 -> 1.6 ms -- else f32
   // atomics into the one gradient (SF_AR_GRAD=atomic forces them).  Measured and dropped: 2 x CUs persistent workgroups that own a
@@ -1218,20 +1217,20 @@ int sf_nsfar_loss_grad(SfNsfAr* n, const float* flat, const float* theta, const 
   const bool part = force != 1 && part_bytes <= ((size_t)512 << 20);
   const long nwg = n_chunks;
   if (part) {
-    SF_TRY_ERR(n->d_gpart.grow(part_bytes / sizeof(float)));
+    SF_TRY_SET(n->d_gpart.grow(part_bytes / sizeof(float)));
   } else {
-    SF_TRY_ERR(hipMemsetAsync(grad, 0, (size_t)n->n_params * sizeof(float), st));
+    SF_TRY_SET(hipMemsetAsync(grad, 0, (size_t)n->n_params * sizeof(float), st));
   }
   float* gdst = part ? n->d_gpart : grad;
   const long gstride = part ? (long)n->n_params : 0;
   ArArgs aa = args_of(*n);
 #ifdef SF_AR_TRACE
   static unsigned long long* d_tr = nullptr;
-  if (!d_tr) SF_TRY_ERR(hipMalloc(&d_tr, 256 * 8));
-  SF_TRY_ERR(hipMemsetAsync(d_tr, 0, 256 * 8, st));
+  if (!d_tr) SF_TRY_SET(hipMalloc(&d_tr, 256 * 8));
+  SF_TRY_SET(hipMemsetAsync(d_tr, 0, 256 * 8, st));
   aa.trace = d_tr;
 #endif
-  if (ev0) SF_TRY_ERR(hipEventRecord(ev0, st));
+  if (ev0) SF_TRY_SET(hipEventRecord(ev0, st));
   const int nwv = ar_waves(*n, 3);
   const dim3 grid((unsigned)nwg), block(64 * nwv);
   const size_t lds = sf_nsfar_lds_bytes(*n, 3, nwv);
@@ -1242,17 +1241,17 @@ int sf_nsfar_loss_grad(SfNsfAr* n, const float* flat, const float* theta, const 
     if (part) hipLaunchKernelGGL((k_ar_train<1, true>), grid, block, lds, st, aa, theta, x, idx, B, grad_scale, weights, loss, loss_sum, gdst, gstride, n->d_ustash);
     else hipLaunchKernelGGL((k_ar_train<1, false>), grid, block, lds, st, aa, theta, x, idx, B, grad_scale, weights, loss, loss_sum, gdst, gstride, n->d_ustash);
   }
-  SF_TRY_ERR(hipGetLastError());
-  if (ev1) SF_TRY_ERR(hipEventRecord(ev1, st));
+  SF_TRY_SET(hipGetLastError());
+  if (ev1) SF_TRY_SET(hipEventRecord(ev1, st));
   if (part) {
     hipLaunchKernelGGL(k_ar_gather, dim3((unsigned)((n->n_params + 255) / 256)), dim3(256), 0, st, n->d_gpart, gstride, (int)nwg, n->d_live, grad, (long)n->n_params);
-    SF_TRY_ERR(hipGetLastError());
+    SF_TRY_SET(hipGetLastError());
   }
 #ifdef SF_AR_TRACE
   {
-    SF_TRY_ERR(hipStreamSynchronize(st));
+    SF_TRY_SET(hipStreamSynchronize(st));
     unsigned long long h[256];
-    SF_TRY_ERR(hipMemcpy(h, d_tr, sizeof(h), hipMemcpyDeviceToHost));
+    SF_TRY_SET(hipMemcpy(h, d_tr, sizeof(h), hipMemcpyDeviceToHost));
     static int calls = 0;
     if (++calls % 8 == 0) {
       fprintf(stderr, "[nsfar train trace] B=%ld (units of 100 cycles since stamp 0):", B);

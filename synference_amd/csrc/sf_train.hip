@@ -13,6 +13,7 @@
 #include "sf_nsf1.h"
 #include "sf_nsfar.h"
 #include "sf_nsfc.h"
+#include "sf_pack.h"
 #include "sf_trainc.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -199,7 +200,8 @@ __global__ void k_grad_gather(const float* __restrict__ gimg, long stride, int c
 }
 
 // one launch for everything a training step needs before the flow kernel: forward image, transposed image,
-// zeroed gradient image (and zeroed context-gradient rows)
+// zeroed gradient image (and zeroed context-gradient rows); the pack rules are those of sf_pack.h.  (Of the fp32 tables only the
+// 16-row one, u2, carries SF_PACK_TANH_SCALE: for s2, t2 and c2 sf_pack_f32 is the plain two-table sum.)
 __global__ void k_train_prep(const float* __restrict__ flat, const int32_t* __restrict__ s1, const int32_t* __restrict__ s2,
                              float* __restrict__ packed, long n1, const int32_t* __restrict__ t1,
                              const int32_t* __restrict__ t2, float* __restrict__ packedT, long n2,
@@ -209,55 +211,20 @@ __global__ void k_train_prep(const float* __restrict__ flat, const int32_t* __re
                              const int32_t* __restrict__ c1, const int32_t* __restrict__ c2, float* __restrict__ imgC, long n7) {
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n1) {
-    const int a = s1[i], b = s2[i];
-    float v = 0.f;
-    if (a >= 0) v = flat[a];
-    if (b >= 0) v += flat[b];
-    packed[i] = v;
+    packed[i] = sf_pack_f32(flat, s1[i], s2[i]);
     for (int c = 0; c < copies; ++c) gimg[(size_t)c * n1 + i] = 0.f;
     return;
   }
   i -= n1;
-  if (i < n2) {
-    const int a = t1[i], b = t2[i];
-    float v = 0.f;
-    if (a >= 0) v = flat[a];
-    if (b >= 0) v += flat[b];
-    packedT[i] = v;
-    return;
-  }
+  if (i < n2) { packedT[i] = sf_pack_f32(flat, t1[i], t2[i]); return; }
   i -= n2;
   if (i < n4) { dctx[i] = 0.f; return; }
   i -= n4;
-  if (i < n5) {  // 16-row sampler image (so that sampling right after a training step needs no set_params)
-    const int a = u1[i], b = u2[i];
-    float v = 0.f;
-    if (a >= 0) v = flat[a];
-    if (b >= 0) v += flat[b];
-    else if (b == SF_PACK_TANH_SCALE) v *= SF_TANH_PRESCALE;
-    packed16[i] = v;
-    return;
-  }
+  if (i < n5) { packed16[i] = sf_pack_f32(flat, u1[i], u2[i]); return; }  // 16-row sampler image (so that sampling right after a training step needs no set_params)
   i -= n5;
-  if (i < n6) {  // split-bf16 hidden blocks of the persistent sampler (k_pack_bf16_split)
-    const int a = sB[i];
-    unsigned short r = 0;
-    if (a >= 0) {
-      const float w = flat[a & SF_PACK_SPLIT_INDEX] * ((a & SF_PACK_SPLIT_SCALED) ? SF_TANH_PRESCALE : 1.0f);
-      const __bf16 hi = (__bf16)w;
-      r = __builtin_bit_cast(unsigned short, (a >> 30) & 1 ? (__bf16)(w - (float)hi) : hi);
-    }
-    packed16B[i] = r;
-    return;
-  }
+  if (i < n6) { packed16B[i] = sf_pack_bf16_split(flat, sB[i]); return; }  // split-bf16 hidden blocks of the persistent sampler
   i -= n6;
-  if (i < n7) {  // cooperative training image (sf_trainc.hip)
-    const int a = c1[i], b = c2[i];
-    float v = 0.f;
-    if (a >= 0) v = flat[a];
-    if (b >= 0) v += flat[b];
-    imgC[i] = v;
-  }
+  if (i < n7) imgC[i] = sf_pack_f32(flat, c1[i], c2[i]);  // cooperative training image (sf_trainc.hip)
 }
 
 #define SF_TDECL(H)                                                                         \
@@ -277,176 +244,193 @@ static float* sq_for(sf_flow* f, const SfLayout& L) {
   return f->d_sqpart;
 }
 
-int sf_train_loss_grad(sf_flow* f, const float* flat, const float* theta, const float* x, const long long* idx, long B,
-                       float grad_scale, const float* weights, float* loss, double* loss_sum, float* grad, float* dctx,
-                       hipStream_t st, std::string& err) {
+// ---- lazily built training state: all or nothing -- a failed allocation frees what was already taken (the local group), so
+// that the next call starts over instead of launching kernels on half-built state
+static int ensure_trainc(sf_flow* f) {   // the cooperative kernels' image and gather tables
+  if (f->trainc_ready) return SF_OK;
   const SfLayout& L = f->L;
-  if (f->nsf1) {  // one-parameter NSF: T context MLPs + a scalar spline chain (sf_nsf1.hip); the handle keeps the vector it was given
-    if (dctx) { err = "the one-parameter NSF has no context-gradient path"; return SF_ERR_INVALID; }
-    hipError_t e = hipMemcpyAsync(f->d_flat, flat, (size_t)L.n_params * sizeof(float), hipMemcpyDeviceToDevice, st);
-    if (e != hipSuccess) { err = std::string("hipMemcpyAsync: ") + hipGetErrorString(e); return SF_ERR_HIP; }
-    return sf_nsf1_loss_grad(f->nsf1, flat, theta, x, idx, B, grad_scale, weights, loss, loss_sum, grad, st, err);
+  SfFlowTrainC c;
+  SF_TRY_SET(c.d_imgC.alloc((size_t)L.n_imgC));
+  SF_TRY_SET(c.d_sC1.alloc((size_t)L.n_imgC));
+  SF_TRY_SET(c.d_sC2.alloc((size_t)L.n_imgC));
+  SF_TRY_SET(hipMemcpy(c.d_sC1, L.srcC1.data(), (size_t)L.n_imgC * sizeof(int32_t), hipMemcpyHostToDevice));
+  SF_TRY_SET(hipMemcpy(c.d_sC2, L.srcC2.data(), (size_t)L.n_imgC * sizeof(int32_t), hipMemcpyHostToDevice));
+  SF_TRY_SET(c.d_gdstC.alloc((size_t)L.n_params));
+  SF_TRY_SET(hipMemcpy(c.d_gdstC, L.gdstC.data(), (size_t)L.n_params * sizeof(int32_t), hipMemcpyHostToDevice));
+  // position -> parameter(s), for the gather that walks the partials in THEIR order (coalesced reads): a position
+  // feeds at most two parameters (b0 and bc share one); if the packer ever maps more, the parameter-order gather stays
+  std::vector<int32_t> inv((size_t)L.n_gradC * 2, -1), zero;
+  bool ok = true;
+  for (long i = 0; i < (long)L.n_params && ok; ++i) {
+    const int32_t g = L.gdstC[(size_t)i];
+    if (g < 0) { zero.push_back((int32_t)i); continue; }
+    if (g >= (int32_t)L.n_gradC) { ok = false; break; }
+    if (inv[(size_t)g * 2] < 0) inv[(size_t)g * 2] = (int32_t)i;
+    else if (inv[(size_t)g * 2 + 1] < 0) inv[(size_t)g * 2 + 1] = (int32_t)i;
+    else ok = false;
   }
-  if (f->nsfar) {
-    if (dctx) { err = "the autoregressive NSF has no context-gradient path"; return SF_ERR_INVALID; }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (f->profiling) {
-      SF_TRY_ERR(f->ev_train[0].create()); SF_TRY_ERR(f->ev_train[1].create());
-      e0 = f->ev_train[0]; e1 = f->ev_train[1];
-    }
-    const int rc = sf_nsfar_loss_grad(f->nsfar, flat, theta, x, idx, B, grad_scale, weights, loss, loss_sum, grad, st, err, e0, e1);
-    if (!rc && f->profiling) f->ev_train_valid = true;
-    return rc;
+  if (ok) {
+    SF_TRY_SET(c.d_gsrcC.upload(inv));
+    c.n_gzeroC = (long)zero.size();
+    if (!zero.empty()) SF_TRY_SET(c.d_gzeroC.upload(zero));
   }
-  // ---- cooperative 16-row kernels: MAF (sf_trainc.hip: two blocks, D <= 8, T <= SF_TRC_TS, <= 4 hidden tiles) and
-  //      NSF (sf_nsfc.hip: two blocks, D <= 8, H <= 64, K <= 11); they share the image / gather machinery
-  const bool coop_maf = B > 0 && sf_trainc_eligible(L, dctx != nullptr);
-  const bool coop_nsf = B > 0 && !coop_maf && sf_nsfc_eligible(L, dctx != nullptr);
-  if (coop_maf || coop_nsf) {
-    if (!f->trainc_ready) {
-      SfFlowTrainC c;   // all or nothing: moved into the handle once it is complete
-      SF_TRY_ERR(c.d_imgC.alloc((size_t)L.n_imgC));
-      SF_TRY_ERR(c.d_sC1.alloc((size_t)L.n_imgC));
-      SF_TRY_ERR(c.d_sC2.alloc((size_t)L.n_imgC));
-      SF_TRY_ERR(hipMemcpy(c.d_sC1, L.srcC1.data(), (size_t)L.n_imgC * sizeof(int32_t), hipMemcpyHostToDevice));
-      SF_TRY_ERR(hipMemcpy(c.d_sC2, L.srcC2.data(), (size_t)L.n_imgC * sizeof(int32_t), hipMemcpyHostToDevice));
-      SF_TRY_ERR(c.d_gdstC.alloc((size_t)L.n_params));
-      SF_TRY_ERR(hipMemcpy(c.d_gdstC, L.gdstC.data(), (size_t)L.n_params * sizeof(int32_t), hipMemcpyHostToDevice));
-      {
-        // position -> parameter(s), for the gather that walks the partials in THEIR order (coalesced reads): a position
-        // feeds at most two parameters (b0 and bc share one); if the packer ever maps more, the parameter-order gather stays
-        std::vector<int32_t> inv((size_t)L.n_gradC * 2, -1), zero;
-        bool ok = true;
-        for (long i = 0; i < (long)L.n_params && ok; ++i) {
-          const int32_t g = L.gdstC[(size_t)i];
-          if (g < 0) { zero.push_back((int32_t)i); continue; }
-          if (g >= (int32_t)L.n_gradC) { ok = false; break; }
-          if (inv[(size_t)g * 2] < 0) inv[(size_t)g * 2] = (int32_t)i;
-          else if (inv[(size_t)g * 2 + 1] < 0) inv[(size_t)g * 2 + 1] = (int32_t)i;
-          else ok = false;
-        }
-        if (ok) {
-          SF_TRY_ERR(c.d_gsrcC.upload(inv));
-          c.n_gzeroC = (long)zero.size();
-          if (!zero.empty()) SF_TRY_ERR(c.d_gzeroC.upload(zero));
-        }
-      }
-      static_cast<SfFlowTrainC&>(*f) = std::move(c);
-      f->trainc_ready = true;
-    }
-    const int grid = coop_maf ? sf_trainc_grid(B, &L.trc, L.dev.T) : sf_nsfc_grid(B, L.nsc.NT);
-    // Gradient accumulation (sf_fixacc.h): per-workgroup partials + gather while they are few, above that 2^-40 fixed-point
-    // contributions added with int64 atomics into one zeroed replica per XCD (L2-resident, order independent).  The gather
-    // needs the position -> parameter table (d_gsrcC); SF_GRAD_ACC=partial | fix forces one form.
-    const int nsf_mode = coop_nsf ? sf_nsfc_acc_mode(B, grid, (long)L.n_gradC) : 0;
-    bool use_fix = coop_nsf ? nsf_mode != 0 : sf_trainc_fix(grid, (long)L.n_gradC);
-    if (!f->d_gsrcC) use_fix = false;
-    if (use_fix && !f->d_gfixC) SF_TRY_ERR(f->d_gfixC.alloc((size_t)SF_FIX_REPLICAS * (size_t)L.n_gradC));
-    if (use_fix) SF_TRY_ERR(hipMemsetAsync(f->d_gfixC, 0, (size_t)SF_FIX_REPLICAS * (size_t)L.n_gradC * sizeof(long long), st));
-    const int n_part = use_fix ? 1 : grid;   // (fix: d_gpartC is only the base the job descriptors count from)
-    const size_t need = (size_t)n_part * (size_t)L.n_gradC;
-    SF_TRY_ERR(f->d_gpartC.grow(need));
-    {
-      // inside an epoch call (sf_flow_train_epoch, all steps but its last) only the cooperative image is re-tiled: the density
-      // and sampler images are not read by the training kernels, and nobody can look at them before the call returns
-      const bool lite = f->prep_lite;
-      const long n1 = lite ? 0 : (long)L.n_packed;
-      const long n4 = dctx ? B * (long)L.dev.C : 0;
-      const long n5 = (!lite && f->d_packed16) ? (long)L.n_packed16 : 0;
-      const long n6 = (!lite && f->d_packed16B) ? (long)L.n_packed16B : 0;
-      const long n7 = (long)L.n_imgC;
-      const long tot = n1 + n4 + n5 + n6 + n7;
-      hipLaunchKernelGGL(k_train_prep, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, flat, f->d_s1, f->d_s2, f->d_packed,
-                         n1, (const int32_t*)nullptr, (const int32_t*)nullptr, (float*)nullptr, 0L, (float*)nullptr, 0,
-                         dctx, n4, f->d_s16a, f->d_s16b, f->d_packed16, n5, f->d_s16B, f->d_packed16B, n6, f->d_sC1, f->d_sC2,
-                         f->d_imgC, n7);
-      SF_TRY_ERR(hipGetLastError());
-      f->packed16_stale = lite;
-      f->packed_stale = lite;
-      f->wp_stale = true;
-    }
-    if (L.n_packedB > 0) SF_TRY_ERR(sf_launch_pack_bf16(flat, f->d_bsrc, f->d_packedB, (long)L.n_packedB, st));
-    if (coop_nsf) {
-      const long n_chunks = (B + 31) / 32;
-      const size_t ust_need = (size_t)n_chunks * 32 * (size_t)L.dev.T * 16;
-      SF_TRY_ERR(f->d_ustash.grow(ust_need));
-      const SfDev& v = L.dev;
-      SfNscArgs a;
-      a.c = L.nsc;
-      a.img = f->d_imgC; a.cst = f->d_cst;
-      a.D = v.D; a.C = v.C; a.T = v.T; a.K = v.K;
-      a.tail_bound = v.tail_bound; a.min_w = v.min_w; a.min_h = v.min_h; a.min_d = v.min_d; a.lu_eps = v.lu_eps;
-      a.inv_sqrt_h = v.inv_sqrt_h; a.deriv_const = v.deriv_const; a.logdet0 = v.logdet0;
-      a.c_pscale = v.c_pscale; a.c_pshift = v.c_pshift; a.c_xmean = v.c_xmean; a.c_xstd = v.c_xstd;
-      a.theta = theta; a.x = x; a.idx = idx; a.wts = weights; a.B = B; a.n_chunks = n_chunks; a.w = grad_scale;
-      a.loss = loss; a.loss_sum = loss_sum; a.loss_mask = 0;
-      if (loss_sum && f->d_losspart) { a.loss_sum = f->d_losspart; a.loss_mask = SF_LOSS_PARTS - 1; f->losspart_used = true; }
-      a.gpart = f->d_gpartC; a.gpart_stride = (long)L.n_gradC; a.fix = use_fix ? f->d_gfixC : nullptr; a.fix_mode = nsf_mode;
-      a.ustash = f->d_ustash;
-#ifdef SF_NSC_TRACE
-      a.trace = nullptr;
-#endif
-      if (f->profiling) {
-        SF_TRY_ERR(f->ev_train[0].create()); SF_TRY_ERR(f->ev_train[1].create());
-        SF_TRY_ERR(hipEventRecord(f->ev_train[0], st));
-      }
-      SF_TRY_ERR(sf_launch_nsf_trainc(a, grid, st));
-      if (f->profiling) {
-        SF_TRY_ERR(hipEventRecord(f->ev_train[1], st));
-        f->ev_train_valid = true;
-      }
-      if (use_fix && nsf_mode == 2)   // float replicas: the partial gather over SF_FIX_REPLICAS images
-        SF_TRY_ERR(sf_launch_gather_c2(reinterpret_cast<const float*>(f->d_gfixC.get()), (long)L.n_gradC, SF_FIX_REPLICAS, f->d_gsrcC, f->d_gzeroC, f->n_gzeroC, grad, st, sq_for(f, L)));
-      else if (use_fix) SF_TRY_ERR(sf_launch_gather_fix(f->d_gfixC, (long)L.n_gradC, SF_FIX_REPLICAS, f->d_gsrcC, f->d_gzeroC, f->n_gzeroC, grad, st));
-      else if (f->d_gsrcC) SF_TRY_ERR(sf_launch_gather_c2(f->d_gpartC, (long)L.n_gradC, n_part, f->d_gsrcC, f->d_gzeroC, f->n_gzeroC, grad, st, sq_for(f, L)));
-      else SF_TRY_ERR(sf_launch_gather_c(f->d_gpartC, (long)L.n_gradC, n_part, f->d_gdstC, grad, (long)L.n_params, st));
-      return SF_OK;
-    }
-    SfTrcArgs a;
-    a.c = L.trc;
+  static_cast<SfFlowTrainC&>(*f) = std::move(c);
+  f->trainc_ready = true;
+  return SF_OK;
+}
+static int ensure_train(sf_flow* f) {   // the 32-row kernels' transposed image and gradient image
+  if (f->train_ready) return SF_OK;
+  const SfLayout& L = f->L;
+  SfFlowTrain t;
+  SF_TRY_SET(t.d_packedT.alloc((size_t)L.n_packedT));
+  SF_TRY_SET(t.d_t1.alloc((size_t)L.n_packedT));
+  SF_TRY_SET(t.d_t2.alloc((size_t)L.n_packedT));
+  SF_TRY_SET(hipMemcpy(t.d_t1, L.srcT1.data(), (size_t)L.n_packedT * sizeof(int32_t), hipMemcpyHostToDevice));
+  SF_TRY_SET(hipMemcpy(t.d_t2, L.srcT2.data(), (size_t)L.n_packedT * sizeof(int32_t), hipMemcpyHostToDevice));
+  SF_TRY_SET(t.d_gpacked.alloc((size_t)SF_GCOPIES * L.n_packed));
+  SF_TRY_SET(t.d_gdst.upload(L.gdst));
+  static_cast<SfFlowTrain&>(*f) = std::move(t);
+  f->train_ready = true;
+  return SF_OK;
+}
+
+// ---- the profiling bracket (sf_flow_set_profiling): the step's flow kernel between the handle's two events
+static int train_events(sf_flow* f) {
+  if (f->profiling) { SF_TRY_SET(f->ev_train[0].create()); SF_TRY_SET(f->ev_train[1].create()); }
+  return SF_OK;
+}
+template <typename Launch>
+static int bracketed(sf_flow* f, hipStream_t st, Launch launch) {
+  int rc = train_events(f);
+  if (rc) return rc;
+  if (f->profiling) SF_TRY_SET(hipEventRecord(f->ev_train[0], st));
+  rc = launch();
+  if (rc) return rc;
+  if (f->profiling) {
+    SF_TRY_SET(hipEventRecord(f->ev_train[1], st));
+    f->ev_train_valid = true;
+  }
+  return SF_OK;
+}
+
+// ---- cooperative 16-row kernels: MAF (sf_trainc.hip: two blocks, D <= 8, T <= SF_TRC_TS, <= 4 hidden tiles) and
+//      NSF (sf_nsfc.hip: two blocks, D <= 8, H <= 64, K <= 11); they share the image / gather machinery
+static int coop_loss_grad(sf_flow* f, bool coop_nsf, const float* flat, const float* theta, const float* x, const long long* idx,
+                          long B, float grad_scale, const float* weights, float* loss, double* loss_sum, float* grad, float* dctx,
+                          hipStream_t st) {
+  const SfLayout& L = f->L;
+  const SfDev& v = L.dev;
+  int rc = ensure_trainc(f);
+  if (rc) return rc;
+  const int grid = coop_nsf ? sf_nsfc_grid(B, L.nsc.NT) : sf_trainc_grid(B, &L.trc, v.T);
+  // Gradient accumulation (sf_fixacc.h): per-workgroup partials + gather while they are few, above that 2^-40 fixed-point
+  // contributions added with int64 atomics into one zeroed replica per XCD (L2-resident, order independent).  The gather
+  // needs the position -> parameter table (d_gsrcC); SF_GRAD_ACC=partial | fix forces one form.
+  const int nsf_mode = coop_nsf ? sf_nsfc_acc_mode(B, grid, (long)L.n_gradC) : 0;
+  bool use_fix = coop_nsf ? nsf_mode != 0 : sf_trainc_fix(grid, (long)L.n_gradC);
+  if (!f->d_gsrcC) use_fix = false;
+  if (use_fix && !f->d_gfixC) SF_TRY_SET(f->d_gfixC.alloc((size_t)SF_FIX_REPLICAS * (size_t)L.n_gradC));
+  if (use_fix) SF_TRY_SET(hipMemsetAsync(f->d_gfixC, 0, (size_t)SF_FIX_REPLICAS * (size_t)L.n_gradC * sizeof(long long), st));
+  const int n_part = use_fix ? 1 : grid;   // (fix: d_gpartC is only the base the job descriptors count from)
+  const size_t need = (size_t)n_part * (size_t)L.n_gradC;
+  SF_TRY_SET(f->d_gpartC.grow(need));
+  {
+    // inside an epoch call (sf_flow_train_epoch, all steps but its last) only the cooperative image is re-tiled: the density
+    // and sampler images are not read by the training kernels, and nobody can look at them before the call returns
+    const bool lite = f->prep_lite;
+    const long n1 = lite ? 0 : (long)L.n_packed;
+    const long n4 = dctx ? B * (long)v.C : 0;
+    const long n5 = (!lite && f->d_packed16) ? (long)L.n_packed16 : 0;
+    const long n6 = (!lite && f->d_packed16B) ? (long)L.n_packed16B : 0;
+    const long n7 = (long)L.n_imgC;
+    const long tot = n1 + n4 + n5 + n6 + n7;
+    hipLaunchKernelGGL(k_train_prep, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, flat, f->d_s1, f->d_s2, f->d_packed,
+                       n1, (const int32_t*)nullptr, (const int32_t*)nullptr, (float*)nullptr, 0L, (float*)nullptr, 0,
+                       dctx, n4, f->d_s16a, f->d_s16b, f->d_packed16, n5, f->d_s16B, f->d_packed16B, n6, f->d_sC1, f->d_sC2,
+                       f->d_imgC, n7);
+    SF_TRY_SET(hipGetLastError());
+    f->packed16_stale = lite;
+    f->packed_stale = lite;
+    f->wp_stale = true;
+  }
+  if (L.n_packedB > 0) SF_TRY_SET(sf_launch_pack_bf16(flat, f->d_bsrc, f->d_packedB, (long)L.n_packedB, st));
+  auto common = [&](auto& a) {   // the fields SfNscArgs and SfTrcArgs share
     a.img = f->d_imgC; a.cst = f->d_cst;
-    a.D = L.dev.D; a.C = L.dev.C; a.T = L.dev.T; a.scale_fn = L.dev.scale_fn;
-    a.eps = L.dev.eps; a.logdet0 = L.dev.logdet0;
-    a.c_pscale = L.dev.c_pscale; a.c_pshift = L.dev.c_pshift; a.c_tdim = L.dev.c_tdim; a.c_xmean = L.dev.c_xmean; a.c_xstd = L.dev.c_xstd;
-    a.theta = theta; a.x = x; a.idx = idx; a.wts = weights; a.B = B; a.n_chunks = (B + 32L * sf_trainc_groups(B, &L.trc, L.dev.T) - 1) / (32L * sf_trainc_groups(B, &L.trc, L.dev.T)); a.w = grad_scale;
-    a.loss = loss; a.loss_sum = loss_sum; a.dctx = dctx; a.loss_mask = 0;
+    a.D = v.D; a.C = v.C; a.T = v.T; a.logdet0 = v.logdet0;
+    a.c_pscale = v.c_pscale; a.c_pshift = v.c_pshift; a.c_xmean = v.c_xmean; a.c_xstd = v.c_xstd;
+    a.theta = theta; a.x = x; a.idx = idx; a.wts = weights; a.B = B; a.w = grad_scale;
+    a.loss = loss; a.loss_sum = loss_sum; a.loss_mask = 0;
     if (loss_sum && f->d_losspart) { a.loss_sum = f->d_losspart; a.loss_mask = SF_LOSS_PARTS - 1; f->losspart_used = true; }
     a.gpart = f->d_gpartC; a.gpart_stride = (long)L.n_gradC; a.fix = use_fix ? f->d_gfixC : nullptr;
-    if (f->profiling) {
-      SF_TRY_ERR(f->ev_train[0].create()); SF_TRY_ERR(f->ev_train[1].create());
-      SF_TRY_ERR(hipEventRecord(f->ev_train[0], st));
-    }
-    SF_TRY_ERR(sf_launch_maf_trainc(a, grid, st));
-    if (f->profiling) {
-      SF_TRY_ERR(hipEventRecord(f->ev_train[1], st));
-      f->ev_train_valid = true;
-    }
-    if (use_fix) SF_TRY_ERR(sf_launch_gather_fix(f->d_gfixC, (long)L.n_gradC, SF_FIX_REPLICAS, f->d_gsrcC, f->d_gzeroC, f->n_gzeroC, grad, st));
-    else if (f->d_gsrcC) SF_TRY_ERR(sf_launch_gather_c2(f->d_gpartC, (long)L.n_gradC, grid, f->d_gsrcC, f->d_gzeroC, f->n_gzeroC, grad, st, sq_for(f, L)));
-    else SF_TRY_ERR(sf_launch_gather_c(f->d_gpartC, (long)L.n_gradC, grid, f->d_gdstC, grad, (long)L.n_params, st));
-    return SF_OK;
+  };
+  if (coop_nsf) {
+    const long n_chunks = (B + 31) / 32;
+    const size_t ust_need = (size_t)n_chunks * 32 * (size_t)v.T * 16;
+    SF_TRY_SET(f->d_ustash.grow(ust_need));
+    SfNscArgs a;
+    common(a);
+    a.c = L.nsc;
+    a.K = v.K;
+    a.tail_bound = v.tail_bound; a.min_w = v.min_w; a.min_h = v.min_h; a.min_d = v.min_d; a.lu_eps = v.lu_eps;
+    a.inv_sqrt_h = v.inv_sqrt_h; a.deriv_const = v.deriv_const;
+    a.n_chunks = n_chunks; a.fix_mode = nsf_mode;
+    a.ustash = f->d_ustash;
+#ifdef SF_NSC_TRACE
+    a.trace = nullptr;
+#endif
+    rc = bracketed(f, st, [&]() -> int { SF_TRY_SET(sf_launch_nsf_trainc(a, grid, st)); return SF_OK; });
+  } else {
+    const long per_chunk = 32L * sf_trainc_groups(B, &L.trc, v.T);
+    SfTrcArgs a;
+    common(a);
+    a.c = L.trc;
+    a.scale_fn = v.scale_fn; a.eps = v.eps; a.c_tdim = v.c_tdim;
+    a.n_chunks = (B + per_chunk - 1) / per_chunk;
+    a.dctx = dctx;
+    rc = bracketed(f, st, [&]() -> int { SF_TRY_SET(sf_launch_maf_trainc(a, grid, st)); return SF_OK; });
   }
-  // ---- lazily built training state
-  if (!f->train_ready) {
-    // all-or-nothing: a failed allocation frees what was already taken (the local group), so that the next call starts over
-    // instead of launching kernels on half-built state
-    SfFlowTrain t;
-    SF_TRY_ERR(t.d_packedT.alloc((size_t)L.n_packedT));
-    SF_TRY_ERR(t.d_t1.alloc((size_t)L.n_packedT));
-    SF_TRY_ERR(t.d_t2.alloc((size_t)L.n_packedT));
-    SF_TRY_ERR(hipMemcpy(t.d_t1, L.srcT1.data(), (size_t)L.n_packedT * sizeof(int32_t), hipMemcpyHostToDevice));
-    SF_TRY_ERR(hipMemcpy(t.d_t2, L.srcT2.data(), (size_t)L.n_packedT * sizeof(int32_t), hipMemcpyHostToDevice));
-    SF_TRY_ERR(t.d_gpacked.alloc((size_t)SF_GCOPIES * L.n_packed));
-    SF_TRY_ERR(t.d_gdst.upload(L.gdst));
-    static_cast<SfFlowTrain&>(*f) = std::move(t);
-    f->train_ready = true;
+  if (rc) return rc;
+  // the gather: float replicas (NSF only: the partial gather over SF_FIX_REPLICAS images), fixed point, partials by position, partials
+  // by parameter
+  if (use_fix && nsf_mode == 2)
+    SF_TRY_SET(sf_launch_gather_c2(reinterpret_cast<const float*>(f->d_gfixC.get()), (long)L.n_gradC, SF_FIX_REPLICAS, f->d_gsrcC, f->d_gzeroC, f->n_gzeroC, grad, st, sq_for(f, L)));
+  else if (use_fix) SF_TRY_SET(sf_launch_gather_fix(f->d_gfixC, (long)L.n_gradC, SF_FIX_REPLICAS, f->d_gsrcC, f->d_gzeroC, f->n_gzeroC, grad, st));
+  else if (f->d_gsrcC) SF_TRY_SET(sf_launch_gather_c2(f->d_gpartC, (long)L.n_gradC, n_part, f->d_gsrcC, f->d_gzeroC, f->n_gzeroC, grad, st, sq_for(f, L)));
+  else SF_TRY_SET(sf_launch_gather_c(f->d_gpartC, (long)L.n_gradC, n_part, f->d_gdstC, grad, (long)L.n_params, st));
+  return SF_OK;
+}
+
+int sf_train_loss_grad(sf_flow* f, const float* flat, const float* theta, const float* x, const long long* idx, long B,
+                       float grad_scale, const float* weights, float* loss, double* loss_sum, float* grad, float* dctx,
+                       hipStream_t st) {
+  const SfLayout& L = f->L;
+  if (f->nsf1) {  // one-parameter NSF: T context MLPs + a scalar spline chain (sf_nsf1.hip); the handle keeps the vector it was given
+    if (dctx) return sf_fail(SF_ERR_INVALID, "the one-parameter NSF has no context-gradient path");
+    hipError_t e = hipMemcpyAsync(f->d_flat, flat, (size_t)L.n_params * sizeof(float), hipMemcpyDeviceToDevice, st);
+    if (e != hipSuccess) return sf_fail(SF_ERR_HIP, std::string("hipMemcpyAsync: ") + hipGetErrorString(e));
+    return sf_nsf1_loss_grad(f->nsf1, flat, theta, x, idx, B, grad_scale, weights, loss, loss_sum, grad, st);
   }
+  if (f->nsfar) {   // (records the two events itself, around its flow kernel)
+    if (dctx) return sf_fail(SF_ERR_INVALID, "the autoregressive NSF has no context-gradient path");
+    int rc = train_events(f);
+    if (rc) return rc;
+    const bool p = f->profiling;
+    rc = sf_nsfar_loss_grad(f->nsfar, flat, theta, x, idx, B, grad_scale, weights, loss, loss_sum, grad, st,
+                            p ? f->ev_train[0].get() : nullptr, p ? f->ev_train[1].get() : nullptr);
+    if (!rc && p) f->ev_train_valid = true;
+    return rc;
+  }
+  const bool coop_maf = B > 0 && sf_trainc_eligible(L, dctx != nullptr);
+  const bool coop_nsf = B > 0 && !coop_maf && sf_nsfc_eligible(L, dctx != nullptr);
+  if (coop_maf || coop_nsf) return coop_loss_grad(f, coop_nsf, flat, theta, x, idx, B, grad_scale, weights, loss, loss_sum, grad, dctx, st);
+  int rc = ensure_train(f);
+  if (rc) return rc;
   const SfDev& v = L.dev;
   const long waves = (B + 31) / 32;
   const long tiles_per_wave = (long)v.T * (v.kind == SF_MAF ? ((v.NB + 1) * v.HT + 1) : (2 + (3 * v.NB + 1) * v.HT));
   const long act_per_wave = tiles_per_wave * 4 * 64;  // float4
   const size_t need = (size_t)waves * act_per_wave * 4;
-  SF_TRY_ERR(f->d_act.grow(need));
+  SF_TRY_SET(f->d_act.grow(need));
   // gradient accumulation: one replica per tile + plain stores (bitwise reproducible, and cheaper than atomics) up to
   // 16 tiles (batch 512: the reference's batch sizes), or whenever SF_DETERMINISTIC=1 and the replicas fit 2 GiB
   // (batch 2048: +15 % step time for zeroing and summing 64 replicas); else per-XCD replicas + f32 atomics
@@ -454,7 +438,7 @@ int sf_train_loss_grad(sf_flow* f, const float* flat, const float* theta, const 
   if (force_det < 0) { const char* e = std::getenv("SF_DETERMINISTIC"); force_det = e ? std::atoi(e) : 0; }
   const bool det = waves > 0 && (waves <= 16 || (force_det == 1 && (size_t)waves * L.n_packed * sizeof(float) <= ((size_t)2 << 30)));
   const int copies = det ? (int)waves : SF_GCOPIES;
-  SF_TRY_ERR(f->d_gpacked.grow((size_t)copies * L.n_packed));
+  SF_TRY_SET(f->d_gpacked.grow((size_t)copies * L.n_packed));
   {
     const long n4 = (dctx && B > 0) ? B * (long)L.dev.C : 0;
     const long n5 = f->d_packed16 ? (long)L.n_packed16 : 0;
@@ -464,35 +448,31 @@ int sf_train_loss_grad(sf_flow* f, const float* flat, const float* theta, const 
                        (long)L.n_packed, f->d_t1, f->d_t2, f->d_packedT, (long)L.n_packedT, f->d_gpacked, copies, dctx, n4,
                        f->d_s16a, f->d_s16b, f->d_packed16, n5, f->d_s16B, f->d_packed16B, n6, (const int32_t*)nullptr,
                        (const int32_t*)nullptr, (float*)nullptr, 0L);
-    SF_TRY_ERR(hipGetLastError());
+    SF_TRY_SET(hipGetLastError());
   }
   f->packed16_stale = false;
   f->wp_stale = true;
-  if (L.n_packedB > 0) SF_TRY_ERR(sf_launch_pack_bf16(flat, f->d_bsrc, f->d_packedB, (long)L.n_packedB, st));
+  if (L.n_packedB > 0) SF_TRY_SET(sf_launch_pack_bf16(flat, f->d_bsrc, f->d_packedB, (long)L.n_packedB, st));
   if (B > 0) {
     SfTrainArgs a;
     a.theta = theta; a.x = x; a.idx = idx; a.loss_sum = loss_sum; a.B = B; a.w = grad_scale; a.wts = weights; a.loss = loss; a.dctx = dctx; a.gimg = f->d_gpacked; a.gimg_stride = (long)L.n_packed; a.det = det ? 1 : 0;
     a.act = reinterpret_cast<float4*>(f->d_act.get()); a.act_per_wave = act_per_wave;
     const SfDev m = f->dev();
     const bool maf = m.kind == SF_MAF;
-    if (f->profiling) {
-      SF_TRY_ERR(f->ev_train[0].create()); SF_TRY_ERR(f->ev_train[1].create());
-      SF_TRY_ERR(hipEventRecord(f->ev_train[0], st));
-    }
-    switch (m.HT) {
-      case 1: SF_TRY_ERR(maf ? sf_launch_maf_train_h1(m, a, st) : sf_launch_nsf_train_h1(m, a, st)); break;
-      case 2: SF_TRY_ERR(maf ? sf_launch_maf_train_h2(m, a, st) : sf_launch_nsf_train_h2(m, a, st)); break;
-      case 3: SF_TRY_ERR(maf ? sf_launch_maf_train_h3(m, a, st) : sf_launch_nsf_train_h3(m, a, st)); break;
-      case 4: SF_TRY_ERR(maf ? sf_launch_maf_train_h4(m, a, st) : sf_launch_nsf_train_h4(m, a, st)); break;
-      default: err = "bad HT"; return SF_ERR_INVALID;
-    }
-    if (f->profiling) {
-      SF_TRY_ERR(hipEventRecord(f->ev_train[1], st));
-      f->ev_train_valid = true;
-    }
+    rc = bracketed(f, st, [&]() -> int {
+      switch (m.HT) {
+        case 1: SF_TRY_SET(maf ? sf_launch_maf_train_h1(m, a, st) : sf_launch_nsf_train_h1(m, a, st)); break;
+        case 2: SF_TRY_SET(maf ? sf_launch_maf_train_h2(m, a, st) : sf_launch_nsf_train_h2(m, a, st)); break;
+        case 3: SF_TRY_SET(maf ? sf_launch_maf_train_h3(m, a, st) : sf_launch_nsf_train_h3(m, a, st)); break;
+        case 4: SF_TRY_SET(maf ? sf_launch_maf_train_h4(m, a, st) : sf_launch_nsf_train_h4(m, a, st)); break;
+        default: return sf_fail(SF_ERR_INVALID, "bad HT");
+      }
+      return SF_OK;
+    });
+    if (rc) return rc;
   }
   hipLaunchKernelGGL(k_grad_gather, dim3((unsigned)((L.n_params + 255) / 256)), dim3(256), 0, st,
                      f->d_gpacked, (long)L.n_packed, copies, f->d_gdst, grad, (long)L.n_params);
-  SF_TRY_ERR(hipGetLastError());
+  SF_TRY_SET(hipGetLastError());
   return SF_OK;
 }
