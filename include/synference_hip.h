@@ -333,7 +333,8 @@ typedef struct sf_adam_desc {
 int sf_opt_create(int64_t n, const sf_adam_desc* d, sf_opt** out);
 void sf_opt_destroy(sf_opt* o);
 /* max_norm <= 0 disables clipping; *grad_norm_out (device float, may be NULL) gets the
- * pre-clip global L2 norm. */
+ * pre-clip global L2 norm.  The norm is summed in a fixed order at every n: the same inputs give
+ * the same bits, here and in sf_adam_apply. */
 int sf_adam_step(sf_opt* o, float* params, const float* grad, float max_norm,
                  float* grad_norm_out, void* stream);
 /* Stateless form: the caller owns exp_avg / exp_avg_sq [n] (device) and the step counter (the

@@ -6,6 +6,10 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <map>
+#include <mutex>
+#include <thread>
+#include <tuple>
 
 #include "sf_internal.h"
 #include "sf_train_args.h"
@@ -19,30 +23,42 @@
 // ---------------------------------------------------------------------------------------------
 // clip_grad_norm_ + Adam
 // ---------------------------------------------------------------------------------------------
-__global__ void k_sqnorm(const float* __restrict__ g, long n, float* __restrict__ acc) {
+// Two-kernel form (n > 131072, or a gradient that is not 16-byte aligned): every block leaves its share of |grad|^2 in
+// shares[blockIdx.x] (SF_ADAM_SHARES at the most), and every block of k_adam sums the shares in the same fixed order.  No atomics:
+// the norm -- and with it the clip coefficient and the step -- is the same bits call after call, and its rounding error is that of
+// a tree, not of a chain of adds into one growing total (2e-7 relative seen on 129 blocks: more than the rest of the step together).
+#define SF_ADAM_SHARES 256
+__global__ __launch_bounds__(256) void k_sqnorm(const float* __restrict__ g, long n, float* __restrict__ shares) {
   float s = 0.f;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
     s += g[i] * g[i];
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-  __shared__ float part[16];
+  __shared__ float part[4];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   if (lane == 0) part[w] = s;
   __syncthreads();
-  if (threadIdx.x == 0) {
-    float t = 0.f;
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += part[i];
-    atomicAdd(acc, t);
-  }
+  if (threadIdx.x == 0) shares[blockIdx.x] = (part[0] + part[1]) + (part[2] + part[3]);
 }
 
-__global__ void k_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                       float* __restrict__ v, const float* __restrict__ sq, long n, sf_adam_desc d, float bc1,
-                       float bc2, float max_norm, float* __restrict__ norm_out) {
-  const float total = sqrtf(*sq);
+__global__ __launch_bounds__(256) void k_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                              float* __restrict__ v, const float* __restrict__ shares, int n_shares,
+                                              float* __restrict__ sq_out, long n, sf_adam_desc d, float bc1, float bc2,
+                                              float max_norm, float* __restrict__ norm_out) {
+  float s = (int)threadIdx.x < n_shares ? shares[threadIdx.x] : 0.f;   // n_shares <= SF_ADAM_SHARES = blockDim.x
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  __shared__ float part[4];
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
+  __syncthreads();
+  const float sq = (part[0] + part[1]) + (part[2] + part[3]);
+  const float total = sqrtf(sq);
   float coef = 1.f;
   if (max_norm > 0.f) coef = fminf(max_norm / (total + 1e-6f), 1.0f);  // torch clip_grad_norm_
-  if (norm_out && blockIdx.x == 0 && threadIdx.x == 0) *norm_out = total;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    *sq_out = sq;
+    if (norm_out) *norm_out = total;
+  }
   const float step_size = d.lr / bc1;
   const float inv_sqrt_bc2 = rsqrtf(bc2);
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
@@ -156,6 +172,20 @@ hipError_t sf_launch_fold_loss(double* part, int n, double* out, hipStream_t st)
   return hipGetLastError();
 }
 
+// The shares of the two-kernel form: SF_ADAM_SHARES floats per (device, stream, calling thread), taken on first use and kept for
+// the life of the process -- sf_adam_apply has no handle that could own them.  Calls on one stream are ordered, so are the uses of
+// its buffer; two threads that name the same stream (hipStreamPerThread is one name for many) never share one.
+static float* adam_shares(hipStream_t st) {
+  static std::mutex mu;
+  static std::map<std::tuple<int, hipStream_t, std::thread::id>, float*> held;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+  std::lock_guard<std::mutex> lock(mu);
+  float*& p = held[std::make_tuple(dev, st, std::this_thread::get_id())];
+  if (!p && hipMalloc(&p, SF_ADAM_SHARES * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); p = nullptr; }
+  return p;
+}
+
 hipError_t sf_launch_adam(float* params, const float* grad, float* m, float* v, float* norm_scratch, long n,
                           const sf_adam_desc& d, float bc1, float bc2, float max_norm, float* grad_norm_out,
                           hipStream_t st, const float* sq_part, int n_sq) {
@@ -165,11 +195,11 @@ hipError_t sf_launch_adam(float* params, const float* grad, float* m, float* v, 
                        bc2, max_norm, grad_norm_out, sq_part, n_sq);
     return hipGetLastError();
   }
-  hipError_t e = hipMemsetAsync(norm_scratch, 0, sizeof(float), st);
-  if (e != hipSuccess) return e;
-  const int blocks = (int)((n + 1023) / 1024 < 256 ? (n + 1023) / 1024 : 256);
-  hipLaunchKernelGGL(k_sqnorm, dim3(blocks), dim3(256), 0, st, grad, n, norm_scratch);
-  hipLaunchKernelGGL(k_adam, dim3(blocks), dim3(256), 0, st, params, grad, m, v, norm_scratch, n, d, bc1, bc2,
+  float* shares = adam_shares(st);
+  if (!shares) return hipErrorOutOfMemory;
+  const int blocks = (int)((n + 1023) / 1024 < SF_ADAM_SHARES ? (n + 1023) / 1024 : SF_ADAM_SHARES);
+  hipLaunchKernelGGL(k_sqnorm, dim3(blocks), dim3(256), 0, st, grad, n, shares);
+  hipLaunchKernelGGL(k_adam, dim3(blocks), dim3(256), 0, st, params, grad, m, v, shares, blocks, norm_scratch, n, d, bc1, bc2,
                      max_norm, grad_norm_out);
   return hipGetLastError();
 }
