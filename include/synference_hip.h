@@ -348,7 +348,13 @@ int sf_adam_apply(float* params, const float* grad, float* exp_avg, float* exp_a
  * (ref: the batch loop of custom_runner.py:585-618): for b < n_batches:
  *   rows = order[b*batch .. (b+1)*batch);  grad = d/dflat sum_rows grad_scale * (-log p);  clip + Adam(W) step
  *   number step0 + b + 1 on flat (state exp_avg / exp_avg_sq, scratch [2] as in sf_adam_apply).
- * order: DEVICE int64 [n_batches*batch] (the epoch's shuffled training rows); grad: DEVICE scratch [P]. */
+ * order: DEVICE int64 [n_batches*batch] (the epoch's shuffled training rows); grad: DEVICE scratch [P].
+ * What the handle represents afterwards: every image (density, samplers, context products) is that of `flat` as it was when the
+ * LAST step's gradient was taken, i.e. BEFORE the last update -- the start vector for n_batches = 1.  Between the steps of a call
+ * only the training image follows `flat`; the last step re-tiles all of them, and they agree among themselves.  `flat` as returned
+ * is one update ahead: to evaluate or sample at it, call sf_flow_set_params(flat) first.  As after sf_flow_loss_grad*, the
+ * handle holds no vector of its own (sf_flow_get_params / sf_flow_log_prob_grad: SF_ERR_STATE) and a prepared context table is
+ * dropped.  n_batches = 0 leaves the handle as it was. */
 int sf_flow_train_epoch(sf_flow* f, float* flat, const float* theta, const float* x, const int64_t* order,
                         int64_t n_batches, int64_t batch, float grad_scale, float* exp_avg, float* exp_avg_sq,
                         const sf_adam_desc* d, int64_t step0, float max_norm, float* scratch /*[2]*/,

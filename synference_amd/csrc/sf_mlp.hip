@@ -7,12 +7,15 @@
 
 #include "sf_train_kernels.h"
 
+#define SF_MLP_DET_WAVES 16   // 32-row tiles that get a gradient image of their own (sf_mlp_backward)
+
 struct SfMlpArgs {
   const float* x;
   const float* dout;  // backward only
   float* out;         // forward only
   long B;
   float* gimg;
+  long gimg_stride;   // backward: floats between the waves' own gradient images; 0 = one image shared by all waves (f32 atomics)
   float4* act;
   long act_per_wave;
 };
@@ -105,6 +108,7 @@ __global__ __launch_bounds__(256) void k_mlp_bwd(SfMlpDev m, SfMlpArgs a) {
   if (base >= a.B) return;
   float* lds = lds_all + wave * (2 * HT) * SF_TL;
   float4* stash = a.act + wid * a.act_per_wave;
+  float* const gimg = a.gimg + wid * a.gimg_stride;   // (its own zeroed image: every address is added to once)
   const long row = base + c;
   const bool valid = row < a.B;
   const long ii = valid ? row : a.B - 1;
@@ -132,7 +136,7 @@ __global__ __launch_bounds__(256) void k_mlp_bwd(SfMlpDev m, SfMlpArgs a) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) ain[mt][0][r] = sf_act_f(m.act, zin[mt][0][r]);
       }
-      sf_grad_w_local<HT, HT>(lds, d, ain, a.gimg + m.o_w[l], a.gimg + m.o_b[l], m.nG[l], 0, m.nG[l], lane);
+      sf_grad_w_local<HT, HT>(lds, d, ain, gimg + m.o_w[l], gimg + m.o_b[l], m.nG[l], 0, m.nG[l], lane);
       f32x16 din[HT][1];
 #pragma unroll
       for (int mt = 0; mt < HT; ++mt)
@@ -148,7 +152,7 @@ __global__ __launch_bounds__(256) void k_mlp_bwd(SfMlpDev m, SfMlpArgs a) {
   for (int kt = 0; kt * 4 < m.nG[0]; ++kt) {
     f32x16 ct[1][1];
     sf_mlp_in_tile(ct, xr, m, kt, h);
-    sf_grad_w_local<HT, 1>(lds, d, ct, a.gimg + m.o_w[0], kt == 0 ? a.gimg + m.o_b[0] : nullptr, m.nG[0], kt * 4,
+    sf_grad_w_local<HT, 1>(lds, d, ct, gimg + m.o_w[0], kt == 0 ? gimg + m.o_b[0] : nullptr, m.nG[0], kt * 4,
                      min(4, m.nG[0] - kt * 4), lane);
   }
 }
@@ -157,13 +161,13 @@ __global__ __launch_bounds__(256) void k_mlp_bwd(SfMlpDev m, SfMlpArgs a) {
 // host side
 // ---------------------------------------------------------------------------------------------
 struct SfMlpBufs {   // built once, all or nothing (mlp_ensure)
-  SfBuf<float> d_packed, d_packedT, d_cst, d_gimg;
+  SfBuf<float> d_packed, d_packedT, d_cst;
   SfBuf<int32_t> d_s1, d_s2, d_t1, d_t2, d_gdst;
 };
 struct sf_mlp : SfMlpBufs {
   SfMlpLayout L;
   bool dev_ready = false;
-  SfBuf<float> d_act;
+  SfBuf<float> d_act, d_gimg;   // grown per call
   SfMlpDev dev() const {
     SfMlpDev v = L.dev;
     v.packed = d_packed; v.packedT = d_packedT; v.cst = d_cst;
@@ -171,10 +175,15 @@ struct sf_mlp : SfMlpBufs {
   }
 };
 
-__global__ void k_mlp_gather(const float* __restrict__ gimg, const int32_t* __restrict__ gdst,
+__global__ void k_mlp_gather(const float* __restrict__ gimg, long stride, int copies, const int32_t* __restrict__ gdst,
                              float* __restrict__ grad, long n) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) grad[i] = gdst[i] >= 0 ? gimg[gdst[i]] : 0.f;
+  if (i >= n) return;
+  const int g = gdst[i];
+  float v = 0.f;
+  if (g >= 0)
+    for (int c = 0; c < copies; ++c) v += gimg[(size_t)c * stride + g];   // fixed order over the waves' images
+  grad[i] = v;
 }
 
 namespace {
@@ -190,7 +199,6 @@ int mlp_ensure(sf_mlp* m) {
   SfMlpBufs b;
   SF_TRY_SET(b.d_packed.alloc((size_t)L.n_packed));
   SF_TRY_SET(b.d_packedT.alloc(std::max<size_t>((size_t)L.n_packedT, 64)));
-  SF_TRY_SET(b.d_gimg.alloc((size_t)L.n_packed));
   SF_TRY_SET(b.d_cst.upload(L.cst));
   SF_TRY_SET(b.d_s1.upload(L.src1)); SF_TRY_SET(b.d_s2.upload(L.src2));
   SF_TRY_SET(b.d_t1.upload(L.srcT1)); SF_TRY_SET(b.d_t2.upload(L.srcT2));
@@ -271,10 +279,15 @@ int sf_mlp_backward(sf_mlp* m, const float* flat, const float* x, const float* d
   SF_TRY_SET(m->d_act.grow(need));
   SF_TRY_SET(sf_launch_pack(flat, m->d_s1, m->d_s2, m->d_packed, (long)L.n_packed, st));
   if (L.n_packedT > 0) SF_TRY_SET(sf_launch_pack(flat, m->d_t1, m->d_t2, m->d_packedT, (long)L.n_packedT, st));
-  SF_TRY_SET(hipMemsetAsync(m->d_gimg, 0, (size_t)L.n_packed * sizeof(float), st));
+  // Gradient accumulation as in the 32-row flow kernels (sf_train.hip): up to SF_MLP_DET_WAVES tiles (batch 512) every 32-row wave
+  // adds into a zeroed image of its own and the gather sums the images in tile order -- the same inputs give the same bits; above
+  // that one shared image and f32 atomics.  (One shared image at every batch repeated to the bit only up to two waves, 64 rows.)
+  const int copies = (waves >= 1 && waves <= SF_MLP_DET_WAVES) ? (int)waves : 1;
+  SF_TRY_SET(m->d_gimg.grow((size_t)copies * (size_t)L.n_packed));
+  SF_TRY_SET(hipMemsetAsync(m->d_gimg, 0, (size_t)copies * (size_t)L.n_packed * sizeof(float), st));
   if (B > 0) {
     SfMlpArgs a{};
-    a.x = x; a.dout = dout; a.B = B; a.gimg = m->d_gimg;
+    a.x = x; a.dout = dout; a.B = B; a.gimg = m->d_gimg; a.gimg_stride = copies > 1 ? (long)L.n_packed : 0;
     a.act = reinterpret_cast<float4*>(m->d_act.get()); a.act_per_wave = act_per_wave;
     const SfMlpDev d = m->dev();
     switch (d.HT) {
@@ -284,8 +297,8 @@ int sf_mlp_backward(sf_mlp* m, const float* flat, const float* x, const float* d
       default: SF_TRY_SET(launch_bwd<4>(d, a, st)); break;
     }
   }
-  hipLaunchKernelGGL(k_mlp_gather, dim3((unsigned)((L.n_params + 255) / 256)), dim3(256), 0, st, m->d_gimg, m->d_gdst,
-                     grad, (long)L.n_params);
+  hipLaunchKernelGGL(k_mlp_gather, dim3((unsigned)((L.n_params + 255) / 256)), dim3(256), 0, st, m->d_gimg, (long)L.n_packed, copies,
+                     m->d_gdst, grad, (long)L.n_params);
   SF_TRY_SET(hipGetLastError());
   return SF_OK;
 }
