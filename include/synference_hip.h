@@ -732,6 +732,22 @@ const char* sf_version(void);
 /* number of visible HIP devices (0 on a CPU-only box; never fails) */
 int sf_device_count(void);
 
+/* ---- latents -------------------------------------------------------------------------
+ * The density direction with its latent handed out ([UPSTREAM] nflows Flow.transform_to_noise): z = T(theta; x) in the column
+ * order sf_flow_inverse_from_noise reads, logabsdet = log |det dz / dtheta| with the standardisation term, so that
+ * sf_flow_log_prob = -0.5 |z|^2 - 0.5 D log(2 pi) + logabsdet.  The same kernels as sf_flow_log_prob; either output may be
+ * NULL; B == 0 is a no-op.  Asynchronous on `stream`. */
+int sf_flow_to_noise(sf_flow* f, const float* theta /*[B,D]*/, const float* x /*[B,C]*/, int64_t B,
+                     float* z /*[B,D] or NULL*/, float* logabsdet /*[B] or NULL*/, void* stream);
+/* One pass over z[N, D] (1 <= D <= 16, N >= 0), every output a device array that may be NULL.  A row counts if all its D values
+ * are finite (n), the others are skipped (n_bad).  psum[p, d] = sum z_d^(p+1), cross[i, j] = sum z_i z_j, both accumulated in
+ * fp64; pit_counts[d, b]: rows with min(floor(u nb), nb - 1) == b for u = Phi(z_d) = 0.5 erfc(-z_d / sqrt 2);
+ * radial_counts[b]: the same for u = F_chi2_D(|z|^2) (both in fp64; 1 <= nb <= 1024).  Deterministic: two calls give the same
+ * bits.  Asynchronous on `stream`. */
+int sf_latent_summary(const float* z /*[N,D] device*/, int64_t N, int32_t D, int32_t nb,
+                      int64_t* n2 /*[2]: n, n_bad*/, double* psum /*[4,D]*/, double* cross /*[D,D]*/,
+                      int64_t* pit_counts /*[D,nb]*/, int64_t* radial_counts /*[nb]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

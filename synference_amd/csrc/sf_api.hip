@@ -333,16 +333,30 @@ int sf_flow_get_params(sf_flow* f, float* flat, int64_t n, int is_device, void* 
   return SF_OK;
 }
 
-int sf_flow_log_prob(sf_flow* f, const float* theta, const float* x, int64_t B, float* out, void* stream) {
-  if (!f) return sf_fail(SF_ERR_INVALID, "null handle");
-  if (B == 0) return SF_OK;
-  if (!theta || !x || !out) return sf_fail(SF_ERR_INVALID, "null argument");
+// one density-direction pass over B rows: whichever of lp, z, lad the caller asked for (sf_flow_log_prob, sf_flow_to_noise)
+static int density_pass(sf_flow* f, const float* theta, const float* x, int64_t B, SfLpOut out, void* stream) {
   if (!f->params_set) return sf_fail(SF_ERR_STATE, "sf_flow_set_params has not been called");
   if (B < 0) return sf_fail(SF_ERR_INVALID, "B < 0");
   if (f->nsf1) return sf_nsf1_log_prob(f->nsf1, f->d_flat, theta, x, (long)B, out, (hipStream_t)stream);
   if (f->nsfar) return sf_nsfar_log_prob(f->nsfar, theta, x, (long)B, out, (hipStream_t)stream);
   SF_TRY_SET(sf_launch_logprob(f->dev(), theta, x, (long)B, out, (hipStream_t)stream));
   return SF_OK;
+}
+
+int sf_flow_log_prob(sf_flow* f, const float* theta, const float* x, int64_t B, float* out, void* stream) {
+  if (!f) return sf_fail(SF_ERR_INVALID, "null handle");
+  if (B == 0) return SF_OK;
+  if (!theta || !x || !out) return sf_fail(SF_ERR_INVALID, "null argument");
+  return density_pass(f, theta, x, B, sf_lp_out(out, nullptr, nullptr, f->L.dev.D), stream);
+}
+
+int sf_flow_to_noise(sf_flow* f, const float* theta, const float* x, int64_t B, float* z, float* logabsdet, void* stream) {
+  if (!f) return sf_fail(SF_ERR_INVALID, "sf_flow_to_noise: null handle");
+  if (B == 0) return SF_OK;
+  if (!theta || !x) return sf_fail(SF_ERR_INVALID, "sf_flow_to_noise: null argument");
+  if (int rc = ensure_device(f)) return rc;   // (a machine without a GPU says so, whatever the handle's state)
+  if (!z && !logabsdet) return SF_OK;         // (nothing asked for)
+  return density_pass(f, theta, x, B, sf_lp_out(nullptr, z, logabsdet, f->L.dev.D), stream);
 }
 
 int sf_flow_inverse_from_noise(sf_flow* f, const float* z, const float* x, int64_t B, float* theta,

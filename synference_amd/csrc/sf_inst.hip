@@ -72,7 +72,7 @@ static hipError_t launch_persist_lds(const SfDev& m, const SfSampleArgsHost& a, 
 }
 
 template <class OpsB>
-static hipError_t launch_logprob_bf16(const SfDev& m, const float* theta, const float* x, long B, float* out,
+static hipError_t launch_logprob_bf16(const SfDev& m, const float* theta, const float* x, long B, SfLpOut out,
                                       hipStream_t st) {
   static SfAttrCache attr;
   const size_t sh = (size_t)m.part_bytes_max;
@@ -80,7 +80,7 @@ static hipError_t launch_logprob_bf16(const SfDev& m, const float* theta, const 
   if (e != hipSuccess) return e;
   const int wpb = sf_lds_wpb(sh);
   hipLaunchKernelGGL((k_logprob<OpsB, 1, true>), dim3((unsigned)((B + 32 * wpb - 1) / (32 * wpb))), dim3(64 * wpb), sh, st,
-                     m, theta, x, B, out);
+                     m, theta, x, B, out.lp, out.z, out.lad, out.z_vec);
   return hipGetLastError();
 }
 template <class OpsB>
@@ -97,7 +97,7 @@ static hipError_t launch_inverse_bf16(const SfDev& m, const SfSampleArgsHost& a,
 }
 
 template <class OpsG, class OpsL, int NS>
-static hipError_t launch_logprob(const SfDev& m, const float* theta, const float* x, long B, float* out,
+static hipError_t launch_logprob(const SfDev& m, const float* theta, const float* x, long B, SfLpOut out,
                                  hipStream_t st) {
   if (sf_fits_lds(m)) {
     static SfAttrCache attr;
@@ -107,11 +107,11 @@ static hipError_t launch_logprob(const SfDev& m, const float* theta, const float
     const int wpb = sf_lds_wpb(sh);
     const long per_block = (long)wpb * 32 * NS;
     hipLaunchKernelGGL((k_logprob<OpsL, NS, true>), dim3((unsigned)((B + per_block - 1) / per_block)), dim3(64 * wpb),
-                       sh, st, m, theta, x, B, out);
+                       sh, st, m, theta, x, B, out.lp, out.z, out.lad, out.z_vec);
   } else {
     const long per_block = 4L * 32 * NS;
     hipLaunchKernelGGL((k_logprob<OpsG, NS, false>), dim3((unsigned)((B + per_block - 1) / per_block)), dim3(256),
-                       0, st, m, theta, x, B, out);
+                       0, st, m, theta, x, B, out.lp, out.z, out.lad, out.z_vec);
   }
   return hipGetLastError();
 }
@@ -184,7 +184,7 @@ static hipError_t launch_inverse(const SfDev& m, const SfSampleArgsHost& a, hipS
 #endif
 
 hipError_t SF_CAT(sf_launch_logprob_k, SF_KIND, _h, SF_HT)(const SfDev& m, int ns, const float* theta,
-                                                           const float* x, long B, float* out,
+                                                           const float* x, long B, SfLpOut out,
                                                            hipStream_t st) {
   if (m.hidden_bf16) SF_BF_SWITCH(launch_logprob_bf16, m, theta, x, B, out, st)
 #if SF_HT <= 2

@@ -14,13 +14,17 @@
 
 // ---------------------------------------------------------------------------------------------
 // log_prob:  out[i] = log N(z;0,I) + logdet          ref: custom_runner.py:604 (via [UPSTREAM] Flow.log_prob)
+// to_noise:  z_out[i,:] = z, lad_out[i] = logdet       ([UPSTREAM] Flow.transform_to_noise): the register slots at the end of
+//            forward() are the columns k_inverse reads z_in by, i.e. the order of the oracle's forward_transform.
+// One kernel for both (SfLpOut, sf_internal.h): each of the three outputs is written unless NULL.
 // ---------------------------------------------------------------------------------------------
 extern __shared__ float sf_lds_image[];
 
 template <class Ops, int NS, bool LDSW>
 __global__ __launch_bounds__(LDSW ? 512 : 256) void k_logprob(SfDev m, const float* __restrict__ theta,
                                                               const float* __restrict__ x, long B,
-                                                              float* __restrict__ out) {
+                                                              float* __restrict__ out, float* __restrict__ z_out,
+                                                              float* __restrict__ lad_out, int z_vec) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int c = lane & 31, h = lane >> 5;
   const long base = ((long)blockIdx.x * (blockDim.x >> 6) + wave) * (32 * NS);
@@ -52,7 +56,25 @@ __global__ __launch_bounds__(LDSW ? 512 : 256) void k_logprob(SfDev m, const flo
     for (int p = 0; p < SF_DMAX; ++p)
       if (p < m.D) s += u[ns][p] * u[ns][p];
     const float lp = -0.5f * s - 0.5f * (float)m.D * SF_LOG_2PI + logdet[ns];
-    if (h == 0 && row[ns] < B) out[row[ns]] = lp;
+    if (h == 0 && row[ns] < B) {
+      if (out) out[row[ns]] = lp;
+      if (z_out) {
+        // the lane's row, contiguous: 16-byte pieces where the host found the rows aligned (SfLpOut::z_vec), dwords otherwise.
+        // (Written out here on purpose: the same stores through a shared helper -- row pointer formed once, restrict-qualified
+        //  parameter -- compiled the NS = 1 MAF kernels to 216 .. 221 VGPRs instead of 99 .. 168.)
+        if (z_vec != 0) {
+#pragma unroll
+          for (int p = 0; p < SF_DMAX; p += 4)
+            if (p < m.D)
+              reinterpret_cast<float4*>(z_out + row[ns] * m.D)[p >> 2] = make_float4(u[ns][p], u[ns][p + 1], u[ns][p + 2], u[ns][p + 3]);
+        } else {
+#pragma unroll
+          for (int p = 0; p < SF_DMAX; ++p)
+            if (p < m.D) z_out[row[ns] * m.D + p] = u[ns][p];
+        }
+      }
+      if (lad_out) lad_out[row[ns]] = logdet[ns];
+    }
   }
 }
 

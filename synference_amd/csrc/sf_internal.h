@@ -73,8 +73,24 @@ __device__ __forceinline__ void sf_out_store(const SfSampleArgsHost& a, size_t i
 }
 #endif
 
+// What a density-direction kernel writes per row, each unless NULL: lp = log q(theta | x) (sf_flow_log_prob), z[B, D] = the
+// latent T(theta; x) in the column order sf_flow_inverse_from_noise reads, lad = log |det dz / dtheta| with the standardisation
+// term (sf_flow_to_noise).  z_vec: the rows of z are 16-byte aligned (D % 4 == 0 and the base is) and leave as 16-byte pieces,
+// decided once on the host (sf_lp_out).
+struct SfLpOut {
+  float* lp = nullptr;
+  float* z = nullptr;
+  float* lad = nullptr;
+  int z_vec = 0;
+};
+inline SfLpOut sf_lp_out(float* lp, float* z, float* lad, int D) {
+  SfLpOut o;
+  o.lp = lp; o.z = z; o.lad = lad;
+  o.z_vec = (z && (D & 3) == 0 && (reinterpret_cast<uintptr_t>(z) & 15) == 0) ? 1 : 0;
+  return o;
+}
 
-hipError_t sf_launch_logprob(const SfDev& m, const float* theta, const float* x, long B, float* out,
+hipError_t sf_launch_logprob(const SfDev& m, const float* theta, const float* x, long B, SfLpOut out,
                              hipStream_t st);
 hipError_t sf_launch_inverse(const SfDev& m, const SfSampleArgsHost& a, hipStream_t st);
 bool sf_maf16_enabled(const SfDev& m, const SfSampleArgsHost& a);

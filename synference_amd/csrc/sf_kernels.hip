@@ -123,7 +123,7 @@ __global__ void k_fill_i32(int32_t* p, long n, int32_t v) {
 // dispatch on (kind, HT); PT and NS are resolved inside the instantiation TUs
 // ---------------------------------------------------------------------------------------------
 #define SF_DECL(K, H)                                                                                   \
-  hipError_t sf_launch_logprob_k##K##_h##H(const SfDev&, int, const float*, const float*, long, float*, \
+  hipError_t sf_launch_logprob_k##K##_h##H(const SfDev&, int, const float*, const float*, long, SfLpOut, \
                                            hipStream_t);                                                \
   hipError_t sf_launch_inverse_k##K##_h##H(const SfDev&, int, const SfSampleArgsHost&, hipStream_t);
 SF_DECL(0, 1) SF_DECL(0, 2) SF_DECL(0, 3) SF_DECL(0, 4)
@@ -146,7 +146,7 @@ int sf_pick_ns(const SfDev& m, bool inverse) {
 #define SF_CASE(K, H, FN, ...) \
   case K * 10 + H: return FN##_k##K##_h##H(__VA_ARGS__);
 
-hipError_t sf_launch_logprob(const SfDev& m, const float* theta, const float* x, long B, float* out,
+hipError_t sf_launch_logprob(const SfDev& m, const float* theta, const float* x, long B, SfLpOut out,
                              hipStream_t st) {
   if (B <= 0) return hipSuccess;
   const int ns = sf_pick_ns(m, false);

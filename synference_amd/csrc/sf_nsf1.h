@@ -25,7 +25,8 @@ struct SfNsf1 {
 
 int sf_nsf1_create(const sf_flow_desc& d, SfNsf1** out);
 void sf_nsf1_destroy(SfNsf1* n);
-int sf_nsf1_log_prob(SfNsf1* n, const float* flat, const float* theta, const float* x, long B, float* out, hipStream_t st);
+struct SfLpOut;   // sf_internal.h: lp, z, lad -- each written unless NULL
+int sf_nsf1_log_prob(SfNsf1* n, const float* flat, const float* theta, const float* x, long B, SfLpOut out, hipStream_t st);
 int sf_nsf1_inverse(SfNsf1* n, const float* flat, const float* z, const float* x, long B, float* theta, float* logdet, hipStream_t st);
 int sf_nsf1_loss_grad(SfNsf1* n, const float* flat, const float* theta, const float* x, const long long* idx, long B, float grad_scale,
                       const float* weights, float* loss, double* loss_sum, float* grad, hipStream_t st);

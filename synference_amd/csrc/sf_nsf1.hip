@@ -42,7 +42,7 @@ __device__ __forceinline__ void n1_load_q(const float* __restrict__ q, long n_ro
   }
 }
 
-__global__ void k_nsf1_logprob(const float* __restrict__ q, const float* __restrict__ theta, long B, Nsf1C c, float* __restrict__ out) {
+__global__ void k_nsf1_logprob(const float* __restrict__ q, const float* __restrict__ theta, long B, Nsf1C c, SfLpOut out) {
   const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
   float u = theta[b] * c.th_scale + c.th_shift, ld = c.logdet0;
@@ -54,7 +54,9 @@ __global__ void k_nsf1_logprob(const float* __restrict__ q, const float* __restr
     u = v;
     ld += lad;
   }
-  out[b] = -0.5f * u * u - 0.5f * 1.8378770664093453f + ld;
+  if (out.lp) out.lp[b] = -0.5f * u * u - 0.5f * 1.8378770664093453f + ld;
+  if (out.z) out.z[b] = u;   // (D = 1: the row is one dword)
+  if (out.lad) out.lad[b] = ld;
 }
 
 __global__ void k_nsf1_inverse(const float* __restrict__ q, const float* __restrict__ z, long B, Nsf1C c, float* __restrict__ theta,
@@ -245,7 +247,7 @@ int sf_nsf1_create(const sf_flow_desc& d, SfNsf1** out) {
 SfNsf1::~SfNsf1() { sf_mlp_destroy(mlp); }
 void sf_nsf1_destroy(SfNsf1* n) { delete n; }
 
-int sf_nsf1_log_prob(SfNsf1* n, const float* flat, const float* theta, const float* x, long B, float* out, hipStream_t st) {
+int sf_nsf1_log_prob(SfNsf1* n, const float* flat, const float* theta, const float* x, long B, SfLpOut out, hipStream_t st) {
   SF_TRY_SET(n->d_q.grow((size_t)n->T * B * n->NP));
   int rc = conditioner(*n, flat, x, B, n->d_q, st);
   if (rc) return rc;

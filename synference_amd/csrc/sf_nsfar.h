@@ -50,7 +50,8 @@ void sf_nsfar_destroy(SfNsfAr* n);
 size_t sf_nsfar_lds_bytes(const SfNsfAr& n, int hidden_buffers, int waves = 1);
 // re-tiles the logical vector into the masked images (every entry point below reads the images of the LAST pack)
 int sf_nsfar_pack(SfNsfAr* n, const float* flat, hipStream_t st);
-int sf_nsfar_log_prob(SfNsfAr* n, const float* theta, const float* x, long B, float* out, hipStream_t st);
+struct SfLpOut;   // sf_internal.h: lp, z, lad -- each written unless NULL
+int sf_nsfar_log_prob(SfNsfAr* n, const float* theta, const float* x, long B, SfLpOut out, hipStream_t st);
 int sf_nsfar_inverse(SfNsfAr* n, const float* z, const float* x, long B, float* theta, float* logdet, hipStream_t st);
 // count != null: acceptance counting (one attempt per item, item i belongs to row i / S); else the rejection sampler
 int sf_nsfar_sample(SfNsfAr* n, const float* x, long M, long S, const uint32_t* slots, long n_slots, const float* lo, const float* hi,

@@ -349,7 +349,7 @@ __device__ __forceinline__ void ar_load_inputs(const ArArgs& a, const float* __r
 // NWV waves per 64 samples: the tile pairs of a layer and the dimensions of a transform (head + spline) are dealt round robin
 template <int NWV>
 __global__ __launch_bounds__(64 * NWV) void k_ar_logprob(ArArgs a, const float* __restrict__ theta, const float* __restrict__ x, long B,
-                                                          float* __restrict__ out) {
+                                                          SfLpOut out) {
   extern __shared__ float lds[];
   float* E0 = lds;
   float* H1 = E0 + a.NIN16 * RS;
@@ -389,7 +389,19 @@ __global__ __launch_bounds__(64 * NWV) void k_ar_logprob(ArArgs a, const float* 
   if (wid == 0) {
     float ss = 0.f;
     for (int d = 0; d < a.D; ++d) ss += E0[d * RS + lane] * E0[d * RS + lane];
-    if (b < B) out[b] = -0.5f * ss - 0.5f * (float)a.D * 1.8378770664093453f + ld + a.logdet0;
+    if (b < B) {
+      if (out.lp) out.lp[b] = -0.5f * ss - 0.5f * (float)a.D * 1.8378770664093453f + ld + a.logdet0;
+      if (out.z) {   // E0 rows [0, D) hold the latent in theta's column order (k_ar_inverse reads z the same way)
+        float* zr = out.z + b * a.D;
+        if (out.z_vec) {
+          for (int d = 0; d < a.D; d += 4)
+            reinterpret_cast<float4*>(zr)[d >> 2] = make_float4(E0[d * RS + lane], E0[(d + 1) * RS + lane], E0[(d + 2) * RS + lane], E0[(d + 3) * RS + lane]);
+        } else {
+          for (int d = 0; d < a.D; ++d) zr[d] = E0[d * RS + lane];
+        }
+      }
+      if (out.lad) out.lad[b] = ld + a.logdet0;
+    }
   }
   AR_TS(250);
 }
@@ -1044,7 +1056,7 @@ int sf_nsfar_pack(SfNsfAr* n, const float* flat, hipStream_t st) {
   return SF_OK;
 }
 
-int sf_nsfar_log_prob(SfNsfAr* n, const float* theta, const float* x, long B, float* out, hipStream_t st) {
+int sf_nsfar_log_prob(SfNsfAr* n, const float* theta, const float* x, long B, SfLpOut out, hipStream_t st) {
 #ifdef SF_AR_TRACE
   {
     static unsigned long long* d_tr = nullptr;

@@ -196,6 +196,21 @@ class HipFlow:
         _lib.check(self.lib.sf_flow_log_prob(self.handle, _ptr(theta), _ptr(x), B, _ptr(out), _stream(self.device)))
         return out
 
+    def to_noise(self, theta, x) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(z [B, D], logabsdet [B]): the latent z = T(theta; x) of every row, in the column order ``inverse`` reads, and
+        log |det dz / dtheta| with the standardisation term -- ``log_prob`` is ``-0.5 |z|^2 - 0.5 D log(2 pi) + logabsdet``
+        (sf_flow_to_noise: the density kernels themselves, with the latent written out instead of squared and dropped)."""
+        self._dev()
+        theta, x = _f32c(theta, self.device), _f32c(x, self.device)
+        B = theta.shape[0]
+        if theta.shape != (B, self.spec.D) or x.shape != (B, self.spec.C):
+            raise ValueError(f"theta {tuple(theta.shape)} / x {tuple(x.shape)} do not match "
+                             f"(B,{self.spec.D}) / (B,{self.spec.C})")
+        z = torch.empty((B, self.spec.D), dtype=torch.float32, device=self.device)
+        lad = torch.empty(B, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.sf_flow_to_noise(self.handle, _ptr(theta), _ptr(x), B, _ptr(z), _ptr(lad), _stream(self.device)))
+        return z, lad
+
     GRAD_KINDS = ("maf", "nsf")
 
     def supports_log_prob_grad(self) -> bool:

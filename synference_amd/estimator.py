@@ -136,6 +136,16 @@ class FlowEstimator(nn.Module):
         self._sync_params()
         return self.flow.log_prob(theta, e)
 
+    def transform_to_noise(self, inputs, context=None, condition=None):
+        """nflows ``Flow.transform_to_noise``: (z [B, D], logabsdet [B]) of the rows of ``inputs`` under their contexts, the
+        embedding applied exactly as in ``log_prob``.  No graph: the latents are a diagnostic, not a training signal."""
+        x = context if context is not None else condition
+        theta = torch.as_tensor(inputs, dtype=torch.float32, device=self.flat.device)
+        with torch.no_grad():
+            e = self.embed(x)
+        self._sync_params()
+        return self.flow.to_noise(theta.detach(), e)
+
     def loss(self, theta, x):
         """sbi >= 0.23 estimator API: per-sample negative log-likelihood (custom_runner.py:596-601)."""
         return -self.log_prob(theta, context=x)

@@ -208,3 +208,50 @@ def tarp_coverage(samples: torch.Tensor, theta, references="random", metric: str
     if bidx is None:
         bidx = torch.arange(N, dtype=torch.int32).reshape(1, N)
     return e, alpha.cpu().numpy(), counts.cpu().numpy(), bidx.cpu().numpy()
+
+
+def latent_summary(z: torch.Tensor, num_bins: int = 100) -> dict:
+    """Residual statistics of (N, D) device latents ``z`` (``FlowPosterior.to_noise_catalogue``), which are N(0, I) for a calibrated
+    posterior.  One pass on the device (``sf_latent_summary``: fp64 sums, integer histograms, the same bits on every call) over
+    the rows whose D values are all finite; the rest is derived here in float64.  Keys: ``n``, ``n_bad`` (rows with a NaN or
+    an infinity, skipped); ``mean`` [D], ``cov`` [D, D] (population, about the mean), ``skew`` [D], ``excess_kurtosis`` [D];
+    ``pit_counts`` [D, num_bins], the histogram of u = Phi(z_d), and ``radial_counts`` [num_bins], that of
+    u_r = F_chi2_D(|z|^2) -- the expected coverage of the joint posterior read in the base space; ``ks`` [D] and
+    ``radial_ks`` = max_k |cum_k / n - k / num_bins|, the distance of each histogram from uniform; ``alpha`` = k / num_bins and
+    ``ecp`` = cum_k / n of the radial histogram, k = 0 .. num_bins, a curve to read like ``calculate_TARP``'s.  With no
+    finite row the derived values are NaN.  The statistics are those of the flow's own density: see the leakage caveat of
+    ``FlowPosterior.to_noise_catalogue``."""
+    if not isinstance(z, torch.Tensor) or z.device.type != "cuda":
+        raise RuntimeError("latent_summary runs on the GPU (no CPU fallback)")
+    if z.dim() != 2:
+        raise ValueError("z must be (N, D)")
+    zz = z.contiguous().float()
+    N, D = zz.shape
+    nb = int(num_bins)
+    dev = zz.device
+    n2 = torch.empty(2, dtype=torch.int64, device=dev)
+    psum = torch.empty((4, D), dtype=torch.float64, device=dev)
+    cross = torch.empty((D, D), dtype=torch.float64, device=dev)
+    pit = torch.empty((D, nb), dtype=torch.int64, device=dev)
+    rad = torch.empty((nb,), dtype=torch.int64, device=dev)
+    _lib.check(_lib.load().sf_latent_summary(_p(zz), N, D, nb, _p(n2), _p(psum), _p(cross), _p(pit), _p(rad), _stream(dev)))
+    n, n_bad = (int(v) for v in n2.cpu().numpy())
+    s = psum.cpu().numpy()
+    cr = cross.cpu().numpy()
+    pit_c, rad_c = pit.cpu().numpy(), rad.cpu().numpy()
+    alpha = np.arange(nb + 1, dtype=np.float64) / nb
+    with np.errstate(divide="ignore", invalid="ignore"):
+        inv = np.float64(1.0) / np.float64(n) if n else np.float64("nan")
+        m1, r2, r3, r4 = (s[k] * inv for k in range(4))                       # raw moments
+        cov = cr * inv - np.outer(m1, m1)
+        c2 = r2 - m1 ** 2                                                       # central moments
+        c3 = r3 - 3.0 * m1 * r2 + 2.0 * m1 ** 3
+        c4 = r4 - 4.0 * m1 * r3 + 6.0 * m1 ** 2 * r2 - 3.0 * m1 ** 4
+        skew = c3 / c2 ** 1.5
+        kurt = c4 / c2 ** 2 - 3.0
+        cum = np.concatenate([np.zeros((D, 1)), np.cumsum(pit_c, axis=1, dtype=np.float64)], 1) * inv
+        ecp = np.concatenate([[0.0], np.cumsum(rad_c, dtype=np.float64)]) * inv
+        ks = np.abs(cum - alpha[None, :]).max(1)
+        radial_ks = float(np.abs(ecp - alpha).max())
+    return {"n": n, "n_bad": n_bad, "mean": m1, "cov": cov, "skew": skew, "excess_kurtosis": kurt, "pit_counts": pit_c,
+            "radial_counts": rad_c, "ks": ks, "radial_ks": radial_ks, "alpha": alpha, "ecp": ecp}

@@ -1527,15 +1527,18 @@ class SBI_Fitter:
 
     def evaluate_model(self, posteriors=None, X_test=None, y_test=None, num_samples: int = 1000,
                        independent_metrics: bool = True, seed: Optional[int] = None, samples=None,
-                       verbose: bool = False, tarp: bool = False, **unknown) -> dict:
+                       verbose: bool = False, tarp: bool = False, latent: bool = False, **unknown) -> dict:
         """The reference's evaluate_model for flow posteriors (sbi_runner.py:6484-6735), same keys and arithmetic:
         ``MSE``, ``RMSE``, ``mean_ae``, ``median_ae``, ``R_squared`` (total sum of squares about the GLOBAL mean of
         y_test, as there), ``RMSE_norm`` / ``mean_ae_norm`` (divided by the global std), ``log_dpit_max``
         (-0.5 log max |PIT - uniform|, 6613-6616) and ``mean_log_prob``; per parameter with ``independent_metrics``, else
         pooled.  ``tarp=True`` adds the reference's ``tarp`` key (6618-6637), a one-element list holding ``calculate_TARP``
         of the same draws (the reference computes it on every call through the third-party ``tarp`` package; here it is
-        opt-in and runs on the device, ``sf_tarp_coverage``).  The draws stay on the device: means, medians, PIT ranks and
-        the TARP counts are reduced there and only (N, D) summaries cross PCIe."""
+        opt-in and runs on the device, ``sf_tarp_coverage``).  ``latent=True`` adds ``latent_radial_ks`` and ``latent_ks_max``
+        from ``calculate_latent_residuals`` of the test pairs: the members' ``radial_ks`` averaged with the ensemble weights,
+        and the largest per-dimension ``ks`` of any member (both 0 for a calibrated posterior; they draw nothing, so the
+        other keys do not move).  The draws stay on the device: means, medians, PIT ranks and the TARP counts are reduced
+        there and only (N, D) summaries cross PCIe."""
         _warn_unknown("evaluate_model", unknown)
         posteriors = posteriors if posteriors is not None else self.posteriors
         X_test = self._X_test if X_test is None else X_test
@@ -1571,6 +1574,10 @@ class SBI_Fitter:
             metrics["mean_log_prob"] = float(np.mean(self.log_prob(X_test, y_test, posteriors=posteriors)))
         except Exception:
             pass
+        if latent:
+            res = self.calculate_latent_residuals(X_test, y_test, posteriors=posteriors)
+            metrics["latent_radial_ks"] = float(np.dot(res["weights"], [m["radial_ks"] for m in res["members"]]))
+            metrics["latent_ks_max"] = float(max(np.max(m["ks"]) for m in res["members"]))
         metrics = {k: (v.tolist() if isinstance(v, np.ndarray) else float(v)) for k, v in metrics.items()}
         if verbose:
             for k, v in metrics.items():
@@ -1613,6 +1620,38 @@ class SBI_Fitter:
             sd = torch.as_tensor(np.ascontiguousarray(np.asarray(samples, dtype=np.float32).transpose(1, 0, 2))).to(self.device)
         val = self._tarp_value(sd, y, posteriors=posteriors, num_bootstrap=num_bootstrap, seed=seed, norm_axis=norm_axis)
         return torch.tensor(val, dtype=torch.float64, device=self.device)
+
+    def calculate_latent_residuals(self, X=None, y=None, posteriors=None, num_bins: int = 100, return_latents: bool = False):
+        """Calibration read in the base space of the flows (the numbers behind the reference's empty ``plot_latent_residual``,
+        sbi_runner.py:7200): every ensemble member maps the test pairs to its latents ``z_i = T(y_i; X_i)``, which are
+        N(0, I) for a calibrated posterior, and ``features.latent_summary`` reduces them on the device -- moments, the
+        per-dimension PIT histograms of Phi(z_d) and the histogram of F_chi2_D(|z_i|^2), whose cumulative curve is the expected
+        coverage of the joint posterior.  One density-direction pass per pair and member: no draws, where ``calculate_TARP``
+        and ``calculate_PIT`` need ``num_samples`` of them per pair.  ``X`` / ``y`` default to the stored test split.  Returns
+        ``{"members": [summary, ...], "weights": [...]}`` (a mixture has no latent space of its own: one summary per member);
+        with ``return_latents`` also the list of the members' float64 (N, D) host arrays.  Under a process group every rank
+        computes the whole thing.  The test is on the flow's own density q: where the prior box truncates q (leakage) the
+        posterior is q renormalised inside the box and the latents of in-box truths are not exactly N(0, I) -- quote
+        ``acceptance_rows`` next to the result."""
+        from .features import latent_summary
+        posteriors = posteriors if posteriors is not None else self.posteriors
+        X = self._X_test if X is None else X
+        y = self._y_test if y is None else y
+        Xt = torch.as_tensor(np.asarray(X, dtype=np.float32))
+        yt = torch.as_tensor(np.asarray(y, dtype=np.float32))
+        if Xt.dim() == 2:
+            yt = yt.reshape(len(Xt), -1)
+        if hasattr(posteriors, "posteriors"):
+            pairs = posteriors.to_noise_catalogue(yt, Xt)
+            weights = [float(w) for w in posteriors.weights]
+        else:
+            pairs = [posteriors.to_noise_catalogue(yt, Xt)]
+            weights = [1.0]
+        out = {"members": [latent_summary(z, num_bins) for z, _ in pairs], "weights": weights}
+        if return_latents:
+            from .hostio import to_host_f64
+            return out, [to_host_f64(z) for z, _ in pairs]
+        return out
 
     def calculate_PIT(self, X: np.ndarray, y: np.ndarray, num_samples: int = 1000, posteriors=None,
                       samples=None, seed: Optional[int] = None) -> np.ndarray:

@@ -212,6 +212,22 @@ class FlowPosterior:
                 lp = lp - torch.log(acc.clamp_min(1e-30))[inv]
         return lp
 
+    def to_noise_catalogue(self, theta, X):
+        """Latents of aligned rows: (z [N, D], logabsdet [N]) float32 device tensors, z = T(theta_i; x_i) under the flow's own
+        density q ([UPSTREAM] nflows ``Flow.transform_to_noise``; ``FlowEstimator.transform_to_noise``).  For a calibrated
+        posterior the latents of the true parameters are N(0, I).  The prior box plays no part: where it truncates q (leakage)
+        the posterior is q renormalised inside the box and the latents of in-box truths are not exactly normal -- quote
+        ``acceptance_rows`` next to any statistic of them."""
+        est = self.posterior_estimator
+        theta = torch.as_tensor(theta, dtype=torch.float32, device=self.device)
+        if theta.dim() == 1:
+            theta = theta[None, :]
+        X = self._embed(X)
+        if X.shape[0] == 1 and theta.shape[0] > 1:
+            X = X.expand(theta.shape[0], -1).contiguous()
+        est._sync_params()
+        return est.flow.to_noise(theta, X)
+
     # ---- sbi surface ------------------------------------------------------------------------
     def sample(self, sample_shape=(1,), x=None, show_progress_bars=False, seed: Optional[int] = None, **_):
         S = int(np.prod(sample_shape)) if len(tuple(sample_shape)) else 1
@@ -365,6 +381,12 @@ class EnsemblePosterior:
 
     def potential_fn(self, theta, x):
         return self.log_prob_catalogue(theta, x, norm_posterior=False)
+
+    def to_noise_catalogue(self, theta, X):
+        """A list, one ``(z [N, D], logabsdet [N])`` pair per member (``FlowPosterior.to_noise_catalogue``).  A mixture has no
+        latent space of its own: every member maps the rows into its own base space, and the members' latents are read side
+        by side (``weights`` says how much each member counts), never averaged."""
+        return [p.to_noise_catalogue(theta, X) for p in self.posteriors]
 
     # ---- posterior mode ---------------------------------------------------------------------
     def map_catalogue(self, X, num_iter=1000, num_to_optimize=100, learning_rate=0.01, init_method="posterior",
