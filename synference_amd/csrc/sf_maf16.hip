@@ -327,6 +327,35 @@ __global__ __launch_bounds__(256, (SPAN ? 3 : (PREC == 2 ? SF_SAMP16_WG_FUSED : 
     unsigned int g_t[TPW];
     f32x4& u_cur = u_t[0];
     unsigned int& gal_cur = g_t[0];
+    if constexpr (PREC == 2 && TPW == 2) {
+      // D <= 5: a draw is Philox blocks 0 and 1, so the wave's two tiles are ONE call -- lanes 0..31 (row groups 0, 1) draw blocks
+      // 0, 1 of tile 0, lanes 32..63 those of tile 1, and v_permlane32_swap hands the upper half's to row groups 0, 1 (lane L and
+      // lane L + 32 hold the same sample).  Row groups 2, 3 are padding.  Same counters (slot, attempt, block) per draw.
+      static_assert(DD >= 3 && DD <= 5, "paired Philox call: a draw is blocks 0 and 1, row groups 2 and 3 hold no dimension");
+      const int wi = ((g4 >> 1) * 4 + wave) * 16 + s;
+      const unsigned int n_ent = ctrl[0];
+      const int lgA = (int)ctrl[1];
+      const unsigned int e = (unsigned)wi >> lgA;
+      const unsigned int ee = e < n_ent ? e : 0u;
+      const uint32_t slot = ctrl[SF_Q_HDR + ee];
+      const uint32_t att = ctrl[SF_Q_HDR + IPW + ee] + ((unsigned)wi & ((1u << lgA) - 1u));
+      float z4[4];
+      sf_normal4(a.k0, a.k1, (uint64_t)slot + a.rng_slot_offset, att, (uint32_t)(g4 & 1), z4);
+      // (an element of the swap's result goes through a scalar before the bit cast: cast in place, element 1 read element 0)
+      const auto gsw = __builtin_amdgcn_permlane32_swap(slot / (uint32_t)a.S, slot / (uint32_t)a.S, false, false);
+      const unsigned int gal0 = gsw[0], gal1 = gsw[1];
+      g_t[0] = gal0;
+      g_t[1] = gal1;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const unsigned int zb = __builtin_bit_cast(unsigned int, z4[r]);
+        const auto zsw = __builtin_amdgcn_permlane32_swap(zb, zb, false, false);
+        const unsigned int z0 = zsw[0], z1 = zsw[1];   // every lane: the lower half's value | the upper half's
+        const bool on = g4 < 2 && 4 * g4 + r < m.D;
+        u_t[0][r] = on ? __builtin_bit_cast(float, z0) : 0.f;
+        u_t[1][r] = on ? __builtin_bit_cast(float, z1) : 0.f;
+      }
+    } else {
 #pragma unroll
     for (int j = TPW - 1; j >= 0; --j) {  // (j = 0 last: it is the first `cur`)
       const int wi = (j * 4 + wave) * 16 + s;
@@ -341,6 +370,7 @@ __global__ __launch_bounds__(256, (SPAN ? 3 : (PREC == 2 ? SF_SAMP16_WG_FUSED : 
 #pragma unroll
       for (int r = 0; r < 4; ++r) u_t[j][r] = (4 * g4 + r < m.D) ? z4[r] : 0.f;
       g_t[j] = slot / (uint32_t)a.S;
+    }
     }
     SfTiles16 tiles;
     if constexpr (DD == 0) tiles.pack(m);   // (the unrolled kernels know the tile of every pass: p - 2)
