@@ -16,3 +16,8 @@ for k in 0 1; do for h in 2; do
   echo "## sf_inst.hip SF_KIND=$k SF_HT=$h (the tile count of H = 50)"; hipcc $FLAGS -DSF_KIND=$k -DSF_HT=$h -c sf_inst.hip -o /dev/null 2>&1 | fmt
 done; done
 echo "## sf_train_inst.hip SF_HT=2"; hipcc $FLAGS -DSF_HT=2 -c sf_train_inst.hip -o /dev/null 2>&1 | fmt
+# the cooperative 16-row trainers: the six units of sf_trainc.hip (Makefile: TRC_TS) and sf_nsfc.hip
+for t in 5 6 8 15 16 18; do
+  echo "## sf_trainc.hip SF_TRC_TU=$t"; hipcc $FLAGS -DSF_TRC_TU=$t -c sf_trainc.hip -o /dev/null 2>&1 | fmt
+done
+echo "## sf_nsfc.hip"; hipcc $FLAGS -c sf_nsfc.hip -o /dev/null 2>&1 | fmt

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "sf_layout.h"
+#include "sf_trainc.h"   // (sf_trc_slots_needed: the part of the header that needs no HIP)
 
 namespace {
 
@@ -79,15 +80,24 @@ bool build(const Case& c, SfLayout& L) {
   return sf_build_layout(d, L);
 }
 
-// fragment slots the cooperative MAF trainer needs per masked layer and wave (c_slots_needed, sf_trainc.hip)
-int trc_slots(const SfTrcDev& c) {
-  int mx = 0;
-  for (int p = 0; 2 * p < c.NT; ++p) {
-    const int tA = p, tB = c.NT - 1 - p;
-    mx = std::max(mx, (c.kend[tA] + 1) + (tB > tA ? c.kend[tB] + 1 : 0));
-    mx = std::max(mx, (c.NT - c.kbeg[tA]) + (tB > tA ? c.NT - c.kbeg[tB] : 0));
+// gsrcC / gzeroC (the gather's tables) against gdstC: every parameter with a position appears exactly once in the position table,
+// at its position; every parameter without one exactly once in the zero list.  (Not digested: the golden file predates them.)
+bool gather_tables_consistent(const SfLayout& L) {
+  if (L.gsrcC.size() != (size_t)L.n_gradC * 2 || L.gdstC.size() != (size_t)L.n_params) return false;
+  std::vector<int> in_src((size_t)L.n_params, 0), in_zero((size_t)L.n_params, 0);
+  for (size_t k = 0; k < L.gsrcC.size(); ++k) {
+    const int32_t i = L.gsrcC[k];
+    if (i < 0) continue;
+    if (i >= L.n_params || L.gdstC[(size_t)i] != (int32_t)(k / 2)) return false;
+    ++in_src[(size_t)i];
   }
-  return mx;
+  for (int32_t i : L.gzeroC) {
+    if (i < 0 || i >= L.n_params) return false;
+    ++in_zero[(size_t)i];
+  }
+  for (size_t i = 0; i < (size_t)L.n_params; ++i)
+    if (in_src[i] != (L.gdstC[i] >= 0 ? 1 : 0) || in_zero[i] != (L.gdstC[i] >= 0 ? 0 : 1)) return false;
+  return true;
 }
 
 std::vector<Case> flow_cases() {
@@ -204,6 +214,10 @@ int main(int argc, char** argv) {
     std::printf("%s %s %" PRId64 " %" PRId64 " %" PRId64 " %" PRId64 " %" PRId64 " %" PRId64 " %" PRId64 " %" PRId64 " %016" PRIx64 " %s\n",
                 c.key().c_str(), ok ? "ok" : ("\"" + L.error + "\"").c_str(), L.n_params, L.n_packed, L.n_packedT, L.n_packedB,
                 L.n_packed16, L.n_packed16B, L.n_imgC, L.n_gradC, all.h, sig.c_str());
+    if (ok && (L.trc.ok || L.nsc.ok) && !gather_tables_consistent(L)) {
+      std::fprintf(stderr, "%s: gsrcC / gzeroC do not match gdstC\n", c.key().c_str());
+      return 1;
+    }
     const SfDev& v = L.dev;
     const bool maf = ok && c.kind == SF_MAF, nsf = ok && c.kind == SF_NSF;
     bool straddle = false;
@@ -217,7 +231,7 @@ int main(int argc, char** argv) {
       count(("compact_d" + std::to_string(D)).c_str(), maf && c.D == D && !L.src16c.empty() && !L.src16h.empty());
     for (int n = 1; n <= 4; ++n) count(("trc_nt" + std::to_string(n)).c_str(), maf && L.trc.ok && L.trc.NT == n);
     for (int n = 1; n <= 2; ++n) count(("trc_ni" + std::to_string(n)).c_str(), maf && L.trc.ok && L.trc.NI == n);
-    count("trc_span_slots6", maf && L.trc.ok && v.m16_span && trc_slots(L.trc) > 5);
+    count("trc_span_slots6", maf && L.trc.ok && v.m16_span && sf_trc_slots_needed(L.trc) > 5);
     count("nsc_otq6", nsf && L.nsc.ok && L.nsc.OTQ == 6);
     count("nsc_otq8", nsf && L.nsc.ok && L.nsc.OTQ == 8);
     count("nsc_nt5", nsf && L.nsc.ok && L.nsc.NT == 5);

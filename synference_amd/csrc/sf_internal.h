@@ -212,9 +212,9 @@ struct SfFlowTrain {   // the `train_ready` group (sf_train.hip)
 };
 struct SfFlowTrainC {  // the `trainc_ready` group: cooperative 16-row training path (sf_trainc.hip), operand image and gather tables
   SfBuf<float> d_imgC;
-  SfBuf<int32_t> d_sC1, d_sC2, d_gdstC;
-  SfBuf<int32_t> d_gsrcC;       // inverse of gdstC: [n_gradC][2] parameters fed by a position of the gradient partial (-1: none); null: not invertible
-  SfBuf<int32_t> d_gzeroC;      // parameters without a position (their gradient is 0)
+  SfBuf<int32_t> d_sC1, d_sC2;
+  SfBuf<int32_t> d_gsrcC;       // SfLayout::gsrcC: [n_gradC][2] parameters fed by a position of the gradient partial (-1: none)
+  SfBuf<int32_t> d_gzeroC;      // SfLayout::gzeroC: parameters without a position (their gradient is 0)
   long n_gzeroC = 0;
 };
 // transposed INFERENCE image of sf_flow_log_prob_grad (sf_gradtheta.hip): built from d_flat on the first gradient call after

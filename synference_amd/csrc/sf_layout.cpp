@@ -1151,6 +1151,20 @@ struct LayoutBuilder {
     L.n_imgC = (int64_t)L.srcC1.size();
     L.n_gradC = (int64_t)T * (L.trc.ok ? L.trc.g_stride : L.nsc.g_stride);
     L.gdstC.resize((size_t)P, -1);
+    // position -> parameter(s) for the gather.  A position feeds at most two parameters; a layout that maps more (none the
+    // builder emits) has no cooperative image at all and trains with the 32-row kernels
+    L.gsrcC.assign((size_t)L.n_gradC * 2, -1);
+    L.gzeroC.clear();
+    bool ok = true;
+    for (int64_t i = 0; i < P && ok; ++i) {
+      const int32_t g = L.gdstC[(size_t)i];
+      if (g < 0) { L.gzeroC.push_back((int32_t)i); continue; }
+      int32_t* slot = g < L.n_gradC ? &L.gsrcC[(size_t)g * 2] : nullptr;
+      if (slot && slot[0] < 0) slot[0] = (int32_t)i;
+      else if (slot && slot[1] < 0) slot[1] = (int32_t)i;
+      else ok = false;
+    }
+    if (!ok) { L.trc.ok = 0; L.nsc.ok = 0; L.gsrcC.clear(); L.gzeroC.clear(); }
   }
 
   // gradient image of the 32-row path: the first image copy of a parameter owns its gradient

@@ -204,6 +204,9 @@ struct SfLayout {
   SfNscDev nsc;                       // nsc.ok == 0: ... (NSF); srcC1 / srcC2 / gdstC / n_imgC / n_gradC are shared with trc
   std::vector<int32_t> srcC1, srcC2;  // its gather table (sum of two sources, like src1/src2)
   std::vector<int32_t> gdstC;         // logical parameter -> index in a gradient partial (or -1)
+  std::vector<int32_t> gsrcC;         // its inverse, [n_gradC][2]: the one or two parameters a position of the partial feeds (-1: none;
+                                      // b0 and bc share a position) -- the gather walks the partials in THEIR order (k_gather_c2)
+  std::vector<int32_t> gzeroC;        // parameters without a position (their gradient is 0)
   int64_t n_imgC = 0, n_gradC = 0;
   int64_t n_params = 0;
   int64_t n_packed = 0;  // floats in packed (== floats in packedT)

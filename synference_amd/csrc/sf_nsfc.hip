@@ -28,42 +28,20 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include "sf_device.h"
-#include "sf_fixacc.h"
+#include "sf_coop_tile.h"
 #include "sf_internal.h"
 #include "sf_nsfc.h"
 #include "sf_spline_flat.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-#define SF_MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
-
 namespace {
 
 constexpr int PBT = 272;  // floats of a padded B-layout tile: lane l's float4 at 4 l + 4 (l >> 4)
-constexpr int TT = 272;   // floats of a transposed tile: four sample groups of 68 (64 + 4 of padding: conflict-free writes)
 
-__device__ __forceinline__ f32x4 n_ld4(const float* p) {
-  const float4 b = *reinterpret_cast<const float4*>(p);
-  f32x4 r;
-  r[0] = b.x; r[1] = b.y; r[2] = b.z; r[3] = b.w;
-  return r;
-}
-__device__ __forceinline__ void n_st4(float* p, const f32x4 v) { *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); }
-__device__ __forceinline__ f32x4 n_zero() {
-  f32x4 z;
-  z[0] = 0.f; z[1] = 0.f; z[2] = 0.f; z[3] = 0.f;
-  return z;
-}
 __device__ __forceinline__ f32x4 n_relu(const f32x4 v) {
   f32x4 r;
 #pragma unroll
   for (int i = 0; i < 4; ++i) r[i] = fmaxf(v[i], 0.f);
   return r;
-}
-// weight fragment of block (a, b) of a [.][nb] block array (wave-uniform base, one shared per-lane offset)
-__device__ __forceinline__ float4 n_frag(const float* wp, int nb, int a, int b, int lane) {
-  const float4* base = reinterpret_cast<const float4*>(wp) + (a * nb + b) * 64;
-  return base[(unsigned)lane];
 }
 // one weight fragment through the tiles of both subtiles: two independent accumulator chains, their MFMAs alternating;
 // components [k0, kc) of the fragment are in use (rows k, 4 + k, 8 + k, 12 + k of the input tile: sf_layout.h)
@@ -80,61 +58,17 @@ __device__ __forceinline__ void n_mma1(const float4 w, const f32x4 in, f32x4& a0
   if (kc > 2) a0 = SF_MFMA16(w.z, in[2], a0);
   if (kc > 3) a1 = SF_MFMA16(w.w, in[3], a1);
 }
-// transposed tile: element (row, sample) at (sample >> 2) * 68 + row * 4 + (sample & 3); lane l = 16 kk + i then reads
-// row i, samples 4 kk .. 4 kk + 3 with one ds_read_b128 at kk * 68 + i * 4.  (68, not 64: the four ds_write_b32 of a lane
-// then hit 4 (s >> 2) + 16 g4 + (s & 3) + 4 r -- 64 different banks; with 64 the lanes s, s + 4, s + 8, s + 12 collided, 37 % of
-// the kernel's LDS cycles were bank conflicts.)
-__device__ __forceinline__ int n_T_rd(int lane) { return (lane >> 4) * 68 + (lane & 15) * 4; }
-__device__ __forceinline__ void n_put_T(float* tile, const f32x4 v, int s, int g4) {
-  float* p = tile + (s >> 2) * 68 + (s & 3) + 16 * g4;
-  p[0] = v[0]; p[4] = v[1]; p[8] = v[2]; p[12] = v[3];
-}
 __device__ __forceinline__ float n_sel4(int g, float a, float b, float c, float d) { return g == 0 ? a : (g == 1 ? b : (g == 2 ? c : d)); }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Weight-gradient blocks: acc[ro][ri] = sum over the 32 samples of delta[ot rows][s] * in[it rows][s].  The delta tile is read
 // TRANSPOSED out of its padded B layout (element (row i, sample sm) at 4 sm + 68 (i >> 2) + (i & 3): lane (i, kk) takes
-// samples 4 kk .. 4 kk + 3 with four ds_read_b32 that hit 64 different banks), the input tile with one ds_read_b128.
+// samples 4 kk .. 4 kk + 3 with four ds_read_b32 that hit 64 different banks), the input tile with one ds_read_b128
+// (CoopJob and the finish of a block: sf_coop_tile.h; here with the f32-atomic mode 2).
 // ---------------------------------------------------------------------------------------------------------------------
-struct NJob {
-  const float* Xd;  // padded B-layout delta tiles [.][2]
-  const float* Ti;  // transposed input tiles [.][2]
-  float* gw;        // gradient block (256 floats)
-  float* gb;        // bias gradient rows of tile ot (or null)
-  int ot, it;
-};
-__device__ __forceinline__ void n_dw_finish(const NJob& J, f32x4 acc, float bs, const SfAcc& A, int lane) {
-  // A.mode 0: plain store, 1: add to the workgroup's partial (later chunks), 2: f32 atomics into the XCD's replica,
-  // 3: fixed-point (int64) atomics into it
-  if (A.mode == 2) {
-    float* q = reinterpret_cast<float*>(A.fix) + (J.gw - A.base);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) sf_l2_add(q + r * 64 + lane, acc[r]);
-  } else if (A.mode == 3) {
-    long long* q = A.fix + (J.gw - A.base);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) sf_fix_add(q + r * 64 + lane, acc[r]);
-  } else {
-    if (A.mode == 1) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[r] += J.gw[r * 64 + lane];
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) J.gw[r * 64 + lane] = acc[r];
-  }
-  if (J.gb) {
-    bs += __shfl_xor(bs, 16, 64);
-    bs += __shfl_xor(bs, 32, 64);
-    if (lane < 16) {
-      if (A.mode == 2) sf_l2_add(reinterpret_cast<float*>(A.fix) + (J.gb - A.base) + J.ot * 16 + lane, bs);
-      else if (A.mode == 3) sf_fix_add(A.fix + (J.gb - A.base) + J.ot * 16 + lane, bs);
-      else J.gb[J.ot * 16 + lane] = A.mode == 1 ? J.gb[J.ot * 16 + lane] + bs : bs;
-    }
-  }
-}
-__device__ __forceinline__ void n_dw_jobs(const NJob& A, const NJob& B, bool two, const SfAcc& mode, int lane) {
+__device__ __forceinline__ void n_dw_jobs(const CoopJob& A, const CoopJob& B, bool two, const SfAcc& mode, int lane) {
   const int dofs = 16 * (lane >> 4) + 68 * ((lane & 15) >> 2) + (lane & 3);
-  f32x4 a0 = n_zero(), a1 = n_zero(), b0 = n_zero(), b1 = n_zero();
+  f32x4 a0 = coop_zero(), a1 = coop_zero(), b0 = coop_zero(), b1 = coop_zero();
   float bsA = 0.f, bsB = 0.f;
   if (two) {  // two blocks at once: four accumulator chains in flight
 #pragma unroll
@@ -143,8 +77,8 @@ __device__ __forceinline__ void n_dw_jobs(const NJob& A, const NJob& B, bool two
       const float* dB = B.Xd + (B.ot * 2 + q) * PBT + dofs;
       const float dA0 = dA[0], dA1 = dA[4], dA2 = dA[8], dA3 = dA[12];
       const float dB0 = dB[0], dB1 = dB[4], dB2 = dB[8], dB3 = dB[12];
-      const float4 iA = *reinterpret_cast<const float4*>(A.Ti + (A.it * 2 + q) * TT + n_T_rd(lane));
-      const float4 iB = *reinterpret_cast<const float4*>(B.Ti + (B.it * 2 + q) * TT + n_T_rd(lane));
+      const float4 iA = *reinterpret_cast<const float4*>(A.Ti + (A.it * 2 + q) * COOP_TT + coop_T_rd(lane));
+      const float4 iB = *reinterpret_cast<const float4*>(B.Ti + (B.it * 2 + q) * COOP_TT + coop_T_rd(lane));
       a0 = SF_MFMA16(dA0, iA.x, a0);
       b0 = SF_MFMA16(dB0, iB.x, b0);
       a1 = SF_MFMA16(dA1, iA.y, a1);
@@ -158,14 +92,14 @@ __device__ __forceinline__ void n_dw_jobs(const NJob& A, const NJob& B, bool two
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) { a0[r] += a1[r]; b0[r] += b1[r]; }
-    n_dw_finish(A, a0, bsA, mode, lane);
-    n_dw_finish(B, b0, bsB, mode, lane);
+    coop_dw_finish<true>(A, a0, bsA, mode, lane);
+    coop_dw_finish<true>(B, b0, bsB, mode, lane);
   } else {
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
       const float* dA = A.Xd + (A.ot * 2 + q) * PBT + dofs;
       const float dA0 = dA[0], dA1 = dA[4], dA2 = dA[8], dA3 = dA[12];
-      const float4 iA = *reinterpret_cast<const float4*>(A.Ti + (A.it * 2 + q) * TT + n_T_rd(lane));
+      const float4 iA = *reinterpret_cast<const float4*>(A.Ti + (A.it * 2 + q) * COOP_TT + coop_T_rd(lane));
       a0 = SF_MFMA16(dA0, iA.x, a0);
       a1 = SF_MFMA16(dA1, iA.y, a1);
       a0 = SF_MFMA16(dA2, iA.z, a0);
@@ -174,26 +108,11 @@ __device__ __forceinline__ void n_dw_jobs(const NJob& A, const NJob& B, bool two
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) a0[r] += a1[r];
-    n_dw_finish(A, a0, bsA, mode, lane);
+    coop_dw_finish<true>(A, a0, bsA, mode, lane);
   }
 }
 
 }  // namespace
-
-// argument block through the kernarg segment pointer, laundered where a phase starts (see k_maf_trainc)
-__device__ __forceinline__ const SfNscArgs& n_args() {
-  auto kp = __builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(kp));
-  return *(const SfNscArgs*)kp;
-}
-// workgroup barrier for LDS hand-overs: wait for the wave's own LDS operations only (outstanding global loads -- weight
-// fragments requested ahead -- stay in flight), then s_barrier
-__device__ __forceinline__ void n_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-  SF_FUZZ();
-}
 
 // NW waves: 4, or 5 when the flow has five hidden tiles (64 < H <= 80: the reference's production NSF has H = 69); one hidden
 // tile per wave.
@@ -208,7 +127,7 @@ __global__ __launch_bounds__(64 * (NT > 4 ? NT : 4), (NT > 4 ? 1 : 2)) void k_ns
   // units); five waves give whole tiles to the first waves
   constexpr int NEXT = NW == 4 ? (OTQ % 4) * 2 : OTQ % NW;
   using Spl = NSpl<KM, NQV>;
-  const SfNscArgs& a = n_args();
+  const SfNscArgs& a = sf_coop_args<SfNscArgs>();
   const SfNscDev& c = a.c;
   // wave = the wave's ROLE (tile ownership, spline wave of subtile `wave` for roles 0 and 1).  The second half of the grid
   // rotates the roles by two: the two workgroups that share a CU (w and w + grid / 2: the dispatcher fills every CU once
@@ -231,10 +150,10 @@ __global__ __launch_bounds__(64 * (NT > 4 ? NT : 4), (NT > 4 ? 1 : 2)) void k_ns
   float* XQ = XG + NT * NQ * PBT;        // spline-head outputs / their deltas [OTQ][NQ]
   float* XL = XQ + OTQ * NQ * PBT;       // LU deltas [2][NQ]
   float* TIN = XL + 2 * NQ * PBT;        // transposed: input tiles [NI][NQ]
-  float* TI = TIN + NI * NQ * TT;        // transposed layer inputs [NT][NQ], two buffers
-  float* TI2 = TI + NT * NQ * TT;
-  float* TL = TI2 + NT * NQ * TT;        // transposed LU inputs [2][NQ]
-  float* LUC = TL + 2 * NQ * TT;         // LU block of the current transform (144 floats)
+  float* TI = TIN + NI * NQ * COOP_TT;   // transposed layer inputs [NT][NQ], two buffers
+  float* TI2 = TI + NT * NQ * COOP_TT;
+  float* TL = TI2 + NT * NQ * COOP_TT;   // transposed LU inputs [2][NQ]
+  float* LUC = TL + 2 * NQ * COOP_TT;    // LU block of the current transform (144 floats)
   // per-sample state of the spline waves between their phases, [subtile][16 samples][24]: u (forward) / dL/du (backward) [0, 8),
   // u entering the transform [8, 16), the spline's outputs u' [16, 24).  (Held in registers, replicated over the four row
   // groups of a sample, they were 24-32 live VGPRs through every matrix phase of every wave.)
@@ -282,7 +201,7 @@ __global__ __launch_bounds__(64 * (NT > 4 ? NT : 4), (NT > 4 ? 1 : 2)) void k_ns
       }
       st8(0, u);
       for (int it = 0; it < NI; ++it) {
-        f32x4 e = n_zero();
+        f32x4 e = coop_zero();
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
           const int f = it == 0 ? (m - 2) * 4 + g4 : 8 + (it - 1) * 16 + 4 * m + g4;
@@ -295,21 +214,21 @@ __global__ __launch_bounds__(64 * (NT > 4 ? NT : 4), (NT > 4 ? 1 : 2)) void k_ns
           e[0] = n_sel4(g4, u[0], u[2], u[4], u[6]);
           e[1] = n_sel4(g4, u[1], u[3], u[5], u[7]);
         }
-        n_st4(XIN + (it * NQ + wave) * PBT + pbo, e);
-        n_put_T(TIN + (it * NQ + wave) * TT, e, s, g4);
+        coop_st4(XIN + (it * NQ + wave) * PBT + pbo, e);
+        coop_put_T(TIN + (it * NQ + wave) * COOP_TT, e, s, g4);
       }
     }
-    n_barrier();
+    coop_barrier();
 
     // The fragments of the HIDDEN layers (NT per phase) and their bias are requested ONE PHASE AHEAD, into the register set the
     // running phase does not use (wA / bA and wB / bB alternate): their L2 round trip hides behind the running phase's
     // products and the barrier.  Input-layer / gate fragments are requested at the top of their own phase (they are used after
     // the hidden product).  (Everything one phase ahead: 80 live registers, 200 spilled.)
     f32x4 h0[2], t1[2], t2[2], sg[2], t1b[2], t2b[2], sgb[2];
-    auto bias4 = [&](const float* tp, int off, int tile) { return n_ld4(tp + off + tile * 16 + 4 * g4); };
+    auto bias4 = [&](const float* tp, int off, int tile) { return coop_ld4(tp + off + tile * 16 + 4 * g4); };
     auto ld_hid = [&](const float* tp, int o_w, int o_b, float4 (&W)[NT], f32x4& b) {   // (unconditional: a wave without a tile
 #pragma unroll                                                                          //  loads tile 0's and drops them)
-      for (int it = 0; it < NT; ++it) W[it] = n_frag(tp + o_w, NT, j, it, lane);
+      for (int it = 0; it < NT; ++it) W[it] = coop_frag(tp + o_w, NT, j, it, lane);
       b = bias4(tp, o_b, j);
     };
     // acc[q] = b + W[j][:] . X[:][q] over the NT hidden input tiles
@@ -318,7 +237,7 @@ __global__ __launch_bounds__(64 * (NT > 4 ? NT : 4), (NT > 4 ? 1 : 2)) void k_ns
       acc1 = b;
 #pragma unroll
       for (int it = 0; it < NT; ++it) {
-        const f32x4 i0 = n_ld4(X + (it * NQ + 0) * PBT + pbo), i1 = n_ld4(X + (it * NQ + 1) * PBT + pbo);
+        const f32x4 i0 = coop_ld4(X + (it * NQ + 0) * PBT + pbo), i1 = coop_ld4(X + (it * NQ + 1) * PBT + pbo);
         n_mma2(W[it], i0, i1, acc0, acc1, it == NT - 1 ? kc_h : 4);
       }
     };
@@ -326,7 +245,7 @@ __global__ __launch_bounds__(64 * (NT > 4 ? NT : 4), (NT > 4 ? 1 : 2)) void k_ns
     auto ld_in = [&](const float* tp, int o_w, int o_b, float4 (&W)[3], f32x4& b) {
 #pragma unroll
       for (int it = 0; it < 3; ++it)
-        if (it < NI) W[it] = n_frag(tp + o_w, NI, j, it, lane);
+        if (it < NI) W[it] = coop_frag(tp + o_w, NI, j, it, lane);
       b = bias4(tp, o_b, j);
     };
     auto go_in = [&](const float4 (&W)[3], const f32x4 b, int k0, f32x4& acc0, f32x4& acc1) {
@@ -335,24 +254,24 @@ __global__ __launch_bounds__(64 * (NT > 4 ? NT : 4), (NT > 4 ? 1 : 2)) void k_ns
 #pragma unroll
       for (int it = 0; it < 3; ++it)
         if (it < NI) {
-          const f32x4 i0 = n_ld4(XIN + (it * NQ + 0) * PBT + pbo), i1 = n_ld4(XIN + (it * NQ + 1) * PBT + pbo);
+          const f32x4 i0 = coop_ld4(XIN + (it * NQ + 0) * PBT + pbo), i1 = coop_ld4(XIN + (it * NQ + 1) * PBT + pbo);
           n_mma2(W[it], i0, i1, acc0, acc1, kc_in(it), it == 0 ? k0 : 0);
         }
     };
     auto put2 = [&](float* X, const f32x4 v0, const f32x4 v1) {
-      n_st4(X + (j * NQ + 0) * PBT + pbo, v0);
-      n_st4(X + (j * NQ + 1) * PBT + pbo, v1);
+      coop_st4(X + (j * NQ + 0) * PBT + pbo, v0);
+      coop_st4(X + (j * NQ + 1) * PBT + pbo, v1);
     };
     auto putT2 = [&](float* Tb, const f32x4 v0, const f32x4 v1) {
-      n_put_T(Tb + (j * NQ + 0) * TT, v0, s, g4);
-      n_put_T(Tb + (j * NQ + 1) * TT, v1, s, g4);
+      coop_put_T(Tb + (j * NQ + 0) * COOP_TT, v0, s, g4);
+      coop_put_T(Tb + (j * NQ + 1) * COOP_TT, v1, s, g4);
     };
-    auto img_of = [&](int t) { const SfNscArgs& a = n_args(); return a.img + (size_t)t * a.c.t_stride + sf_opaque_zero(); };
+    auto img_of = [&](int t) { const SfNscArgs& a = sf_coop_args<SfNscArgs>(); return a.img + (size_t)t * a.c.t_stride + sf_opaque_zero(); };
 
     // F1 .. F6 of transform t: conditioner forward; leaves the head outputs in XQ.  bw: recomputation at the start of the
     // transform's backward sweep (also writes h2 transposed for the head's weight gradient).
     auto fwd_mat = [&](int t, bool bw) {
-      const SfNscArgs& a = n_args();
+      const SfNscArgs& a = sf_coop_args<SfNscArgs>();
       const SfNscDev& c = a.c;
       const float* tp = img_of(t);
       float4 wA[NT], wB[NT];
@@ -371,7 +290,7 @@ __global__ __launch_bounds__(64 * (NT > 4 ? NT : 4), (NT > 4 ? 1 : 2)) void k_ns
         }
       }
       SF_NC(300 + (bw ? 10 : 0) + 0);
-      n_barrier();
+      coop_barrier();
       SF_NC(300 + (bw ? 10 : 0) + 1);
       // F2: t1 = b1 + W1 relu(h0)
       ld_hid(tp, c.o_w2[0], c.o_b2[0], wA, bA);
@@ -379,7 +298,7 @@ __global__ __launch_bounds__(64 * (NT > 4 ? NT : 4), (NT > 4 ? 1 : 2)) void k_ns
         go_hid(wB, bB, XA, t1[0], t1[1]);
         put2(XB, n_relu(t1[0]), n_relu(t1[1]));
       }
-      n_barrier();
+      coop_barrier();
       SF_NC(300 + (bw ? 10 : 0) + 2);
       // F3: t2 = b2 + W2 relu(t1); gate = sigmoid(bg + Wg e); h1 = h0 + t2 * gate
       ld_hid(tp, c.o_w1[1], c.o_b1[1], wB, bB);
@@ -399,7 +318,7 @@ __global__ __launch_bounds__(64 * (NT > 4 ? NT : 4), (NT > 4 ? 1 : 2)) void k_ns
         }
         put2(XA, h1a, h1b);
       }
-      n_barrier();
+      coop_barrier();
       SF_NC(300 + (bw ? 10 : 0) + 3);
       // F4: t1' = b1' + W1' relu(h1)
       ld_hid(tp, c.o_w2[1], c.o_b2[1], wA, bA);
@@ -407,12 +326,12 @@ __global__ __launch_bounds__(64 * (NT > 4 ? NT : 4), (NT > 4 ? 1 : 2)) void k_ns
         go_hid(wB, bB, XA, t1b[0], t1b[1]);
         put2(XB, n_relu(t1b[0]), n_relu(t1b[1]));
       }
-      n_barrier();
+      coop_barrier();
       SF_NC(300 + (bw ? 10 : 0) + 4);
       // F5: t2' = b2' + W2' relu(t1'); gate'; h2 = h1 + t2' * gate'  (no activation in front of the head).  Ahead: the head
       // fragments of tile `wave` (both subtiles)
 #pragma unroll
-      for (int it = 0; it < NT; ++it) wB[it] = n_frag(tp + c.o_wout, NT, wave, it, lane);
+      for (int it = 0; it < NT; ++it) wB[it] = coop_frag(tp + c.o_wout, NT, wave, it, lane);
       bB = bias4(tp, c.o_bout, wave);
       if (has) {
         float4 wi[3];
@@ -431,7 +350,7 @@ __global__ __launch_bounds__(64 * (NT > 4 ? NT : 4), (NT > 4 ? 1 : 2)) void k_ns
         put2(XA, h2a, h2b);
         if (bw) putT2(TI2, h2a, h2b);
       }
-      n_barrier();
+      coop_barrier();
       SF_NC(300 + (bw ? 10 : 0) + 5);
       // F6: q = bout + Wout h2: tiles wave, wave + 4 for both subtiles; the remaining tiles one (tile, subtile) unit per wave
       {
@@ -440,45 +359,45 @@ __global__ __launch_bounds__(64 * (NT > 4 ? NT : 4), (NT > 4 ? 1 : 2)) void k_ns
         const int tile2 = NOWN > 1 ? wave + NW : (NW > 4 ? NW * NOWN + wave : 4 * NOWN + (wave >> 1));
         const bool do2 = NOWN > 1 || (NEXT > 0 && wave < NEXT);
         float4 w2[NT];
-        f32x4 b2 = n_zero();
+        f32x4 b2 = coop_zero();
         if (do2) {
 #pragma unroll
-          for (int it = 0; it < NT; ++it) w2[it] = n_frag(tp + c.o_wout, NT, tile2, it, lane);
+          for (int it = 0; it < NT; ++it) w2[it] = coop_frag(tp + c.o_wout, NT, tile2, it, lane);
           b2 = bias4(tp, c.o_bout, tile2);
         }
         f32x4 acc0 = bB, acc1 = bB;
 #pragma unroll
         for (int it = 0; it < NT; ++it) {
-          const f32x4 i0 = n_ld4(XA + (it * NQ + 0) * PBT + pbo), i1 = n_ld4(XA + (it * NQ + 1) * PBT + pbo);
+          const f32x4 i0 = coop_ld4(XA + (it * NQ + 0) * PBT + pbo), i1 = coop_ld4(XA + (it * NQ + 1) * PBT + pbo);
           n_mma2(wB[it], i0, i1, acc0, acc1, it == NT - 1 ? kc_h : 4);
         }
-        n_st4(XQ + (wave * NQ + 0) * PBT + pbo, acc0);
-        n_st4(XQ + (wave * NQ + 1) * PBT + pbo, acc1);
+        coop_st4(XQ + (wave * NQ + 0) * PBT + pbo, acc0);
+        coop_st4(XQ + (wave * NQ + 1) * PBT + pbo, acc1);
         if (do2) {
           if (OWN2) {
             acc0 = b2;
             acc1 = b2;
 #pragma unroll
             for (int it = 0; it < NT; ++it) {
-              const f32x4 i0 = n_ld4(XA + (it * NQ + 0) * PBT + pbo), i1 = n_ld4(XA + (it * NQ + 1) * PBT + pbo);
+              const f32x4 i0 = coop_ld4(XA + (it * NQ + 0) * PBT + pbo), i1 = coop_ld4(XA + (it * NQ + 1) * PBT + pbo);
               n_mma2(w2[it], i0, i1, acc0, acc1, it == NT - 1 ? kc_h : 4);
             }
-            n_st4(XQ + (tile2 * NQ + 0) * PBT + pbo, acc0);
-            n_st4(XQ + (tile2 * NQ + 1) * PBT + pbo, acc1);
+            coop_st4(XQ + (tile2 * NQ + 0) * PBT + pbo, acc0);
+            coop_st4(XQ + (tile2 * NQ + 1) * PBT + pbo, acc1);
           } else {
             const int sub = wave & 1;
             acc0 = b2;
-            acc1 = n_zero();
+            acc1 = coop_zero();
 #pragma unroll
-            for (int it = 0; it < NT; ++it) n_mma1(w2[it], n_ld4(XA + (it * NQ + sub) * PBT + pbo), acc0, acc1, it == NT - 1 ? kc_h : 4);
+            for (int it = 0; it < NT; ++it) n_mma1(w2[it], coop_ld4(XA + (it * NQ + sub) * PBT + pbo), acc0, acc1, it == NT - 1 ? kc_h : 4);
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc0[r] += acc1[r];
-            n_st4(XQ + (tile2 * NQ + sub) * PBT + pbo, acc0);
+            coop_st4(XQ + (tile2 * NQ + sub) * PBT + pbo, acc0);
           }
         }
       }
       SF_NC(300 + (bw ? 10 : 0) + 6);
-      n_barrier();
+      coop_barrier();
       SF_NC(300 + (bw ? 10 : 0) + 7);
     };
     // LU constants of the transform whose block sits in LUC
@@ -487,11 +406,11 @@ __global__ __launch_bounds__(64 * (NT > 4 ? NT : 4), (NT > 4 ? 1 : 2)) void k_ns
       for (int i = 0; i < 8; ++i) dg[i] = i < D ? sf_softplus(LUC[128 + i]) + a.lu_eps : 1.f;
     };
     auto write_in0 = [&](const float (&uu)[8]) {   // input tile 0 of my subtile: theta rows from uu, context rows as they are
-      f32x4 e = n_ld4(XIN + (0 * NQ + wave) * PBT + pbo);
+      f32x4 e = coop_ld4(XIN + (0 * NQ + wave) * PBT + pbo);
       e[0] = n_sel4(g4, uu[0], uu[2], uu[4], uu[6]);
       e[1] = n_sel4(g4, uu[1], uu[3], uu[5], uu[7]);
-      n_st4(XIN + (0 * NQ + wave) * PBT + pbo, e);
-      n_put_T(TIN + (0 * NQ + wave) * TT, e, s, g4);
+      coop_st4(XIN + (0 * NQ + wave) * PBT + pbo, e);
+      coop_put_T(TIN + (0 * NQ + wave) * COOP_TT, e, s, g4);
     };
     float* ust = a.ustash + ((size_t)(chunk * 32 + (spl ? wave : 0) * 16 + s) * T) * 16;
     // F7 (spline waves): spline on my (sample, transformed dimension g4), then LULinear on replicated registers.
@@ -502,7 +421,7 @@ __global__ __launch_bounds__(64 * (NT > 4 ? NT : 4), (NT > 4 ? 1 : 2)) void k_ns
       float q[NQV];
 #pragma unroll
       for (int jt = 0; jt < OTQ; ++jt) {
-        const f32x4 v = n_ld4(XQ + (jt * NQ + wave) * PBT + pbo);
+        const f32x4 v = coop_ld4(XQ + (jt * NQ + wave) * PBT + pbo);
         q[4 * jt] = v[0]; q[4 * jt + 1] = v[1]; q[4 * jt + 2] = v[2]; q[4 * jt + 3] = v[3];
       }
       ld8(0, u);
@@ -562,12 +481,12 @@ __global__ __launch_bounds__(64 * (NT > 4 ? NT : 4), (NT > 4 ? 1 : 2)) void k_ns
         float u[8], ui[8], up[8];
         fwd_spline(t, false, u, ui, up);
       }
-      n_barrier();
+      coop_barrier();
     }
 
     // ------------------------------------------------------------------ backward sweep (the top transform: first evaluation)
     for (int t = T - 1; t >= 0; --t) {
-      const SfNscArgs& a = n_args();
+      const SfNscArgs& a = sf_coop_args<SfNscArgs>();
       const SfNscDev& c = a.c;
       const float* tp = img_of(t);
       float* gp = gpart + (size_t)t * c.g_stride;
@@ -579,7 +498,7 @@ __global__ __launch_bounds__(64 * (NT > 4 ? NT : 4), (NT > 4 ? 1 : 2)) void k_ns
           ld8(8, ui);
           write_in0(ui);
         }
-        n_barrier();
+        coop_barrier();
       }
       fwd_mat(t, true);
       SF_NC(41 + 10 * (T - 1 - t));
@@ -642,16 +561,16 @@ __global__ __launch_bounds__(64 * (NT > 4 ? NT : 4), (NT > 4 ? 1 : 2)) void k_ns
           f32x4 v;
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] = n_sel4(g4, G[r], G[4 + r], z[r], z[4 + r]);
-          n_st4(XL + (0 * NQ + wave) * PBT + pbo, v);
+          coop_st4(XL + (0 * NQ + wave) * PBT + pbo, v);
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] = g4 == 0 ? dt[r] : (g4 == 1 ? dt[4 + r] : 0.f);
-          n_st4(XL + (1 * NQ + wave) * PBT + pbo, v);
+          coop_st4(XL + (1 * NQ + wave) * PBT + pbo, v);
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] = g4 == 0 ? tt[r] : (g4 == 1 ? tt[4 + r] : 0.f);
-          n_put_T(TL + (0 * NQ + wave) * TT, v, s, g4);
+          coop_put_T(TL + (0 * NQ + wave) * COOP_TT, v, s, g4);
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] = g4 == 0 ? up[r] : (g4 == 1 ? up[4 + r] : 0.f);
-          n_put_T(TL + (1 * NQ + wave) * TT, v, s, g4);
+          coop_put_T(TL + (1 * NQ + wave) * COOP_TT, v, s, g4);
         }
 #pragma unroll
         for (int p = 0; p < 8; ++p) G[p] = p < D ? Gn[p] : 0.f;
@@ -661,7 +580,7 @@ __global__ __launch_bounds__(64 * (NT > 4 ? NT : 4), (NT > 4 ? 1 : 2)) void k_ns
         float q[NQV], dq[NQV];
 #pragma unroll
         for (int jt = 0; jt < OTQ; ++jt) {
-          const f32x4 v = n_ld4(XQ + (jt * NQ + wave) * PBT + pbo);
+          const f32x4 v = coop_ld4(XQ + (jt * NQ + wave) * PBT + pbo);
           q[4 * jt] = v[0]; q[4 * jt + 1] = v[1]; q[4 * jt + 2] = v[2]; q[4 * jt + 3] = v[3];
         }
         const float vin = start ? n_sel4(g4, ui[1], ui[3], ui[5], ui[7]) : n_sel4(g4, ui[0], ui[2], ui[4], ui[6]);
@@ -674,7 +593,7 @@ __global__ __launch_bounds__(64 * (NT > 4 ? NT : 4), (NT > 4 ? 1 : 2)) void k_ns
           f32x4 v;
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] = have ? dq[4 * jt + r] : 0.f;
-          n_st4(XQ + (jt * NQ + wave) * PBT + pbo, v);
+          coop_st4(XQ + (jt * NQ + wave) * PBT + pbo, v);
         }
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
@@ -686,7 +605,7 @@ __global__ __launch_bounds__(64 * (NT > 4 ? NT : 4), (NT > 4 ? 1 : 2)) void k_ns
         st8(0, G);
         SF_NC(342);
       }
-      n_barrier();
+      coop_barrier();
       SF_NC(42 + 10 * (T - 1 - t));
       // generic job runner: blocks n = wave, wave + NW, ... of a list, two at a time
       // (atomic modes: the i-th workgroup of an XCD starts the list at block i -- the workgroups of an XCD run the same phase at about the same
@@ -696,7 +615,7 @@ __global__ __launch_bounds__(64 * (NT > 4 ? NT : 4), (NT > 4 ? 1 : 2)) void k_ns
         auto at = [&](int n) { const int m = n + rot; return m >= total ? m - total : m; };
         for (int n = wave; n < total; n += 2 * NW) {
           const bool two = n + NW < total;
-          const NJob A = mk(at(n)), B = mk(at(two ? n + NW : n));
+          const CoopJob A = mk(at(n)), B = mk(at(two ? n + NW : n));
           n_dw_jobs(A, B, two, mode, lane);
         }
       };
@@ -706,15 +625,15 @@ __global__ __launch_bounds__(64 * (NT > 4 ? NT : 4), (NT > 4 ? 1 : 2)) void k_ns
       auto ld_hidT = [&](int o_wT, float4 (&W)[NT]) {
         if (has) {
 #pragma unroll
-          for (int ot = 0; ot < NT; ++ot) W[ot] = n_frag(tp + o_wT, NT, j, ot, lane);
+          for (int ot = 0; ot < NT; ++ot) W[ot] = coop_frag(tp + o_wT, NT, j, ot, lane);
         }
       };
       auto go_hidT = [&](const float4 (&W)[NT], const float* X, f32x4& acc0, f32x4& acc1) {
-        acc0 = n_zero();
-        acc1 = n_zero();
+        acc0 = coop_zero();
+        acc1 = coop_zero();
 #pragma unroll
         for (int ot = 0; ot < NT; ++ot) {
-          const f32x4 i0 = n_ld4(X + (ot * NQ + 0) * PBT + pbo), i1 = n_ld4(X + (ot * NQ + 1) * PBT + pbo);
+          const f32x4 i0 = coop_ld4(X + (ot * NQ + 0) * PBT + pbo), i1 = coop_ld4(X + (ot * NQ + 1) * PBT + pbo);
           n_mma2(W[ot], i0, i1, acc0, acc1, ot == NT - 1 ? kc_h : 4);
         }
       };
@@ -724,24 +643,24 @@ __global__ __launch_bounds__(64 * (NT > 4 ? NT : 4), (NT > 4 ? 1 : 2)) void k_ns
         float4 wf[OTQ];
         if (has) {
 #pragma unroll
-          for (int ot = 0; ot < OTQ; ++ot) wf[ot] = n_frag(tp + c.o_woutT, OTQ, j, ot, lane);
+          for (int ot = 0; ot < OTQ; ++ot) wf[ot] = coop_frag(tp + c.o_woutT, OTQ, j, ot, lane);
         }
         const int nw = OTQ * NT;
-        run_jobs(nw + 2, [&](int n) -> NJob {
+        run_jobs(nw + 2, [&](int n) -> CoopJob {
           if (n < nw) {
             const int ot = n / NT, it = n - ot * NT;
-            return NJob{XQ, TI2, gp + c.g_wout + n * 256, it == 0 ? gp + c.g_bout : nullptr, ot, it};
+            return CoopJob{XQ, TI2, gp + c.g_wout + n * 256, it == 0 ? gp + c.g_bout : nullptr, ot, it};
           }
           const int b = n - nw;
-          return NJob{XL, TL, gp + c.g_lu + b * 256, b == 0 ? gp + c.g_lu + 512 : nullptr, b, b};
+          return CoopJob{XL, TL, gp + c.g_lu + b * 256, b == 0 ? gp + c.g_lu + 512 : nullptr, b, b};
         });
         SF_NC(350);
         if (has) {
-          dh[0] = n_zero();
-          dh[1] = n_zero();
+          dh[0] = coop_zero();
+          dh[1] = coop_zero();
 #pragma unroll
           for (int ot = 0; ot < OTQ; ++ot) {
-            const f32x4 i0 = n_ld4(XQ + (ot * NQ + 0) * PBT + pbo), i1 = n_ld4(XQ + (ot * NQ + 1) * PBT + pbo);
+            const f32x4 i0 = coop_ld4(XQ + (ot * NQ + 0) * PBT + pbo), i1 = coop_ld4(XQ + (ot * NQ + 1) * PBT + pbo);
             n_mma2(wf[ot], i0, i1, dh[0], dh[1], 4);
           }
           f32x4 d2[2], dgt[2];
@@ -758,7 +677,7 @@ __global__ __launch_bounds__(64 * (NT > 4 ? NT : 4), (NT > 4 ? 1 : 2)) void k_ns
         }
       }
       SF_NC(351);
-      n_barrier();
+      coop_barrier();
       SF_NC(43 + 10 * (T - 1 - t));
       // the two residual blocks, top down
 #pragma unroll
@@ -773,14 +692,14 @@ __global__ __launch_bounds__(64 * (NT > 4 ? NT : 4), (NT > 4 ? 1 : 2)) void k_ns
           float4 wf[NT];
           ld_hidT(o_w2T, wf);
           const int n2 = NT * NT;
-          run_jobs(n2 + NT * NI, [&](int n) -> NJob {
+          run_jobs(n2 + NT * NI, [&](int n) -> CoopJob {
             if (n < n2) {
               const int ot = n / NT, it = n - ot * NT;
-              return NJob{XB, TI, gp + g_w2 + n * 256, it == 0 ? gp + g_b2 : nullptr, ot, it};
+              return CoopJob{XB, TI, gp + g_w2 + n * 256, it == 0 ? gp + g_b2 : nullptr, ot, it};
             }
             const int m = n - n2;
             const int ot = m / NI, it = m - ot * NI;
-            return NJob{XG, TIN, gp + g_wg + m * 256, it == 0 ? gp + g_bg : nullptr, ot, it};
+            return CoopJob{XG, TIN, gp + g_wg + m * 256, it == 0 ? gp + g_bg : nullptr, ot, it};
           });
           SF_NC(360 + 10 * kk);
           if (has) {
@@ -802,16 +721,16 @@ __global__ __launch_bounds__(64 * (NT > 4 ? NT : 4), (NT > 4 ? 1 : 2)) void k_ns
           }
         }
         SF_NC(361 + 10 * kk);
-        n_barrier();
+        coop_barrier();
         SF_NC(362 + 10 * kk);
         // B3 / B5: gradient at the block's input; (block 1) deltas of block 0's second layer and gate; weight gradients
         // of the block's first layer
         {
           float4 wf[NT];
           ld_hidT(o_w1T, wf);
-          run_jobs(NT * NT, [&](int n) -> NJob {
+          run_jobs(NT * NT, [&](int n) -> CoopJob {
             const int ot = n / NT, it = n - ot * NT;
-            return NJob{XA, TI2, gp + g_w1 + n * 256, it == 0 ? gp + g_b1 : nullptr, ot, it};
+            return CoopJob{XA, TI2, gp + g_w1 + n * 256, it == 0 ? gp + g_b1 : nullptr, ot, it};
           });
           SF_NC(363 + 10 * kk);
           if (has) {
@@ -843,7 +762,7 @@ __global__ __launch_bounds__(64 * (NT > 4 ? NT : 4), (NT > 4 ? 1 : 2)) void k_ns
           }
         }
         SF_NC(364 + 10 * kk);
-        n_barrier();
+        coop_barrier();
         SF_NC(365 + 10 * kk);
       }
       SF_NC(44 + 10 * (T - 1 - t));
@@ -851,18 +770,18 @@ __global__ __launch_bounds__(64 * (NT > 4 ? NT : 4), (NT > 4 ? 1 : 2)) void k_ns
       // spline waves: u / u' of the transform below (used in B7 and in its backward sweep)
       {
         float4 w = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (has) w = n_frag(tp + c.o_winT, NT, 0, j, lane);
+        if (has) w = coop_frag(tp + c.o_winT, NT, 0, j, lane);
         float4 s0 = w, s1 = w, s2 = w, s3 = w;
-        run_jobs(NT * NI, [&](int n) -> NJob {
+        run_jobs(NT * NI, [&](int n) -> CoopJob {
           const int ot = n / NI, it = n - ot * NI;
-          return NJob{XB, TIN, gp + c.g_win + n * 256, it == 0 ? gp + c.g_bin : nullptr, ot, it};
+          return CoopJob{XB, TIN, gp + c.g_win + n * 256, it == 0 ? gp + c.g_bin : nullptr, ot, it};
         });
         if (spl && t > 0) {
           const float4* srcp = reinterpret_cast<const float4*>(ust + (t - 1) * 16);
           s0 = srcp[0]; s1 = srcp[1]; s2 = srcp[2]; s3 = srcp[3];
         }
         if (has) {
-          f32x4 p0 = n_zero(), p1 = n_zero();
+          f32x4 p0 = coop_zero(), p1 = coop_zero();
           n_mma2(w, dh[0], dh[1], p0, p1, j == NT - 1 ? kc_h : 4);
           put2(XA, p0, p1);
         }
@@ -871,7 +790,7 @@ __global__ __launch_bounds__(64 * (NT > 4 ? NT : 4), (NT > 4 ? 1 : 2)) void k_ns
           *reinterpret_cast<float4*>(sst + 16) = s2; *reinterpret_cast<float4*>(sst + 20) = s3;
         }
       }
-      n_barrier();
+      coop_barrier();
       SF_NC(45 + 10 * (T - 1 - t));
       // B7 (spline waves): dL/du of the transform below = what came through the spline / the identity + Win^T delta
       if (spl) {
@@ -890,7 +809,7 @@ __global__ __launch_bounds__(64 * (NT > 4 ? NT : 4), (NT > 4 ? 1 : 2)) void k_ns
         st8(0, G);
       }
     }
-    n_barrier();  // the last reads of XA / XIN are done before the next chunk's inputs are written
+    coop_barrier();  // the last reads of XA / XIN are done before the next chunk's inputs are written
     SF_NC(200);
   }
 }
@@ -898,7 +817,7 @@ __global__ __launch_bounds__(64 * (NT > 4 ? NT : 4), (NT > 4 ? 1 : 2)) void k_ns
 // ---------------------------------------------------------------------------------------------------------------------
 size_t sf_nsfc_lds_bytes(const SfNscDev& c) {
   const size_t pb = (size_t)(c.NI + 3 * c.NT + c.OTQ + 2) * 2 * PBT;
-  const size_t tt = (size_t)(c.NI + 2 * c.NT + 2) * 2 * TT;
+  const size_t tt = (size_t)(c.NI + 2 * c.NT + 2) * 2 * COOP_TT;
   return (pb + tt + 160 + 2 * 16 * 24) * sizeof(float);
 }
 
@@ -910,13 +829,7 @@ bool sf_nsfc_eligible(const SfLayout& L, bool want_dctx) {
 }
 
 int sf_nsfc_grid(long B, int NT) {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    hipDeviceProp_t pr;
-    cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0)
-              ? pr.multiProcessorCount : 256;
-  }
+  const int cus = sf_coop_cus();
   const long chunks = (B + 31) / 32, cap = (NT > 4 ? 1L : 2L) * cus;   // (five-wave workgroups: one per CU)
   return (int)(chunks < cap ? chunks : cap);
 }
@@ -956,28 +869,9 @@ static hipError_t n_launch(const SfNscArgs& a, int grid, hipStream_t st) {
   }
   const size_t sh = sf_nsfc_lds_bytes(a.c);
 #ifdef SF_NSC_TRACE
-  {
-    static unsigned long long* d_tr = nullptr;
-    if (!d_tr && hipMalloc(&d_tr, 4 * 512 * 8) != hipSuccess) return hipErrorOutOfMemory;
-    (void)hipMemsetAsync(d_tr, 0, 4 * 512 * 8, st);
-    SfNscArgs b = a;
-    b.trace = d_tr;
+  return sf_coop_trace_launch(a, grid, st, NT > 4 ? NT : 4, 512, "nsfc", [&](const SfNscArgs& b) {
     hipLaunchKernelGGL((k_nsf_trainc<NT, OTQ>), dim3((unsigned)grid), dim3(64 * (NT > 4 ? NT : 4)), sh, st, b);
-    (void)hipStreamSynchronize(st);
-    static unsigned long long h[4 * 512];
-    (void)hipMemcpy(h, d_tr, sizeof(h), hipMemcpyDeviceToHost);
-    static int calls = 0;
-    if (++calls % 8 == 0) {
-      fprintf(stderr, "[nsfc trace] B=%ld grid=%d (units of 100 cycles since stamp 0 of wave 0)\n", a.B, grid);
-      for (int w = 0; w < 4; ++w) {
-        fprintf(stderr, "  wave %d:", w);
-        for (int i = 0; i < 512; ++i)
-          if (h[w * 512 + i]) fprintf(stderr, " %d:%.1f", i, (double)(long long)(h[w * 512 + i] - h[0]) * 0.01);
-        fprintf(stderr, "\n");
-      }
-    }
-    return hipGetLastError();
-  }
+  });
 #endif
   hipLaunchKernelGGL((k_nsf_trainc<NT, OTQ>), dim3((unsigned)grid), dim3(64 * (NT > 4 ? NT : 4)), sh, st, a);
   return hipGetLastError();

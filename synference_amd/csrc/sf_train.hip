@@ -285,25 +285,10 @@ static int ensure_trainc(sf_flow* f) {   // the cooperative kernels' image and g
   SF_TRY_SET(c.d_sC2.alloc((size_t)L.n_imgC));
   SF_TRY_SET(hipMemcpy(c.d_sC1, L.srcC1.data(), (size_t)L.n_imgC * sizeof(int32_t), hipMemcpyHostToDevice));
   SF_TRY_SET(hipMemcpy(c.d_sC2, L.srcC2.data(), (size_t)L.n_imgC * sizeof(int32_t), hipMemcpyHostToDevice));
-  SF_TRY_SET(c.d_gdstC.alloc((size_t)L.n_params));
-  SF_TRY_SET(hipMemcpy(c.d_gdstC, L.gdstC.data(), (size_t)L.n_params * sizeof(int32_t), hipMemcpyHostToDevice));
-  // position -> parameter(s), for the gather that walks the partials in THEIR order (coalesced reads): a position
-  // feeds at most two parameters (b0 and bc share one); if the packer ever maps more, the parameter-order gather stays
-  std::vector<int32_t> inv((size_t)L.n_gradC * 2, -1), zero;
-  bool ok = true;
-  for (long i = 0; i < (long)L.n_params && ok; ++i) {
-    const int32_t g = L.gdstC[(size_t)i];
-    if (g < 0) { zero.push_back((int32_t)i); continue; }
-    if (g >= (int32_t)L.n_gradC) { ok = false; break; }
-    if (inv[(size_t)g * 2] < 0) inv[(size_t)g * 2] = (int32_t)i;
-    else if (inv[(size_t)g * 2 + 1] < 0) inv[(size_t)g * 2 + 1] = (int32_t)i;
-    else ok = false;
-  }
-  if (ok) {
-    SF_TRY_SET(c.d_gsrcC.upload(inv));
-    c.n_gzeroC = (long)zero.size();
-    if (!zero.empty()) SF_TRY_SET(c.d_gzeroC.upload(zero));
-  }
+  // position -> parameter(s) and the parameters without a position (sf_layout.cpp): the gather walks the partials in THEIR order
+  SF_TRY_SET(c.d_gsrcC.upload(L.gsrcC));
+  c.n_gzeroC = (long)L.gzeroC.size();
+  if (!L.gzeroC.empty()) SF_TRY_SET(c.d_gzeroC.upload(L.gzeroC));
   static_cast<SfFlowTrainC&>(*f) = std::move(c);
   f->trainc_ready = true;
   return SF_OK;
@@ -355,10 +340,9 @@ static int coop_loss_grad(sf_flow* f, bool coop_nsf, const float* flat, const fl
   const int grid = coop_nsf ? sf_nsfc_grid(B, L.nsc.NT) : sf_trainc_grid(B, &L.trc, v.T);
   // Gradient accumulation (sf_fixacc.h): per-workgroup partials + gather while they are few, above that 2^-40 fixed-point
   // contributions added with int64 atomics into one zeroed replica per XCD (L2-resident, order independent).  The gather
-  // needs the position -> parameter table (d_gsrcC); SF_GRAD_ACC=partial | fix forces one form.
+  // reads the position -> parameter table (d_gsrcC) either way; SF_GRAD_ACC=partial | fix forces one form.
   const int nsf_mode = coop_nsf ? sf_nsfc_acc_mode(B, grid, (long)L.n_gradC) : 0;
-  bool use_fix = coop_nsf ? nsf_mode != 0 : sf_trainc_fix(grid, (long)L.n_gradC);
-  if (!f->d_gsrcC) use_fix = false;
+  const bool use_fix = coop_nsf ? nsf_mode != 0 : sf_trainc_fix(grid, (long)L.n_gradC);
   if (use_fix && !f->d_gfixC) SF_TRY_SET(f->d_gfixC.alloc((size_t)SF_FIX_REPLICAS * (size_t)L.n_gradC));
   if (use_fix) SF_TRY_SET(hipMemsetAsync(f->d_gfixC, 0, (size_t)SF_FIX_REPLICAS * (size_t)L.n_gradC * sizeof(long long), st));
   const int n_part = use_fix ? 1 : grid;   // (fix: d_gpartC is only the base the job descriptors count from)
@@ -420,13 +404,11 @@ static int coop_loss_grad(sf_flow* f, bool coop_nsf, const float* flat, const fl
     rc = bracketed(f, st, [&]() -> int { SF_TRY_SET(sf_launch_maf_trainc(a, grid, st)); return SF_OK; });
   }
   if (rc) return rc;
-  // the gather: float replicas (NSF only: the partial gather over SF_FIX_REPLICAS images), fixed point, partials by position, partials
-  // by parameter
+  // the gather: float replicas (NSF only: the partial gather over SF_FIX_REPLICAS images), fixed point, partials by position
   if (use_fix && nsf_mode == 2)
     SF_TRY_SET(sf_launch_gather_c2(reinterpret_cast<const float*>(f->d_gfixC.get()), (long)L.n_gradC, SF_FIX_REPLICAS, f->d_gsrcC, f->d_gzeroC, f->n_gzeroC, grad, st, sq_for(f, L)));
   else if (use_fix) SF_TRY_SET(sf_launch_gather_fix(f->d_gfixC, (long)L.n_gradC, SF_FIX_REPLICAS, f->d_gsrcC, f->d_gzeroC, f->n_gzeroC, grad, st));
-  else if (f->d_gsrcC) SF_TRY_SET(sf_launch_gather_c2(f->d_gpartC, (long)L.n_gradC, n_part, f->d_gsrcC, f->d_gzeroC, f->n_gzeroC, grad, st, sq_for(f, L)));
-  else SF_TRY_SET(sf_launch_gather_c(f->d_gpartC, (long)L.n_gradC, n_part, f->d_gdstC, grad, (long)L.n_params, st));
+  else SF_TRY_SET(sf_launch_gather_c2(f->d_gpartC, (long)L.n_gradC, n_part, f->d_gsrcC, f->d_gzeroC, f->n_gzeroC, grad, st, sq_for(f, L)));
   return SF_OK;
 }
 

@@ -12,7 +12,7 @@
 //     transform), u and the head outputs (a few floats per sample) in LDS; h0 is recomputed (one 16-row product);
 //   * weight gradients are products over all 64 samples (K = 64: delta and input tiles transposed through LDS once per
 //     layer, read back with conflict-free ds_read_b128), spread over the eight waves, and written with PLAIN stores
-//     into the workgroup's own gradient partial: no atomics, no zeroing pass, bitwise reproducible; k_gather_c sums
+//     into the workgroup's own gradient partial: no atomics, no zeroing pass, bitwise reproducible; k_gather_c2 sums
 //     the partials in a fixed order.  A workgroup that is given several chunks adds into its partial.
 //   * weight fragments come straight from L2 (each wave needs 4-5 KB per layer), issued a phase ahead.
 // Tile = 16 rows x 16 samples in 4 VGPRs: lane l = sample (l & 15) + 16 * row group (l >> 4), register r = row
@@ -22,8 +22,7 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include "sf_device.h"
-#include "sf_fixacc.h"
+#include "sf_coop_tile.h"
 #include "sf_internal.h"
 #include "sf_trainc.h"
 
@@ -35,9 +34,6 @@
 #endif
 #define SF_TRC_TS_OF_TU (SF_TRC_TU % 10)
 #define SF_TRC_NFS_OF_TU (SF_TRC_TU >= 10 ? 8 : 5)
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-#define SF_MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
 namespace {
 
@@ -59,28 +55,6 @@ __device__ __forceinline__ void c_mma2(const float4 wa, const f32x4 ina, f32x4& 
   acca = SF_MFMA16(wa.w, ina[3], acca);
   accb = SF_MFMA16(wb.w, inb[3], accb);
 }
-__device__ __forceinline__ f32x4 c_ld4(const float* p) {
-  const float4 b = *reinterpret_cast<const float4*>(p);
-  f32x4 r;
-  r[0] = b.x; r[1] = b.y; r[2] = b.z; r[3] = b.w;
-  return r;
-}
-__device__ __forceinline__ void c_st4(float* p, const f32x4 v) {
-  *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-}
-// weight fragment of block (a, b) of a [.][nb] block array
-// (block index first, as a wave-uniform 64-bit base; the lane enters as an unsigned 32-bit offset: the load then takes
-//  the SGPR-base + VGPR-offset form and every fragment address shares ONE per-lane register)
-__device__ __forceinline__ float4 c_frag(const float* wp, int nb, int a, int b, int lane) {
-  const float4* base = reinterpret_cast<const float4*>(wp) + (a * nb + b) * 64;
-  return base[(unsigned)lane];
-}
-__device__ __forceinline__ f32x4 c_zero() {
-  f32x4 z;
-  z[0] = 0.f; z[1] = 0.f; z[2] = 0.f; z[3] = 0.f;
-  return z;
-}
-
 // One block product split over two partial accumulators (k-steps 0, 2 -> acc0; 1, 3 -> acc1): two MFMAs on one accumulator
 // are always two issues apart, so the 40-cycle dependent latency of v_mfma_f32_16x16x4_f32 (issue: 32) never stalls the
 // wave, without any extra control flow.  The caller adds the partials once per layer.
@@ -92,17 +66,7 @@ __device__ __forceinline__ void c_mma_alt(const float4 w, const f32x4 in, f32x4&
 }
 // LDS tile addressing: a tile (16 rows x 16 samples of subtile q) is 256 floats
 //   B layout: lane l holds float4 at l*4 (rows 4*(l>>4)+r of sample l&15): the MFMA B operand of a data product
-//   T layout: [sample >> 2][row][sample & 3]: lane l = 16*kk + i reads float4 at l*4 = row i, samples 4kk..4kk+3:
-//             A / B operand of a weight-gradient product (k = sample)
-//   (round 4: sample groups of 68 floats, not 64 -- TTS = 272 floats per tile: the four ds_write_b32 of a lane then hit
-//   4 (s >> 2) + 16 g4 + (s & 3) + 4 r = 64 different banks; with 64 the lanes s, s + 4, s + 8, s + 12 collided and 41 % of the
-//   kernel's LDS cycles were bank conflicts, profiles/r03_pmc_summary.json)
-#define TTS 272
-__device__ __forceinline__ int c_T_rd(int lane) { return (lane >> 4) * 68 + (lane & 15) * 4; }
-__device__ __forceinline__ void c_put_T(float* tile, const f32x4 v, int s, int g4) {
-  float* p = tile + (s >> 2) * 68 + (s & 3) + 16 * g4;
-  p[0] = v[0]; p[4] = v[1]; p[8] = v[2]; p[12] = v[3];
-}
+//   T layout: the transposed tile of sf_coop_tile.h (COOP_TT floats): A / B operand of a weight-gradient product (k = sample)
 __device__ __forceinline__ float c_scale(int scale_fn, float av, float eps) {
   return (scale_fn == 0 ? sf_softplus(av) : sf_sigmoid(av + 2.0f)) + eps;
 }
@@ -112,49 +76,20 @@ __device__ __forceinline__ float c_dscale(int scale_fn, float av) {
   return sg * (1.0f - sg);
 }
 
-// Weight-gradient blocks: acc = sum over the 64 samples of delta[ot rows][s] * in[it rows][s]; plain store (first chunk
-// of the workgroup) or add into the workgroup's partial.  gb != nullptr: also the bias gradient of tile ot.  A wave that
-// holds two blocks of a batch runs them together (independent accumulators hide the MFMA's dependent latency).
-struct CJob {
-  const float* Td;
-  const float* Ti;
-  float* gw;
-  float* gb;
-  int ot, it;
-};
-__device__ __forceinline__ void c_dw_finish(const CJob& J, f32x4 acc, float bs, const SfAcc& A, int lane) {
-  if (A.mode == 3) {  // fixed-point atomics into the XCD's replica (sf_fixacc.h)
-    long long* q = A.fix + (J.gw - A.base);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) sf_fix_add(q + r * 64 + lane, acc[r]);
-  } else {
-    if (A.mode == 1) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[r] += J.gw[r * 64 + lane];
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) J.gw[r * 64 + lane] = acc[r];
-  }
-  if (J.gb) {
-    bs += __shfl_xor(bs, 16, 64);
-    bs += __shfl_xor(bs, 32, 64);
-    if (lane < 16) {
-      if (A.mode == 3) sf_fix_add(A.fix + (J.gb - A.base) + J.ot * 16 + lane, bs);
-      else J.gb[J.ot * 16 + lane] = A.mode == 1 ? J.gb[J.ot * 16 + lane] + bs : bs;
-    }
-  }
-}
+// Weight-gradient blocks (CoopJob, sf_coop_tile.h): acc = sum over the 64 samples of delta[ot rows][s] * in[it rows][s], both
+// operands from transposed tiles with one ds_read_b128 each.  A wave that holds two blocks of a batch runs them together
+// (independent accumulators hide the MFMA's dependent latency).
 template <int NQ>
-__device__ __forceinline__ void c_dw_jobs(const CJob& A, const CJob& B, bool two, const SfAcc& accumulate, int lane) {
-  f32x4 accA = c_zero(), accB = c_zero();
+__device__ __forceinline__ void c_dw_jobs(const CoopJob& A, const CoopJob& B, bool two, const SfAcc& accumulate, int lane) {
+  f32x4 accA = coop_zero(), accB = coop_zero();
   float bsA = 0.f, bsB = 0.f;
   if (two) {  // (two blocks at once: their chains alternate, the 40-cycle dependent latency of the MFMA is hidden)
 #pragma unroll 2
     for (int q = 0; q < NQ; ++q) {  // (two subtiles' operands in flight at a time: 32 registers, not 64)
-      const float4 dA = *reinterpret_cast<const float4*>(A.Td + (A.ot * NQ + q) * TTS + c_T_rd(lane));
-      const float4 iA = *reinterpret_cast<const float4*>(A.Ti + (A.it * NQ + q) * TTS + c_T_rd(lane));
-      const float4 dB = *reinterpret_cast<const float4*>(B.Td + (B.ot * NQ + q) * TTS + c_T_rd(lane));
-      const float4 iB = *reinterpret_cast<const float4*>(B.Ti + (B.it * NQ + q) * TTS + c_T_rd(lane));
+      const float4 dA = *reinterpret_cast<const float4*>(A.Xd + (A.ot * NQ + q) * COOP_TT + coop_T_rd(lane));
+      const float4 iA = *reinterpret_cast<const float4*>(A.Ti + (A.it * NQ + q) * COOP_TT + coop_T_rd(lane));
+      const float4 dB = *reinterpret_cast<const float4*>(B.Xd + (B.ot * NQ + q) * COOP_TT + coop_T_rd(lane));
+      const float4 iB = *reinterpret_cast<const float4*>(B.Ti + (B.it * NQ + q) * COOP_TT + coop_T_rd(lane));
       accA = SF_MFMA16(dA.x, iA.x, accA);
       accB = SF_MFMA16(dB.x, iB.x, accB);
       accA = SF_MFMA16(dA.y, iA.y, accA);
@@ -166,13 +101,13 @@ __device__ __forceinline__ void c_dw_jobs(const CJob& A, const CJob& B, bool two
       bsA += (dA.x + dA.y) + (dA.z + dA.w);
       bsB += (dB.x + dB.y) + (dB.z + dB.w);
     }
-    c_dw_finish(A, accA, bsA, accumulate, lane);
-    c_dw_finish(B, accB, bsB, accumulate, lane);
+    coop_dw_finish<false>(A, accA, bsA, accumulate, lane);
+    coop_dw_finish<false>(B, accB, bsB, accumulate, lane);
   } else {  // one block: two partial accumulators over alternating k-steps, for the same reason
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
-      const float4 dA = *reinterpret_cast<const float4*>(A.Td + (A.ot * NQ + q) * TTS + c_T_rd(lane));
-      const float4 iA = *reinterpret_cast<const float4*>(A.Ti + (A.it * NQ + q) * TTS + c_T_rd(lane));
+      const float4 dA = *reinterpret_cast<const float4*>(A.Xd + (A.ot * NQ + q) * COOP_TT + coop_T_rd(lane));
+      const float4 iA = *reinterpret_cast<const float4*>(A.Ti + (A.it * NQ + q) * COOP_TT + coop_T_rd(lane));
       accA = SF_MFMA16(dA.x, iA.x, accA);
       accB = SF_MFMA16(dA.y, iA.y, accB);
       accA = SF_MFMA16(dA.z, iA.z, accA);
@@ -181,30 +116,11 @@ __device__ __forceinline__ void c_dw_jobs(const CJob& A, const CJob& B, bool two
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) accA[r] += accB[r];
-    c_dw_finish(A, accA, bsA, accumulate, lane);
+    coop_dw_finish<false>(A, accA, bsA, accumulate, lane);
   }
 }
 
 }  // namespace
-
-// The argument block is read through the kernarg segment pointer, laundered where a phase starts: descriptor fields
-// are then scalar loads next to their use (scalar-cache hits) instead of ~80 SGPRs held -- and spilled -- for the
-// life of the kernel (same device as k_maf_samp16).
-__device__ __forceinline__ const SfTrcArgs& c_args() {
-  auto kp = __builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(kp));
-  return *(const SfTrcArgs*)kp;
-}
-
-// Workgroup barrier for the LDS hand-overs.  __syncthreads() carries a workgroup-scope fence that also drains the
-// wave's outstanding GLOBAL loads (s_waitcnt vmcnt(0)): every weight fragment issued a phase ahead would be waited for
-// at the very next barrier.  The exchanged data is LDS only: wait for the wave's own LDS operations, then s_barrier.
-__device__ __forceinline__ void c_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-  SF_FUZZ();
-}
 
 // Block offsets of the cooperative image and of a gradient partial: functions of (NT, NI) alone (sf_layout.cpp emits the blocks
 // in this order; sf_trainc_eligible checks the descriptor against these formulas), so the kernel carries them as
@@ -265,7 +181,7 @@ __global__ __launch_bounds__(256 * NG, SF_TRC_WGS(NG)) void k_maf_trainc(SfTrcAr
   constexpr int NQ = 2 * NG, NW = 4 * NG, NTH = 256 * NG;
   constexpr int NP = (NT + 1) / 2;  // wave rows (p) that own tiles
   using L = CLay<NT, NI>;
-  const SfTrcArgs& a = c_args();
+  const SfTrcArgs& a = sf_coop_args<SfTrcArgs>();
   const SfTrcDev& c = a.c;
   // (the wave index is made visibly wave-uniform: tile indices, buffer bases and fragment bases then live in SGPRs and the
   //  per-lane address part is one register)
@@ -292,15 +208,15 @@ __global__ __launch_bounds__(256 * NG, SF_TRC_WGS(NG)) void k_maf_trainc(SfTrcAr
   constexpr int HSZ = NT * NQ * 256;     // one hidden-size tensor: NT tiles x NQ subtiles x 256
   float* XBa = lds;                      // B layout: h0 (fwd) / dpre2 (bwd); backward partial sums of du
   float* XBb = XBa + HSZ;                // B layout: a1 (fwd) / dpre1 (bwd)
-  constexpr int HST = NT * NQ * TTS;     // ... in the (padded) T layout
+  constexpr int HST = NT * NQ * COOP_TT;     // ... in the (padded) T layout
   float* TB0 = XBb + HSZ;                // T layout x5: TD2, TA2 (later TD0), TH0, TD1, TA1; forward: head partial sums
   float* TD2 = TB0, *TA2 = TB0 + HST, *TH0 = TB0 + 2 * HST, *TD1 = TB0 + 3 * HST, *TA1 = TB0 + 4 * HST;
   float* TD0 = TA2;
   float* PBf = TB0;                      // [NP][NQ] tiles
   float* PBb = XBa;                      // [NP][NQ] tiles
   float* TDF = TB0 + 5 * HST;            // T layout: head delta, 1 tile x NQ
-  float* TIN = TDF + NQ * TTS;           // T layout: input tiles, NI tiles x NQ
-  float* USt = TIN + NI * NQ * TTS;      // [TS][16*NQ samples][8]: u entering transform t
+  float* TIN = TDF + NQ * COOP_TT;           // T layout: input tiles, NI tiles x NQ
+  float* USt = TIN + NI * NQ * COOP_TT;      // [TS][16*NQ samples][8]: u entering transform t
   float* ASt = USt + TS * NQ * 128;      // [TS][16*NQ][8]: head output a (slots)
   // constants of the whole call: biases of every transform, the weight-gradient block list, per input-row and
   // per-slot standardisation constants (read from LDS in the phases instead of through dependent global loads)
@@ -350,8 +266,8 @@ __global__ __launch_bounds__(256 * NG, SF_TRC_WGS(NG)) void k_maf_trainc(SfTrcAr
       const float* tp0 = a.img + sf_opaque_zero();
 #pragma unroll
       for (int it = 0; it < NI; ++it) {
-        pwin[0][it] = c_frag(tp0 + L::o_win, NI, tA, it, lane);
-        pwin[1][it] = c_frag(tp0 + L::o_win, NI, tB_, it, lane);
+        pwin[0][it] = coop_frag(tp0 + L::o_win, NI, tA, it, lane);
+        pwin[1][it] = coop_frag(tp0 + L::o_win, NI, tB_, it, lane);
       }
     }
     // ------------------------------------------------------------------ per-sample inputs (one subtile per wave)
@@ -388,7 +304,7 @@ __global__ __launch_bounds__(256 * NG, SF_TRC_WGS(NG)) void k_maf_trainc(SfTrcAr
 #pragma unroll
     for (int t = 0; t < TS; ++t) {
       if (t < a.T) {
-        const SfTrcArgs& a = c_args();
+        const SfTrcArgs& a = sf_coop_args<SfTrcArgs>();
         const SfTrcDev& c = a.c;
         const float* tp = a.img + (size_t)t * L::t_stride + sf_opaque_zero();  // (not loop-invariant: see sf_device.h)
         const float* cb = CBb + t * NBIAS;
@@ -398,7 +314,7 @@ __global__ __launch_bounds__(256 * NG, SF_TRC_WGS(NG)) void k_maf_trainc(SfTrcAr
         if (has0) {
           // next phase's fragments: in flight across the barrier
 #pragma unroll
-          for (int i = 0; i < NFS; ++i) w1f[i] = c_frag(tp + L::o_w1, NT, fslot_tile(i), fslot_it(i), lane);
+          for (int i = 0; i < NFS; ++i) w1f[i] = coop_frag(tp + L::o_w1, NT, fslot_tile(i), fslot_it(i), lane);
           f32x4 in0 = inx[0];
           in0[0] = s0on ? u0 : in0[0];
           in0[1] = s1on ? u1 : in0[1];
@@ -406,32 +322,32 @@ __global__ __launch_bounds__(256 * NG, SF_TRC_WGS(NG)) void k_maf_trainc(SfTrcAr
           for (int k = 0; k < 2; ++k) {
             if (k == 0 || has1) {
               const int tk = k == 0 ? tA : tB_;
-              f32x4 h0 = c_ld4(cb + (tk * 4 + g4) * 4);
+              f32x4 h0 = coop_ld4(cb + (tk * 4 + g4) * 4);
               h0 = c_mma(pwin[k][0], in0, h0);
               if constexpr (NI > 1) h0 = c_mma(pwin[k][NI - 1], inx[NI - 1], h0);
-              c_st4(XBa + (tk * NQ + q) * 256 + lane * 4, h0);
+              coop_st4(XBa + (tk * NQ + q) * 256 + lane * 4, h0);
             }
           }
         }
         SF_TC(2 + 5 * t);
-        c_barrier();
+        coop_barrier();
         // F2: a1 = tanh(b1 + W1 h0)
         float4 wff[2];
         SF_TCX(t == 1, 200, u0);
         if (has0) {
 #pragma unroll
-          for (int i = 0; i < NFS; ++i) w2f[i] = c_frag(tp + L::o_w2, NT, fslot_tile(i), fslot_it(i), lane);
-          wff[0] = c_frag(tp + L::o_wf, NT, 0, tA, lane);
-          wff[1] = c_frag(tp + L::o_wf, NT, 0, tB_, lane);
-          f32x4 accA = c_ld4(cb + NT * 16 + (tA * 4 + g4) * 4), accB = c_ld4(cb + NT * 16 + (tB_ * 4 + g4) * 4);
+          for (int i = 0; i < NFS; ++i) w2f[i] = coop_frag(tp + L::o_w2, NT, fslot_tile(i), fslot_it(i), lane);
+          wff[0] = coop_frag(tp + L::o_wf, NT, 0, tA, lane);
+          wff[1] = coop_frag(tp + L::o_wf, NT, 0, tB_, lane);
+          f32x4 accA = coop_ld4(cb + NT * 16 + (tA * 4 + g4) * 4), accB = coop_ld4(cb + NT * 16 + (tB_ * 4 + g4) * 4);
           SF_TCX(t == 1, 201, accA[0] + accB[0]);
           SF_TCX(t == 1, 202, w1f[0].x + w1f[4].x);
 {
-            f32x4 accA1 = c_zero(), accB1 = c_zero();
+            f32x4 accA1 = coop_zero(), accB1 = coop_zero();
 #pragma unroll
             for (int i = 0; i < NFS; ++i) {
               if (i < nfT) {
-                const f32x4 tv = c_ld4(XBa + (fslot_it(i) * NQ + q) * 256 + lane * 4);
+                const f32x4 tv = coop_ld4(XBa + (fslot_it(i) * NQ + q) * 256 + lane * 4);
                 if (i < nfA) c_mma_alt(w1f[i], tv, accA, accA1);
                 else c_mma_alt(w1f[i], tv, accB, accB1);
               }
@@ -444,29 +360,29 @@ __global__ __launch_bounds__(256 * NG, SF_TRC_WGS(NG)) void k_maf_trainc(SfTrcAr
           for (int r = 0; r < 4; ++r) { accA[r] = sf_tanh(accA[r]); accB[r] = sf_tanh(accB[r]); }
           SF_TCX(t == 1, 204, accA[0] + accB[0] + accA[3] + accB[3]);
           a1s[t][0] = accA; a1s[t][1] = accB;
-          c_st4(XBb + (tA * NQ + q) * 256 + lane * 4, accA);
-          if (has1) c_st4(XBb + (tB_ * NQ + q) * 256 + lane * 4, accB);
+          coop_st4(XBb + (tA * NQ + q) * 256 + lane * 4, accA);
+          if (has1) coop_st4(XBb + (tB_ * NQ + q) * 256 + lane * 4, accB);
           SF_TCX(t == 1, 205, accA[0]);
         }
         SF_TC(3 + 5 * t);
-        c_barrier();
+        coop_barrier();
         // F3: a2 = tanh(b2 + W2 a1); head partial sums over my hidden rows
         if (has0) {
           {  // the next transform's first fragments (the last transform reloads its own: no branch around a load)
             const float* tpn = tp + (t + 1 < a.T ? L::t_stride : 0);
 #pragma unroll
             for (int it = 0; it < NI; ++it) {
-              pwin[0][it] = c_frag(tpn + L::o_win, NI, tA, it, lane);
-              pwin[1][it] = c_frag(tpn + L::o_win, NI, tB_, it, lane);
+              pwin[0][it] = coop_frag(tpn + L::o_win, NI, tA, it, lane);
+              pwin[1][it] = coop_frag(tpn + L::o_win, NI, tB_, it, lane);
             }
           }
-          f32x4 accA = c_ld4(cb + 2 * NT * 16 + (tA * 4 + g4) * 4), accB = c_ld4(cb + 2 * NT * 16 + (tB_ * 4 + g4) * 4);
+          f32x4 accA = coop_ld4(cb + 2 * NT * 16 + (tA * 4 + g4) * 4), accB = coop_ld4(cb + 2 * NT * 16 + (tB_ * 4 + g4) * 4);
 {
-            f32x4 accA1 = c_zero(), accB1 = c_zero();
+            f32x4 accA1 = coop_zero(), accB1 = coop_zero();
 #pragma unroll
             for (int i = 0; i < NFS; ++i) {
               if (i < nfT) {
-                const f32x4 tv = c_ld4(XBb + (fslot_it(i) * NQ + q) * 256 + lane * 4);
+                const f32x4 tv = coop_ld4(XBb + (fslot_it(i) * NQ + q) * 256 + lane * 4);
                 if (i < nfA) c_mma_alt(w2f[i], tv, accA, accA1);
                 else c_mma_alt(w2f[i], tv, accB, accB1);
               }
@@ -477,19 +393,19 @@ __global__ __launch_bounds__(256 * NG, SF_TRC_WGS(NG)) void k_maf_trainc(SfTrcAr
 #pragma unroll
           for (int r = 0; r < 4; ++r) { accA[r] = sf_tanh(accA[r]); accB[r] = sf_tanh(accB[r]); }
           a2s[t][0] = accA; a2s[t][1] = accB;
-          f32x4 hp = c_mma(wff[0], accA, c_zero());
+          f32x4 hp = c_mma(wff[0], accA, coop_zero());
           if (has1) hp = c_mma(wff[1], accB, hp);
-          c_st4(PBf + (p * NQ + q) * 256 + lane * 4, hp);
+          coop_st4(PBf + (p * NQ + q) * 256 + lane * 4, hp);
         }
         SF_TC(4 + 5 * t);
-        c_barrier();
+        coop_barrier();
         SF_TC(5 + 5 * t);
         // F4 (both waves of the subtile, replicated): head = bf + partial sums; affine update of this lane's two slots
         {
-          f32x4 fin = c_ld4(cb + 3 * NT * 16 + g4 * 4);
+          f32x4 fin = coop_ld4(cb + 3 * NT * 16 + g4 * 4);
 #pragma unroll
           for (int pp = 0; pp < NP; ++pp) {
-            const f32x4 pv = c_ld4(PBf + (pp * NQ + q) * 256 + lane * 4);
+            const f32x4 pv = coop_ld4(PBf + (pp * NQ + q) * 256 + lane * 4);
 #pragma unroll
             for (int r = 0; r < 4; ++r) fin[r] += pv[r];
           }
@@ -508,18 +424,18 @@ __global__ __launch_bounds__(256 * NG, SF_TRC_WGS(NG)) void k_maf_trainc(SfTrcAr
     // first fragments of the backward sweep (top transform): in flight behind the loss
     float4 pwfT[2], pw2T[NFS], pwinB[2][NI];
     {
-      const SfTrcArgs& a = c_args();
+      const SfTrcArgs& a = sf_coop_args<SfTrcArgs>();
       const SfTrcDev& c = a.c;
       const float* tpl = a.img + (size_t)(a.T - 1) * L::t_stride + sf_opaque_zero();
-      pwfT[0] = c_frag(tpl + L::o_wfT, 1, tA, 0, lane);
-      pwfT[1] = c_frag(tpl + L::o_wfT, 1, tB_, 0, lane);
+      pwfT[0] = coop_frag(tpl + L::o_wfT, 1, tA, 0, lane);
+      pwfT[1] = coop_frag(tpl + L::o_wfT, 1, tB_, 0, lane);
 #pragma unroll
       for (int it = 0; it < NI; ++it) {
-        pwinB[0][it] = c_frag(tpl + L::o_win, NI, tA, it, lane);
-        pwinB[1][it] = c_frag(tpl + L::o_win, NI, tB_, it, lane);
+        pwinB[0][it] = coop_frag(tpl + L::o_win, NI, tA, it, lane);
+        pwinB[1][it] = coop_frag(tpl + L::o_win, NI, tB_, it, lane);
       }
 #pragma unroll
-      for (int i = 0; i < NFS; ++i) pw2T[i] = c_frag(tpl + L::o_w2T, NT, bslot_tile(i), bslot_ot(i), lane);
+      for (int i = 0; i < NFS; ++i) pw2T[i] = coop_frag(tpl + L::o_w2T, NT, bslot_tile(i), bslot_ot(i), lane);
     }
     // ------------------------------------------------------------------ loss, dL/du_T
     float G0, G1;
@@ -543,7 +459,7 @@ __global__ __launch_bounds__(256 * NG, SF_TRC_WGS(NG)) void k_maf_trainc(SfTrcAr
       G1 = wgt * u1;
     }
     SF_TC(39);
-    c_barrier();  // the last head sums have been read (PBf is TD2's buffer), the u / a stash is complete
+    coop_barrier();  // the last head sums have been read (PBf is TD2's buffer), the u / a stash is complete
 
     // ------------------------------------------------------------------ backward
     // gradient target: this workgroup's partial (plain stores; adds from its second chunk on), or -- a.fix -- the fixed-point
@@ -554,7 +470,7 @@ __global__ __launch_bounds__(256 * NG, SF_TRC_WGS(NG)) void k_maf_trainc(SfTrcAr
     for (int tt = 0; tt < TS; ++tt) {
       const int t = TS - 1 - tt;
       if (t < a.T) {
-        const SfTrcArgs& a = c_args();
+        const SfTrcArgs& a = sf_coop_args<SfTrcArgs>();
         const SfTrcDev& c = a.c;
         const float* tp = a.img + (size_t)t * L::t_stride + sf_opaque_zero();
         const float* cb = CBb + t * NBIAS;
@@ -579,30 +495,30 @@ __global__ __launch_bounds__(256 * NG, SF_TRC_WGS(NG)) void k_maf_trainc(SfTrcAr
           in0[0] = s0on ? uu.x : in0[0];
           in0[1] = s1on ? uu.y : in0[1];
           if (p == 0) {
-            c_put_T(TDF + q * TTS, dfin, s, g4);
-            c_put_T(TIN + q * TTS, in0, s, g4);
-            if constexpr (NI > 1) c_put_T(TIN + (NQ + q) * TTS, inx[NI - 1], s, g4);
+            coop_put_T(TDF + q * COOP_TT, dfin, s, g4);
+            coop_put_T(TIN + q * COOP_TT, in0, s, g4);
+            if constexpr (NI > 1) coop_put_T(TIN + (NQ + q) * COOP_TT, inx[NI - 1], s, g4);
           }
           if (has0) {
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
               if (k == 0 || has1) {
                 const int tk = k == 0 ? tA : tB_;
-                f32x4 dp2 = c_mma(pwfT[k], dfin, c_zero());
+                f32x4 dp2 = c_mma(pwfT[k], dfin, coop_zero());
 #pragma unroll
                 for (int r = 0; r < 4; ++r) dp2[r] *= 1.0f - a2s[t][k][r] * a2s[t][k][r];
-                c_st4(XBa + (tk * NQ + q) * 256 + lane * 4, dp2);
-                c_put_T(TD2 + (tk * NQ + q) * TTS, dp2, s, g4);
-                c_put_T(TA2 + (tk * NQ + q) * TTS, a2s[t][k], s, g4);
-                f32x4 h0 = c_mma(pwinB[k][0], in0, c_ld4(cb + (tk * 4 + g4) * 4));
+                coop_st4(XBa + (tk * NQ + q) * 256 + lane * 4, dp2);
+                coop_put_T(TD2 + (tk * NQ + q) * COOP_TT, dp2, s, g4);
+                coop_put_T(TA2 + (tk * NQ + q) * COOP_TT, a2s[t][k], s, g4);
+                f32x4 h0 = c_mma(pwinB[k][0], in0, coop_ld4(cb + (tk * 4 + g4) * 4));
                 if constexpr (NI > 1) h0 = c_mma(pwinB[k][NI - 1], inx[NI - 1], h0);
-                c_put_T(TH0 + (tk * NQ + q) * TTS, h0, s, g4);
+                coop_put_T(TH0 + (tk * NQ + q) * COOP_TT, h0, s, g4);
               }
             }
           }
         }
         SF_TC(41 + 12 * tt);
-        c_barrier();
+        coop_barrier();
         SF_TC(42 + 12 * tt);
         // B2: delta of block 1; weight gradients of the head.  The two halves of a backward phase (data path, weight-
         // gradient blocks) are independent: odd groups run them in the opposite order, so that the two waves that share
@@ -611,16 +527,16 @@ __global__ __launch_bounds__(256 * NG, SF_TRC_WGS(NG)) void k_maf_trainc(SfTrcAr
         auto b2_data = [&]() {
         if (has0) {
 #pragma unroll
-          for (int i = 0; i < NFS; ++i) w1T[i] = c_frag(tp + L::o_w1T, NT, bslot_tile(i), bslot_ot(i), lane);
-          wiT[0] = c_frag(tp + L::o_winT, NT, 0, tA, lane);
-          wiT[1] = c_frag(tp + L::o_winT, NT, 0, tB_, lane);
-          f32x4 accA = c_zero(), accB = c_zero();
+          for (int i = 0; i < NFS; ++i) w1T[i] = coop_frag(tp + L::o_w1T, NT, bslot_tile(i), bslot_ot(i), lane);
+          wiT[0] = coop_frag(tp + L::o_winT, NT, 0, tA, lane);
+          wiT[1] = coop_frag(tp + L::o_winT, NT, 0, tB_, lane);
+          f32x4 accA = coop_zero(), accB = coop_zero();
 {
-            f32x4 accA1 = c_zero(), accB1 = c_zero();
+            f32x4 accA1 = coop_zero(), accB1 = coop_zero();
 #pragma unroll
             for (int i = 0; i < NFS; ++i) {
               if (i < nbT) {
-                const f32x4 tv = c_ld4(XBa + (bslot_ot(i) * NQ + q) * 256 + lane * 4);
+                const f32x4 tv = coop_ld4(XBa + (bslot_ot(i) * NQ + q) * 256 + lane * 4);
                 if (i < nbA) c_mma_alt(pw2T[i], tv, accA, accA1);
                 else c_mma_alt(pw2T[i], tv, accB, accB1);
               }
@@ -633,13 +549,13 @@ __global__ __launch_bounds__(256 * NG, SF_TRC_WGS(NG)) void k_maf_trainc(SfTrcAr
             accA[r] *= 1.0f - a1s[t][0][r] * a1s[t][0][r];
             accB[r] *= 1.0f - a1s[t][1][r] * a1s[t][1][r];
           }
-          c_st4(XBb + (tA * NQ + q) * 256 + lane * 4, accA);
-          c_put_T(TD1 + (tA * NQ + q) * TTS, accA, s, g4);
-          c_put_T(TA1 + (tA * NQ + q) * TTS, a1s[t][0], s, g4);
+          coop_st4(XBb + (tA * NQ + q) * 256 + lane * 4, accA);
+          coop_put_T(TD1 + (tA * NQ + q) * COOP_TT, accA, s, g4);
+          coop_put_T(TA1 + (tA * NQ + q) * COOP_TT, a1s[t][0], s, g4);
           if (has1) {
-            c_st4(XBb + (tB_ * NQ + q) * 256 + lane * 4, accB);
-            c_put_T(TD1 + (tB_ * NQ + q) * TTS, accB, s, g4);
-            c_put_T(TA1 + (tB_ * NQ + q) * TTS, a1s[t][1], s, g4);
+            coop_st4(XBb + (tB_ * NQ + q) * 256 + lane * 4, accB);
+            coop_put_T(TD1 + (tB_ * NQ + q) * COOP_TT, accB, s, g4);
+            coop_put_T(TA1 + (tB_ * NQ + q) * COOP_TT, a1s[t][1], s, g4);
           }
         }
         };
@@ -647,25 +563,25 @@ __global__ __launch_bounds__(256 * NG, SF_TRC_WGS(NG)) void k_maf_trainc(SfTrcAr
         for (int n = wave; n < NT; n += 2 * NW) {  // dWf[head tile][hidden tile]; bias with the first block
           const bool two = n + NW < NT;
           const int n2 = two ? n + NW : n;
-          const CJob A = {TDF, TA2, gp + L::g_wf + n * 256, n == 0 ? gp + L::g_bf : nullptr, 0, n};
-          const CJob B = {TDF, TA2, gp + L::g_wf + n2 * 256, nullptr, 0, n2};
+          const CoopJob A = {TDF, TA2, gp + L::g_wf + n * 256, n == 0 ? gp + L::g_bf : nullptr, 0, n};
+          const CoopJob B = {TDF, TA2, gp + L::g_wf + n2 * 256, nullptr, 0, n2};
           c_dw_jobs<NQ>(A, B, two, accumulate, lane);
         }
         };
         if (swapped) { b2_jobs(); SF_TC(43 + 12 * tt); b2_data(); } else { b2_data(); SF_TC(43 + 12 * tt); b2_jobs(); }
         SF_TC(44 + 12 * tt);
-        c_barrier();
+        coop_barrier();
         SF_TC(45 + 12 * tt);
         // B3: delta of the initial layer, partial sums of W_in^T delta; weight gradients of block 2
         auto b3_data = [&]() {
         if (has0) {
-          f32x4 accA = c_zero(), accB = c_zero();
+          f32x4 accA = coop_zero(), accB = coop_zero();
 {
-            f32x4 accA1 = c_zero(), accB1 = c_zero();
+            f32x4 accA1 = coop_zero(), accB1 = coop_zero();
 #pragma unroll
             for (int i = 0; i < NFS; ++i) {
               if (i < nbT) {
-                const f32x4 tv = c_ld4(XBb + (bslot_ot(i) * NQ + q) * 256 + lane * 4);
+                const f32x4 tv = coop_ld4(XBb + (bslot_ot(i) * NQ + q) * 256 + lane * 4);
                 if (i < nbA) c_mma_alt(w1T[i], tv, accA, accA1);
                 else c_mma_alt(w1T[i], tv, accB, accB1);
               }
@@ -673,13 +589,13 @@ __global__ __launch_bounds__(256 * NG, SF_TRC_WGS(NG)) void k_maf_trainc(SfTrcAr
 #pragma unroll
             for (int r = 0; r < 4; ++r) { accA[r] += accA1[r]; accB[r] += accB1[r]; }
           }
-          c_put_T(TD0 + (tA * NQ + q) * TTS, accA, s, g4);
-          f32x4 dup = c_mma(wiT[0], accA, c_zero());
+          coop_put_T(TD0 + (tA * NQ + q) * COOP_TT, accA, s, g4);
+          f32x4 dup = c_mma(wiT[0], accA, coop_zero());
           if (has1) {
-            c_put_T(TD0 + (tB_ * NQ + q) * TTS, accB, s, g4);
+            coop_put_T(TD0 + (tB_ * NQ + q) * COOP_TT, accB, s, g4);
             dup = c_mma(wiT[1], accB, dup);
           }
-          c_st4(PBb + (p * NQ + q) * 256 + lane * 4, dup);
+          coop_st4(PBb + (p * NQ + q) * 256 + lane * 4, dup);
         }
         };
         auto b3_jobs = [&]() {
@@ -687,34 +603,34 @@ __global__ __launch_bounds__(256 * NG, SF_TRC_WGS(NG)) void k_maf_trainc(SfTrcAr
           for (int n = wave; n < nj; n += 2 * NW) {
             const bool two = n + NW < nj;
             const int cA = CBj[n], cB = CBj[two ? n + NW : n];
-            const CJob A = {TD2, TA1, gp + L::g_w2 + ((cA >> 2) * NT + (cA & 3)) * 256, (cA & 3) == 0 ? gp + L::g_b2 : nullptr, cA >> 2, cA & 3};
-            const CJob B = {TD2, TA1, gp + L::g_w2 + ((cB >> 2) * NT + (cB & 3)) * 256, (cB & 3) == 0 ? gp + L::g_b2 : nullptr, cB >> 2, cB & 3};
+            const CoopJob A = {TD2, TA1, gp + L::g_w2 + ((cA >> 2) * NT + (cA & 3)) * 256, (cA & 3) == 0 ? gp + L::g_b2 : nullptr, cA >> 2, cA & 3};
+            const CoopJob B = {TD2, TA1, gp + L::g_w2 + ((cB >> 2) * NT + (cB & 3)) * 256, (cB & 3) == 0 ? gp + L::g_b2 : nullptr, cB >> 2, cB & 3};
             c_dw_jobs<NQ>(A, B, two, accumulate, lane);
           }
         };
         if (swapped) { b3_jobs(); SF_TC(46 + 12 * tt); b3_data(); } else { b3_data(); SF_TC(46 + 12 * tt); b3_jobs(); }
         SF_TC(47 + 12 * tt);
-        c_barrier();
+        coop_barrier();
         SF_TC(48 + 12 * tt);
         // B4 (both waves of the subtile, replicated): dL/du of the transform below; weight gradients of block 1 and
         // the initial layer
         {  // first fragments of the transform below (the bottom transform reloads its own)
           const float* tpn = tp - (t >= 1 ? L::t_stride : 0);
-          pwfT[0] = c_frag(tpn + L::o_wfT, 1, tA, 0, lane);
-          pwfT[1] = c_frag(tpn + L::o_wfT, 1, tB_, 0, lane);
+          pwfT[0] = coop_frag(tpn + L::o_wfT, 1, tA, 0, lane);
+          pwfT[1] = coop_frag(tpn + L::o_wfT, 1, tB_, 0, lane);
 #pragma unroll
           for (int it = 0; it < NI; ++it) {
-            pwinB[0][it] = c_frag(tpn + L::o_win, NI, tA, it, lane);
-            pwinB[1][it] = c_frag(tpn + L::o_win, NI, tB_, it, lane);
+            pwinB[0][it] = coop_frag(tpn + L::o_win, NI, tA, it, lane);
+            pwinB[1][it] = coop_frag(tpn + L::o_win, NI, tB_, it, lane);
           }
 #pragma unroll
-          for (int i = 0; i < NFS; ++i) pw2T[i] = c_frag(tpn + L::o_w2T, NT, bslot_tile(i), bslot_ot(i), lane);
+          for (int i = 0; i < NFS; ++i) pw2T[i] = coop_frag(tpn + L::o_w2T, NT, bslot_tile(i), bslot_ot(i), lane);
         }
         {
-          f32x4 du = c_zero();
+          f32x4 du = coop_zero();
 #pragma unroll
           for (int pp = 0; pp < NP; ++pp) {
-            const f32x4 pv = c_ld4(PBb + (pp * NQ + q) * 256 + lane * 4);
+            const f32x4 pv = coop_ld4(PBb + (pp * NQ + q) * 256 + lane * 4);
 #pragma unroll
             for (int r = 0; r < 4; ++r) du[r] += pv[r];
           }
@@ -734,24 +650,24 @@ __global__ __launch_bounds__(256 * NG, SF_TRC_WGS(NG)) void k_maf_trainc(SfTrcAr
         {
           // jobs 0..n1-1: block 1 (TD1 x TH0); n1..n1+n2-1: initial layer (TD0 x TIN)
           const int n1 = c.n_jobs, n2 = NT * NI, ntot = n1 + n2;
-          auto mk = [&](int n) -> CJob {
+          auto mk = [&](int n) -> CoopJob {
             if (n < n1) {
               const int code = CBj[n];
               const int ot = code >> 2, it = code & 3;
-              return CJob{TD1, TH0, gp + L::g_w1 + (ot * NT + it) * 256, it == 0 ? gp + L::g_b1 : nullptr, ot, it};
+              return CoopJob{TD1, TH0, gp + L::g_w1 + (ot * NT + it) * 256, it == 0 ? gp + L::g_b1 : nullptr, ot, it};
             }
             const int m = n - n1;
             const int ot = m / NI, it = m - ot * NI;
-            return CJob{TD0, TIN, gp + L::g_win + (ot * NI + it) * 256, it == 0 ? gp + L::g_b0 : nullptr, ot, it};
+            return CoopJob{TD0, TIN, gp + L::g_win + (ot * NI + it) * 256, it == 0 ? gp + L::g_b0 : nullptr, ot, it};
           };
           for (int n = wave; n < ntot; n += 2 * NW) {
             const bool two = n + NW < ntot;
-            const CJob A = mk(n), B = mk(two ? n + NW : n);
+            const CoopJob A = mk(n), B = mk(two ? n + NW : n);
             c_dw_jobs<NQ>(A, B, two, accumulate, lane);
           }
         }
         SF_TC(50 + 12 * tt);
-        c_barrier();
+        coop_barrier();
         SF_TC(51 + 12 * tt);
       }
     }
@@ -760,44 +676,10 @@ __global__ __launch_bounds__(256 * NG, SF_TRC_WGS(NG)) void k_maf_trainc(SfTrcAr
 }
 
 #if SF_TRC_TU == 5
-// sum of the workgroups' gradient partials in a fixed order: block = 64 parameters x 16 groups of partials (1024 threads);
-// a thread has up to eight of its group's loads in flight (the kernel is a chain of L2 / HBM round trips over 33 MB at
-// batch 16 384: 15 us with 64 partials per thread four at a time, a third of that with 16 per thread eight at a time)
-__global__ __launch_bounds__(1024) void k_gather_c(const float* __restrict__ gpart, long stride, int nwg,
-                                                    const int32_t* __restrict__ gdst, float* __restrict__ grad, long n) {
-  __shared__ float part[16][64];
-  const int px = threadIdx.x & 63, qy = threadIdx.x >> 6;
-  const long i = (long)blockIdx.x * 64 + px;
-  const int g = i < n ? gdst[i] : -1;
-  float v = 0.f;
-  if (g >= 0) {
-    const int per = (nwg + 15) / 16;
-    const int lo = qy * per, hi = min(nwg, lo + per);
-    float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    int w = lo;
-    for (; w + 8 <= hi; w += 8) {
-      float q[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) q[k] = gpart[(size_t)(w + k) * stride + g];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) a[k] += q[k];
-    }
-    for (int k = 0; w < hi; ++w, ++k) a[k] += gpart[(size_t)w * stride + g];
-    v = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
-  }
-  part[qy][px] = v;
-  __syncthreads();
-  if (qy == 0 && i < n) {
-    float t = 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) t += part[k][px];
-    grad[i] = t;
-  }
-}
-
-// The same sum walking the partials in THEIR order: thread j owns position j of a partial -- consecutive threads read
-// consecutive floats of every partial (k_gather_c's parameter order scatters its 4-byte reads over the fragment layout:
-// 15 us for 33 MB at batch 16 384) -- and writes the one or two parameters that position feeds; the tail of the grid zeroes
+// Sum of the workgroups' gradient partials in a fixed order, walking the partials in THEIR order: thread j owns position j of a
+// partial -- consecutive threads read consecutive floats of every partial (a gather in parameter order scatters its 4-byte reads
+// over the fragment layout: 15 us for 33 MB at batch 16 384) -- and writes the one or two parameters that position feeds
+// (SfLayout::gsrcC; a layout whose positions feed more is not cooperative at all, sf_layout.cpp); the tail of the grid zeroes
 // the parameters without a position.  Order of the sum: partial 0, 1, 2 ... through eight interleaved accumulators.
 // sq_part (optional): the block's share of |grad|^2 -> sq_part[blockIdx.x], so that the optimiser step that follows need not read
 // the whole gradient again for the clipping norm (sf_launch_adam sums the shares in block order: deterministic).
@@ -870,7 +752,7 @@ __global__ __launch_bounds__(256) void k_gather_fix(const long long* __restrict_
 
 size_t sf_trainc_lds_bytes(const SfTrcDev& c, int TS, int NG) {
   const size_t NQ = 2 * (size_t)NG;
-  return ((size_t)c.NT * NQ * (256 * 2 + TTS * 5) + NQ * TTS + (size_t)c.NI * NQ * TTS + (size_t)TS * NQ * 256 +
+  return ((size_t)c.NT * NQ * (256 * 2 + COOP_TT * 5) + NQ * COOP_TT + (size_t)c.NI * NQ * COOP_TT + (size_t)TS * NQ * 256 +
           (size_t)sf_trc_cb_floats(c.NT, c.NI, TS)) * sizeof(float);
 }
 
@@ -917,24 +799,12 @@ bool sf_trainc_eligible(const SfLayout& L, bool want_dctx) {
     }
     if (!ok) return false;  // (the packer and the kernel disagree about the block order: never launch on that)
   }
-  // a wave holds the fragments of tiles p and NT-1-p in five slots per layer (aligned MADE placement: NT + 1 blocks)
-  for (int p = 0; 2 * p < c.NT; ++p) {
-    const int tA = p, tB = c.NT - 1 - p;
-    const int nf = (c.kend[tA] + 1) + (tB > tA ? c.kend[tB] + 1 : 0);
-    const int nb = (c.NT - c.kbeg[tA]) + (tB > tA ? c.NT - c.kbeg[tB] : 0);
-    if (nf > 8 || nb > 8) return false;
-  }
+  if (sf_trc_slots_needed(c) > 8) return false;   // (fragment slots per masked layer and wave: the instantiations hold five or eight)
   return sf_trainc_lds_bytes(c, sf_trc_ts(L.dev.T), 1) <= (size_t)160 * 1024;
 }
 
 int sf_trainc_grid(long B, const SfTrcDev* c, int T) {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    hipDeviceProp_t pr;
-    cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0)
-              ? pr.multiProcessorCount : 256;
-  }
+  const int cus = sf_coop_cus();
   const int ng = sf_trainc_groups(B, c, T);
   const long per = 32L * ng, chunks = (B + per - 1) / per;
   const long cap = (long)cus * (ng == 1 ? 2 : 1);
@@ -954,28 +824,9 @@ static hipError_t c_launch_ts(const SfTrcArgs& a, int grid, hipStream_t st) {
   }
   const size_t sh = sf_trainc_lds_bytes(a.c, TS, NG);
 #ifdef SF_TRC_TRACE
-  {
-    static unsigned long long* d_tr = nullptr;
-    if (!d_tr && hipMalloc(&d_tr, 8 * 256 * 8) != hipSuccess) return hipErrorOutOfMemory;
-    (void)hipMemsetAsync(d_tr, 0, 8 * 256 * 8, st);
-    SfTrcArgs b = a;
-    b.trace = d_tr;
+  return sf_coop_trace_launch(a, grid, st, 4 * NG, 256, "trainc", [&](const SfTrcArgs& b) {
     hipLaunchKernelGGL((k_maf_trainc<TS, NI, NT, NG, NFS>), dim3((unsigned)grid), dim3(256 * NG), sh, st, b);
-    (void)hipStreamSynchronize(st);
-    static unsigned long long h[8 * 256];
-    (void)hipMemcpy(h, d_tr, sizeof(h), hipMemcpyDeviceToHost);
-    static int calls = 0;
-    if (++calls % 8 == 0) {
-      fprintf(stderr, "[trainc trace] B=%ld grid=%d (units of 100 cycles since stamp 0 of wave 0)\n", a.B, grid);
-      for (int w = 0; w < 4 * NG; ++w) {
-        fprintf(stderr, "  wave %d:", w);
-        for (int i = 0; i < 256; ++i)
-          if (h[w * 256 + i]) fprintf(stderr, " %d:%.1f", i, (double)(long long)(h[w * 256 + i] - h[0]) * 0.01);
-        fprintf(stderr, "\n");
-      }
-    }
-    return hipGetLastError();
-  }
+  });
 #endif
   hipLaunchKernelGGL((k_maf_trainc<TS, NI, NT, NG, NFS>), dim3((unsigned)grid), dim3(256 * NG), sh, st, a);
   return hipGetLastError();
@@ -1011,25 +862,13 @@ hipError_t sf_trainc_launch_ts8(const SfTrcArgs& a, int grid, int ng, hipStream_
 hipError_t sf_trainc_launch_ts15(const SfTrcArgs& a, int grid, int ng, hipStream_t st);
 hipError_t sf_trainc_launch_ts16(const SfTrcArgs& a, int grid, int ng, hipStream_t st);
 hipError_t sf_trainc_launch_ts18(const SfTrcArgs& a, int grid, int ng, hipStream_t st);
-// fragment slots a flow's placement needs per masked layer and wave (sf_trainc_eligible admits up to eight)
-static int c_slots_needed(const SfTrcDev& c) {
-  int mx = 0;
-  for (int p = 0; 2 * p < c.NT; ++p) {
-    const int tA = p, tB = c.NT - 1 - p;
-    const int nf = (c.kend[tA] + 1) + (tB > tA ? c.kend[tB] + 1 : 0);
-    const int nb = (c.NT - c.kbeg[tA]) + (tB > tA ? c.NT - c.kbeg[tB] : 0);
-    mx = nf > mx ? nf : mx;
-    mx = nb > mx ? nb : mx;
-  }
-  return mx;
-}
 // T <= 5: every transform's a1 / a2 tiles in registers (80 VGPRs of stash); T = 6 and T = 7..8 are instantiations of their own --
 // the reference's example CLI trains num_transforms = 6 (examples/sbi/scripts/train_model.py:56-57) -- whose longer stash the
 // compiler parks partly in scratch: same cooperative decomposition (no activation in HBM), measured 0.173 of the fp32 roof at
 // T = 6 and batch 16 384 (86.9 us; the generic kernel: 187.5 us)
 hipError_t sf_launch_maf_trainc(const SfTrcArgs& a, int grid, hipStream_t st) {
   const int ng = sf_trainc_groups(a.B, &a.c, a.T);
-  if (c_slots_needed(a.c) > 5) {   // contiguous ("span") placement: the eight-slot instantiations
+  if (sf_trc_slots_needed(a.c) > 5) {   // contiguous ("span") placement: the eight-slot instantiations
     switch (sf_trc_ts(a.T)) {
       case 5: return sf_trainc_launch_ts15(a, grid, ng, st);
       case 6: return sf_trainc_launch_ts16(a, grid, ng, st);
@@ -1054,10 +893,6 @@ hipError_t sf_launch_gather_fix(const long long* gfix, long stride, int nrep, co
                                 float* grad, hipStream_t st) {
   const long tot = stride + n_zero;
   hipLaunchKernelGGL(k_gather_fix, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, gfix, stride, nrep, gsrc, gzero, n_zero, grad);
-  return hipGetLastError();
-}
-hipError_t sf_launch_gather_c(const float* gpart, long stride, int nwg, const int32_t* gdst, float* grad, long n, hipStream_t st) {
-  hipLaunchKernelGGL(k_gather_c, dim3((unsigned)((n + 63) / 64)), dim3(1024), 0, st, gpart, stride, nwg, gdst, grad, n);
   return hipGetLastError();
 }
 #endif  // SF_TRC_TU == 5
