@@ -672,6 +672,30 @@ int sf_knn(const float* base /*[N,C] device*/, int64_t N, int32_t C, const float
 int sf_kde_logsumexp(const float* base_w /*[N,C] device*/, int64_t N, int32_t C, const float* query_w /*[M,C] device*/,
                      int64_t M, double* out /*[M] device*/, void* stream);
 
+/* ---- Gaussian-kernel sums of the MMD misspecification test (csrc/sf_mmd.hip; synference_amd/misspecification.py; DESIGN.md
+ * section 18).  A term is k(a, b) = exp2(d2(a, b) * c2) with d2 the squared distance above (fp32, unfused), the product rounded
+ * to fp32 and v_exp_f32; c2 = (float)(-0.5 / scale^2 * log2(e)) comes from the caller, c2 <= 0 and finite.  A NaN term counts
+ * as 0.  Sums are fp64 of fp32 terms in an order fixed by the shapes alone -- no atomics: two calls give the same bits.
+ *
+ * sf_rbf_rowsum: out[q] = sum_i k(query[q], base[i]); exclude_self = 1 skips base row self_offset + q (by position, as in
+ * sf_knn: the base against itself, possibly in pieces).  1 <= C <= SF_RBF_MAX_C, 1 <= N < 2^31, with exclude_self
+ * self_offset + M <= N; anything else is SF_ERR_INVALID with a message and the output is untouched.  M == 0: SF_OK. */
+#define SF_RBF_MAX_C 64
+int sf_rbf_rowsum(const float* base /*[N,C] device*/, int64_t N, int32_t C, const float* query /*[M,C] device*/, int64_t M,
+                  float c2, int32_t exclude_self, int64_t self_offset, double* out /*[M] device*/, void* stream);
+
+/* sf_rbf_subset_sums: pair_sum[s] = sum over positions a != b of k(rows[idx[s,a]], rows[idx[s,b]]) -- ordered pairs, the
+ * exclusion by position -- and, with rowsum, picked_rowsum[s] = sum_a rowsum[idx[s,a]].  Only the tiles on and below the
+ * diagonal of the m x m block are visited; terms below it are doubled.  The entries of a set being distinct and inside [0, N)
+ * is the caller's contract; the device clamps an entry outside into the range and never reads out of bounds.
+ * 1 <= C <= SF_RBF_MAX_C, N < 2^31, 2 <= m <= N, rowsum and picked_rowsum both NULL or both given; anything else is
+ * SF_ERR_INVALID with a message and the outputs are untouched.  n_sets == 0: SF_OK.  Scratch (one partial per visited tile of
+ * at most 64 MiB of sets at a time) is owned per device. */
+int sf_rbf_subset_sums(const float* rows /*[N,C] device*/, int64_t N, int32_t C, const int32_t* idx /*[n_sets,m] device*/,
+                       int64_t n_sets, int64_t m, float c2, const double* rowsum /*[N] device or NULL*/,
+                       double* pair_sum /*[n_sets] device*/, double* picked_rowsum /*[n_sets] device; NULL iff rowsum NULL*/,
+                       void* stream);
+
 /* ---- L-C2ST: the classifiers of the local calibration test (csrc/sf_lc2st.hip; synference_amd/lc2st.py; DESIGN.md section 15;
  * ref: sbi_runner.py:986-1063, sbi.diagnostics.lc2st.LC2ST with sklearn's MLPClassifier) ---------------------------------------
  * A handle holds n_cls independent classifiers over ONE row matrix rows[R, n_in]: two ReLU layers of `width` units and a logistic

@@ -180,6 +180,10 @@ PROTOTYPES = {
     "sf_knn": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_void_p,
                          C.c_void_p, C.c_void_p]),
     "sf_kde_logsumexp": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "sf_rbf_rowsum": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_float, C.c_int32, C.c_int64,
+                                C.c_void_p, C.c_void_p]),
+    "sf_rbf_subset_sums": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_float, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     "sf_c2st_create": (C.c_int, [C.POINTER(sf_c2st_desc), C.POINTER(C.c_void_p), C.c_void_p]),
     "sf_c2st_destroy": (None, [C.c_void_p]),
     "sf_c2st_num_params": (C.c_int64, [C.c_void_p]),

@@ -116,6 +116,8 @@ class SBI_Fitter:
         self._target_scalar = None
         self.posteriors = None
         self.last_lc2st = None
+        self.last_misspecification = None
+        self.marginal_trainer = self.marginal_trainer_est = None
         self.stats = None
         self._prior = None
         self._train_indices = self._test_indices = None
@@ -1727,4 +1729,53 @@ class SBI_Fitter:
                          "probs_data": probs_data[0], "probs_null": probs_null, "n_iter": n_iter})
         out = rows[0] if len(rows) == 1 else {k: np.stack([np.asarray(r[k]) for r in rows]) for k in rows[0]}
         self.last_lc2st = out
+        return out
+
+    def detect_misspecification(self, x_obs, X_train=None, retrain=False, *, method: str = "logprob", alpha: float = 0.05,
+                                seed: Optional[int] = None, plot: bool = False, **kwargs) -> dict:
+        """Is the library misspecified for the observations (ref: sbi_runner.py:905-984; Schmitt et al. 2023)?
+        ``method="logprob"`` is the reference's path: an unconditional flow of the training features
+        (``misspecification.MarginalTrainer``, kept as ``self.marginal_trainer`` / ``self.marginal_trainer_est``) and where
+        ``log p(x_obs)`` falls among ``log p(X_train)``; ``retrain=False`` reuses a kept flow (the reference tests a misspelt
+        attribute and so always retrains), ``kwargs`` go to ``MarginalTrainer.train``.  ``method="mmd"`` is the catalogue-level
+        permutation test of ``misspecification.calc_misspecification_mmd``: ``mode=``, ``n_shuffle=`` and its other keywords
+        come from ``kwargs``, ``self.posteriors`` serves ``mode="embedding"``.  ``X_train`` defaults to the training split.
+        The reference plots and returns nothing; this returns, and keeps as ``self.last_misspecification``,
+        ``{"method", "p_value", "reject", "log_prob_obs", "log_prob_train"}`` or ``{"method", "p_value", "reject", "mmd",
+        "mmds_baseline", "mmd2", "null_mmd2", "scale"}``.  ``seed`` None: the posterior's next seed (0 without one); under a
+        process group every rank runs the whole test on rank 0's seed."""
+        from . import misspecification as MS
+        from .posterior import broadcast_seed
+        if method not in MS.METHODS:
+            raise ValueError(f"Unknown method: {method}; available: {list(MS.METHODS)}")
+        if X_train is None:
+            if self._X_train is None:
+                raise ValueError("No training data found. Please set the training data first.")
+            X_train = self._X_train
+        if plot:
+            logger.info("detect_misspecification: plot=True is skipped on the HIP path (plotting is out of scope)")
+        post = getattr(self, "posteriors", None)
+        if seed is None:
+            seed = post._next_seed(None) if post is not None and hasattr(post, "_next_seed") else 0
+        seed = int(broadcast_seed(int(seed)))
+        if method == "mmd":
+            kw = dict(kwargs)
+            mode, n_shuffle = kw.pop("mode", "x_space"), kw.pop("n_shuffle", 1000)
+            out = MS.calc_misspecification_mmd(post, x_obs, X_train, mode, n_shuffle, seed=seed, alpha=alpha, return_details=True,
+                                               **kw)
+            out = {"method": "mmd", **out}
+        else:
+            X = np.asarray(X_train, dtype=np.float32)
+            MS._check_features(X.shape[1] if X.ndim == 2 else 0)
+            if retrain or getattr(self, "marginal_trainer_est", None) is None:
+                self.marginal_trainer = MS.MarginalTrainer(density_estimator="NSF")
+                self.marginal_trainer.append_samples(X)
+                self.marginal_trainer_est = self.marginal_trainer.train(seed=seed, **kwargs)
+            est = self.marginal_trainer_est
+            p_value, reject = MS.calc_misspecification_logprob(X, x_obs, est, alpha=alpha)
+            xo = np.asarray(x_obs, dtype=np.float32)
+            lp_o = est.log_prob(xo).double().cpu().numpy()
+            out = {"method": "logprob", "p_value": p_value, "reject": reject,
+                   "log_prob_obs": float(lp_o[0]) if xo.ndim == 1 else lp_o, "log_prob_train": est.log_prob(X).double().cpu().numpy()}
+        self.last_misspecification = out
         return out
