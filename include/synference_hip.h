@@ -178,6 +178,34 @@ int sf_map_step(int64_t B, int64_t D, float* phi /*[B,D]*/, float* exp_avg /*[B,
                 const float* hi /*[D]*/, float* best_theta /*[B,D]*/, float* best_lp /*[B]*/, float learning_rate,
                 int64_t step, int save_best, void* stream);
 
+/* ---- conditional posteriors: one half-step of the ensemble sampler --------------------
+ * The affine-invariant stretch move (Goodman & Weare 2010; emcee's default move) for N independent catalogue rows x W
+ * walkers, some coordinates of a row held fixed (no handle: the density is the caller's, evaluated between two launches).
+ * One launch does, per row and in this order:
+ *   resolve != 0  the pending proposals prop[i] of half-step `half_step - 1`, given their log-density lp_prop[i]: walker w
+ *                 takes its proposal iff it lies inside [lo, hi], lp_prop is finite and
+ *                 log u < (n_i - 1) log z + lp_prop - lp[i, w]; lp and accepted[i] (+= accepted moves) follow
+ *   collect >= 0  walkers[i] and lp[i] are copied to slots collect * W + w of out[i] / out_lp[i] (slots >= S dropped)
+ *   propose != 0  the active walkers w % 2 == half_step % 2 write prop[i, w / 2, :] = theta_j + z (theta_w - theta_j) on the
+ *                 free coordinates (fixed ones: theta_w copied), partner j = 2 * (((r0 >> 9) * (W / 2)) >> 23) + 1 - h of the
+ *                 other half, z = (u + 1)^2 / 2
+ * with r = philox4x32_10((p_lo, p_hi, half_step, w), (seed_lo, seed_hi ^ 0x53545200)), p = row_offset + i, u = the uniform
+ * of r1 (z) and of r2 (accept), as in the sampler's stream.  The first call of a chain has resolve = 0 and half_step = 0, the
+ * last one propose = 0.
+ *   fixed[i]   bit d set: coordinate d of row i is fixed (n_i = D minus the set bits); negative: the row is skipped whole
+ *              (nothing of it is read or written: a NaN row of the caller)
+ *   max_fixed  the caller's bound on the set bits of any row; max_fixed >= D (an empty free set) is refused, and a row that
+ *              breaks the bound is skipped
+ *   W          even, 4 <= W <= 64;  D in 1..16;  lo / hi NULL (both): no box;  out_lp, trace_* may be NULL
+ *   trace_partner / trace_accept [N, W/2]: the partner of every proposal written / the flag of every proposal resolved
+ * Replaces: one Python chain per object behind sbi.analysis.conditional_potential + an MCMC posterior [UPSTREAM sbi]. */
+int sf_stretch_step(int64_t N, int64_t D, int64_t W, int64_t max_fixed, float* walkers /*[N,W,D]*/, float* lp /*[N,W]*/,
+                    const int32_t* fixed /*[N]*/, const float* lo /*[D]*/, const float* hi /*[D]*/,
+                    const float* lp_prop /*[N,W/2]*/, float* prop /*[N,W/2,D]*/, int32_t* accepted /*[N]*/,
+                    float* out /*[N,S,D]*/, float* out_lp /*[N,S]*/, int64_t S, int64_t collect, uint64_t seed,
+                    int64_t row_offset, int64_t half_step, int resolve, int propose, int32_t* trace_partner,
+                    int32_t* trace_accept, void* stream);
+
 /* ---- sampling direction -------------------------------------------------------------
  * Parity hook: theta = inverse(z | x), logdet = log|det d theta / d z|  (may be NULL). */
 int sf_flow_inverse_from_noise(sf_flow* f, const float* z /*[B,D]*/, const float* x /*[B,C]*/,

@@ -1188,8 +1188,18 @@ class SBI_Fitter:
                       return_feature_array: bool = False, return_full_samples: bool = False,
                       missing_data_mcmc: bool = False, missing_data_mcmc_params: Optional[dict] = None,
                       missing_data_sigma=None, check_out_of_distribution: bool = False, outlier_methods=None,
-                      map_estimate: bool = False, map_kwargs: Optional[dict] = None, **unknown):
+                      map_estimate: bool = False, map_kwargs: Optional[dict] = None,
+                      fixed_parameters: Optional[dict] = None, conditional_kwargs: Optional[dict] = None, **unknown):
         """Sampling + quantile section of the reference's fit_catalogue (sbi_runner.py:3230-3282).
+
+        ``fixed_parameters`` (an addition; default None: the call is what it was): a dict from parameter name to a scalar,
+        an (N,) array or the name of a column of ``observations`` -- the rows where it holds a finite value are fitted with
+        that parameter held at it (``sample_conditional_posterior``; ``conditional_kwargs``: its keywords).  Their quantile
+        columns come from the conditional draws, so a fixed parameter's quantiles equal its value, and the table gains
+        ``conditional_acceptance`` (NaN where nothing was fixed).  Rows whose fixed entries are all NaN are sampled as
+        without the keyword, bit for bit; masked, out-of-distribution and missing-band rows stay NaN; the ``map_estimate``
+        columns stay those of the unconditional posterior.  Not combined with ``missing_data_mcmc``.  Under a process group
+        every rank runs the whole conditional call.
 
         ``map_estimate=True`` (an addition; default False: the call is what it was): the table gains ``{param}_map`` per
         parameter and ``map_log_prob`` -- the posterior mode of every row by ``calculate_MAP`` (``map_kwargs``: its
@@ -1223,6 +1233,18 @@ class SBI_Fitter:
         import pandas as pd
         _warn_unknown("fit_catalogue", unknown)
         return_samples = return_samples or return_full_samples
+        if fixed_parameters is not None and not return_feature_array:
+            if missing_data_mcmc:
+                raise ValueError("fit_catalogue: fixed_parameters cannot be combined with missing_data_mcmc=True (the pooled draws "
+                                 "of an imputed row are unconditional)")
+            return self._fit_catalogue_conditional(
+                observations, fixed_parameters, conditional_kwargs,
+                dict(columns_to_feature_names=columns_to_feature_names, num_samples=num_samples, quantiles=quantiles,
+                     sample_method=sample_method, append_to_input=append_to_input, return_samples=return_samples,
+                     log_times=log_times, seed=seed, device_quantiles=device_quantiles, flux_units=flux_units,
+                     missing_data_flag=missing_data_flag, override_transformations=override_transformations,
+                     timeout_seconds_per_row=timeout_seconds_per_row, check_out_of_distribution=check_out_of_distribution,
+                     outlier_methods=outlier_methods, map_estimate=map_estimate, map_kwargs=map_kwargs))
         ood_kw = dict(check_out_of_distribution=check_out_of_distribution, outlier_methods=outlier_methods)
         ood_kw.update(map_estimate=map_estimate, map_kwargs=map_kwargs)   # (both travel with the check to the inner call)
         if missing_data_mcmc and not return_feature_array:
@@ -1376,6 +1398,105 @@ class SBI_Fitter:
         for i, param in enumerate(self.simple_fitted_parameter_names):
             table[f"{param}_map"] = th[:, i]
         table["map_log_prob"] = lp
+
+    # ---- conditional posteriors (synference_amd/conditional.py) ---------------------------------------------------------------
+    def _fixed_condition(self, fixed_parameters: dict, N: int, table=None) -> np.ndarray:
+        """``fixed_parameters`` -> the (N, D) float32 condition of ``sample_conditional_catalogue`` (NaN = free): a value is a
+        scalar, an (N,) array or -- with ``table`` -- the name of one of its columns.  No GPU needed."""
+        names = list(self.fitted_parameter_names)
+        simple = list(getattr(self, "simple_fitted_parameter_names", None) or names)
+        if not isinstance(fixed_parameters, dict):
+            raise TypeError("fixed_parameters must be a dict from parameter name to a scalar, an (N,) array or a column name")
+        cond = np.full((N, len(names)), np.nan, dtype=np.float32)
+        for key, val in fixed_parameters.items():
+            if key in names:
+                d = names.index(key)
+            elif key in simple:
+                d = simple.index(key)
+            else:
+                raise ValueError(f"fixed_parameters: unknown parameter '{key}'; the fitted parameters are {names}")
+            if isinstance(val, str):
+                if table is None or val not in table:
+                    raise ValueError(f"fixed_parameters['{key}']: '{val}' is not a column of the observations")
+                val = np.asarray(table[val], dtype=np.float64)
+            val = np.asarray(val, dtype=np.float64)
+            if val.ndim > 1 or (val.ndim == 1 and len(val) != N):
+                raise ValueError(f"fixed_parameters['{key}']: a scalar or an (N = {N},) array, not {val.shape}")
+            cond[:, d] = val
+        return cond
+
+    def sample_conditional_posterior(self, X_test: np.ndarray = None, fixed_parameters: dict = None, num_samples: int = 1000,
+                                     posteriors: object = None, seed: Optional[int] = None, row_offset: int = 0,
+                                     **conditional_kwargs) -> np.ndarray:
+        """(num_objects, num_samples, num_parameters) float64 draws with the parameters of ``fixed_parameters`` -- a dict
+        from parameter name to a scalar or an (N,) array, NaN = free in that row -- held at the given values: the first
+        follow-up of an SED fit ("this galaxy has a spectroscopic redshift").  [UPSTREAM] reaches it through
+        ``sbi.analysis.conditional_potential`` behind an MCMC posterior, one Python chain per object; here every row runs
+        an ensemble sampler on the device (``sample_conditional_catalogue``; ``conditional_kwargs``: ``num_walkers``,
+        ``burn_in``, ``thin``, ``num_init_samples``).  The accepted fraction per row -- the diagnostic to quote -- is kept in
+        ``self.last_conditional_acceptance``; NaN rows as there.  Under a process group every rank runs the whole call."""
+        from .conditional import check_conditional_args
+        if posteriors is None:
+            posteriors = self.posteriors
+        if X_test is None:
+            if getattr(self, "_X_test", None) is not None:
+                X_test = self._X_test
+            else:
+                raise ValueError("X_test must be provided or set in the object.")
+        if fixed_parameters is None:
+            raise ValueError("sample_conditional_posterior needs fixed_parameters")
+        X = np.asarray(X_test, dtype=np.float32)
+        if X.ndim == 1:
+            X = X[None, :]
+        kw = dict(num_walkers=64, burn_in=200, thin=5, num_init_samples=1000, dims_to_sample=None)
+        unknown = {k: v for k, v in conditional_kwargs.items() if k not in kw}
+        if unknown:
+            raise TypeError(f"sample_conditional_posterior: unknown keyword(s) {sorted(unknown)}")
+        kw.update(conditional_kwargs)
+        cond = self._fixed_condition(fixed_parameters, len(X))
+        check_conditional_args(num_samples, kw["num_walkers"], kw["burn_in"], kw["thin"], kw["num_init_samples"])
+        from .hostio import to_host_f64
+        s, acc = posteriors.sample_conditional_catalogue(torch.as_tensor(X), cond, num_samples=num_samples, seed=seed,
+                                                         row_offset=int(row_offset), **kw)
+        self.last_conditional_acceptance = acc.double().cpu().numpy()
+        return to_host_f64(s)
+
+    def _fit_catalogue_conditional(self, observations, fixed_parameters, conditional_kwargs, kw):
+        """fit_catalogue(fixed_parameters=...): the ordinary call first, then the rows with something fixed are drawn again
+        from their conditional posterior and their quantile columns replaced.  The streams are keyed by the row's position
+        among the complete rows, like the ordinary call's."""
+        import pandas as pd
+        from .posterior import device_quantiles as _dq, device_quantiles_large as _dql
+        table_in = pd.DataFrame(observations) if isinstance(observations, dict) else observations
+        named = table_in if hasattr(table_in, "columns") else None
+        cond = self._fixed_condition(fixed_parameters, len(table_in), named)
+        ckw = dict(conditional_kwargs or {})
+        out = self.fit_catalogue(observations, **kw)
+        table = out[0] if kw["return_samples"] else out
+        # the complete rows as the ordinary call saw them (their positions key the streams), then the rows it sampled
+        fa_kw = {k: kw[k] for k in ("columns_to_feature_names", "flux_units", "missing_data_flag", "override_transformations")}
+        good, base_mask = self.fit_catalogue(observations, return_feature_array=True, **fa_kw)
+        pos = np.flatnonzero(~np.asarray(base_mask))
+        final_mask = table["is_outlier"].to_numpy(bool) if kw["check_out_of_distribution"] else np.asarray(base_mask)
+        want = (~final_mask[pos]) & np.isfinite(cond[pos]).any(1)
+        acc = np.full(len(table), np.nan)
+        seed, S, quantiles = kw["seed"], int(kw["num_samples"]), kw["quantiles"]
+        edges = np.flatnonzero(np.diff(np.concatenate([[False], want, [False]]).astype(np.int8)))
+        runs = list(zip(edges[0::2].tolist(), edges[1::2].tolist()))
+        if seed is None and len(runs) > 1:
+            seed = self.posteriors._next_seed(None)
+        for a, b in runs:
+            s_dev, a_dev = self.posteriors.sample_conditional_catalogue(torch.as_tensor(good[a:b]), cond[pos[a:b]], num_samples=S,
+                                                                        seed=seed, row_offset=a, **ckw)
+            q = (_dq if S <= 8192 else _dql)(s_dev, quantiles).double().cpu().numpy()
+            for i, param in enumerate(self.simple_fitted_parameter_names):
+                for j, qv in enumerate(quantiles):
+                    table.iloc[pos[a:b], table.columns.get_loc(f"{param}_{int(qv * 100)}")] = q[:, i, j]
+            acc[pos[a:b]] = a_dev.double().cpu().numpy()
+            if kw["return_samples"]:
+                out[1][pos[a:b]] = s_dev.double().cpu().numpy()
+        table["conditional_acceptance"] = acc
+        return (table, out[1]) if kw["return_samples"] else table
 
     # ---- out-of-distribution check (synference_amd/ood.py) ------------------------------------------------------------------
     def _ood_base(self):

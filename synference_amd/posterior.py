@@ -276,6 +276,27 @@ class FlowPosterior:
         return map_one(self, x, num_iter, num_to_optimize, learning_rate, init_method, num_init_samples, save_best_every,
                        show_progress_bars, force_update, seed)
 
+    # ---- conditional posterior --------------------------------------------------------------
+    def sample_conditional_catalogue(self, X, condition, dims_to_sample=None, num_samples: int = 1000, num_walkers: int = 64,
+                                     burn_in: int = 200, thin: int = 5, num_init_samples: int = 1000,
+                                     seed: Optional[int] = None, row_offset: int = 0, return_log_prob: bool = False,
+                                     _trace: bool = False):
+        """Draws from q(theta_free | theta_fixed, x) for every row of X: (samples [N, S, D], acceptance [N]) float32 device
+        tensors (plus the raw density lp [N, S] with ``return_log_prob``).  ``condition`` is (N, D) or (D,), a NaN entry means
+        "free in that row"; ``dims_to_sample`` ([UPSTREAM] ``sbi.analysis.conditional_potential``'s name) frees those
+        dimensions in every row.  An ensemble of ``num_walkers`` walkers per row with the affine-invariant stretch move, on
+        the device: see synference_amd/conditional.py.  Rows with nothing fixed are ``sample_catalogue``'s draws
+        (acceptance 1); a row whose fixed value lies outside the prior box, or is not finite, is NaN.  ``acceptance`` -- the
+        accepted fraction of the row's proposals -- is the diagnostic to quote with the draws."""
+        from .conditional import conditional_catalogue
+        return conditional_catalogue(self, [self], None, X, condition, dims_to_sample, num_samples, num_walkers, burn_in, thin,
+                                     num_init_samples, seed, row_offset, return_log_prob, _trace)
+
+    def sample_conditional(self, sample_shape=(1,), x=None, condition=None, dims_to_sample=None, seed: Optional[int] = None,
+                           **kwargs):
+        from .conditional import sample_conditional_one
+        return sample_conditional_one(self, sample_shape, x, condition, dims_to_sample, seed, **kwargs)
+
 
 class EnsemblePosterior:
     """Weighted mixture of posteriors ([UPSTREAM] sbi EnsemblePosterior; built in the reference at
@@ -402,6 +423,27 @@ class EnsemblePosterior:
         from .map import map_one
         return map_one(self, x, num_iter, num_to_optimize, learning_rate, init_method, num_init_samples, save_best_every,
                        show_progress_bars, force_update, seed)
+
+    # ---- conditional posterior --------------------------------------------------------------
+    def sample_conditional_catalogue(self, X, condition, dims_to_sample=None, num_samples: int = 1000, num_walkers: int = 64,
+                                     burn_in: int = 200, thin: int = 5, num_init_samples: int = 1000,
+                                     seed: Optional[int] = None, row_offset: int = 0, return_log_prob: bool = False,
+                                     _trace: bool = False):
+        """Draws from q(theta_free | theta_fixed, x) for every row of X: (samples [N, S, D], acceptance [N]) float32 device
+        tensors (plus the raw density lp [N, S] with ``return_log_prob``).  ``condition`` is (N, D) or (D,), a NaN entry means
+        "free in that row"; ``dims_to_sample`` ([UPSTREAM] ``sbi.analysis.conditional_potential``'s name) frees those
+        dimensions in every row.  An ensemble of ``num_walkers`` walkers per row with the affine-invariant stretch move, on
+        the device: see synference_amd/conditional.py.  Rows with nothing fixed are ``sample_catalogue``'s draws
+        (acceptance 1); a row whose fixed value lies outside the prior box, or is not finite, is NaN.  ``acceptance`` -- the
+        accepted fraction of the row's proposals -- is the diagnostic to quote with the draws."""
+        from .conditional import conditional_catalogue
+        return conditional_catalogue(self, self.posteriors, self._weights, X, condition, dims_to_sample, num_samples, num_walkers, burn_in, thin,
+                                     num_init_samples, seed, row_offset, return_log_prob, _trace)
+
+    def sample_conditional(self, sample_shape=(1,), x=None, condition=None, dims_to_sample=None, seed: Optional[int] = None,
+                           **kwargs):
+        from .conditional import sample_conditional_one
+        return sample_conditional_one(self, sample_shape, x, condition, dims_to_sample, seed, **kwargs)
 
 
 def _checked_q(quantiles) -> np.ndarray:
